@@ -124,7 +124,7 @@ def test_bench_collective_branch_runs_on_hardware(tmp_path):
     import sys
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29577", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--scene", "hw11", "--width", "320", "--height", "192",
-                        "--steps", "3", "--warmup", "2", "--in-flight", "2", "--no-cpu-baseline", "--no-alone"],
+                        "--steps", "3", "--warmup", "2", "--in-flight", "2", "--no-cpu-baseline", "--no-alone", "--full"],
                        capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
@@ -133,3 +133,27 @@ def test_bench_collective_branch_runs_on_hardware(tmp_path):
     assert line["frame_matches_counting_build"] is True and line["host_frame_matches_device"] is True
     assert line["pipelined"]["frames_match_one_at_a_time"] is True and line["fallback_frames"] == 0
     assert line["value"] > 0 and line["value_device_resident"] > 0
+
+
+def test_bench_plain_run_dumps_the_delivered_frame(scenes, oracle, tmp_path):
+    """A plain bench.py run (no --full): the headline line of exactly --steps timed steps, none of the extra measurements, and
+    --dump-outputs writes the frame its last timed step delivered to host memory -- the oracle's frame of the same scene, bit for bit."""
+    import json
+    import sys
+    import numpy as np
+    from helpers import assert_same_floats
+    out_dir = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scene", "hw11", "--width", "320", "--height", "192",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(out_dir)],
+                       capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
+    assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0 and line["fallback_frames"] == 0
+    assert line["unit"] == "Mpixels/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    for extra in ("cpu_baseline", "pipelined", "value_device_resident", "roofline", "kernel_ms", "frame_matches_counting_build"):
+        assert extra not in line, extra
+    got = np.load(str(out_dir / "frame.npy"))
+    assert got.dtype == np.float32 and got.shape == (192, 320, 3)
+    scene = scenes.make("hw11", width=320, height=192)
+    want, _ = oracle.OracleScene(scenes.to_blob(scene)).render(scenes.CONFIGS["hw11"][3])
+    assert_same_floats(got, want, "bench.py --dump-outputs frame")

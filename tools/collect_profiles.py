@@ -21,7 +21,7 @@ LEVELS = "bvh_trace_queue<0"     # the frame's critical path below level 0
 import importlib
 sys.path.insert(0, root)
 CSRC = importlib.import_module("course-assignment-danielhalachev_amd").csrc_sha256()
-BENCH = ["--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--in-flight", "0"]
+BENCH = ["--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline", "--in-flight", "0"]
 
 
 def run(args, name, extra=()):
@@ -123,7 +123,7 @@ if dom:
     doc = {"csrc_sha256": CSRC,
            key: {"kernel": dom[0], "per_launch": per, "launches": max(v["launches"] for v in pmc[dom[0]].values()),
                  "clock_ghz": round(clock, 4) if clock else 2.0, "kernel_ms_in_the_clock_pass": round(ms_in_pass, 4) if clock else None,
-                 "how": "rocprofv3 --pmc <group> -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --in-flight 0 --no-alone --tuning level_queue=513 (the level queue's launch behind level 0: launches are serialised while counting), one pass per group "
+                 "how": "rocprofv3 --pmc <group> -- python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --in-flight 0 --no-alone --tuning level_queue=513 (the level queue's launch behind level 0: launches are serialised while counting), one pass per group "
                         "(tools/collect_profiles.py); counts averaged over the launches of the kernel in the pass"}}
     lev = [k for k in pmc if k.startswith(LEVELS)]
     if lev and clock_levels:

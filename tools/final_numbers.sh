@@ -5,7 +5,7 @@ out=gpurun_out/final_$tag
 mkdir -p $out
 export TMPDIR=/tmp
 set -e
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench_default.err
+timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full > $out/bench_default.json 2> $out/bench_default.err
 timeout -k 10 700 python tools/collect_profiles.py $tag > $out/collect.log 2>&1
 timeout -k 10 200 python tools/trace_levels.py hw14 $tag > $out/trace_hw14.txt 2>&1
 for s in hw14 hw11 hw12 hw08 hw07; do timeout -k 10 200 python tools/bvh_sweep.py $s "" >> $out/frames.txt 2>&1; done
