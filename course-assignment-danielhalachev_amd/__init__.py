@@ -100,6 +100,29 @@ class Stats(C.Structure):
                                                    "shadow_rays")}
 
 
+# ---- ray queries (include/crt_hip.h: crt_trace_rays*, crt_occluded_rays*, crt_camera_rays_device)
+RAY_PRIMARY, RAY_SHADOW, RAY_REFLECTION, RAY_REFRACTION = range(4)   # enum RayType, Ray.h:14
+
+
+class Ray(C.Structure):
+    """crt_ray, 24 bytes"""
+    _fields_ = [("origin", C.c_float * 3), ("direction", C.c_float * 3)]
+
+
+class Hit(C.Structure):
+    """crt_hit, 48 bytes"""
+    _fields_ = [("t", C.c_float), ("point", C.c_float * 3), ("normal", C.c_float * 3), ("u", C.c_float), ("v", C.c_float),
+                ("mesh", C.c_uint32), ("triangle", C.c_uint32), ("hit", C.c_uint32)]
+
+
+class QueryStats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("hits", C.c_uint64), ("rerouted", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+# crt_hit as a numpy record (what Tracer.trace_rays returns, and the layout of a torch.uint8 [n, 48] output tensor)
+HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, 3), ("normal", np.float32, 3), ("u", np.float32), ("v", np.float32),
+                      ("mesh", np.uint32), ("triangle", np.uint32), ("hit", np.uint32)])
+
 MODE_STREAM, MODE_LANES = range(2)
 
 
@@ -138,6 +161,8 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_tuning_defaults", "crt_create_tuned",
                   "crt_get_stats", "crt_get_kernel_counters", "crt_synchronize", "crt_destroy", "crt_last_error", "crt_device_count", "crt_test_pow5", "crt_test_gi",
                   "crt_describe_kernels", "crt_debug_stream_counts", "crt_get_executed_counters", "crt_get_executed_plan_tests",
                   "crt_render_async", "crt_wait", "crt_alloc_pinned", "crt_free_pinned",
+                  "crt_trace_rays", "crt_trace_rays_device", "crt_occluded_rays", "crt_occluded_rays_device", "crt_camera_rays_device",
+                  "crt_get_query_stats",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -183,6 +208,12 @@ def lib():
     L.crt_kernel_elapsed_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.crt_kernel_times_ms.argtypes = [vp, C.POINTER(C.c_double), u32, C.POINTER(u32)]
     L.crt_get_stats.argtypes = [vp, C.POINTER(Stats)]
+    L.crt_trace_rays.argtypes = [vp, vp, C.c_uint64, u32, vp]
+    L.crt_trace_rays_device.argtypes = [vp, vp, C.c_uint64, u32, vp, vp]
+    L.crt_occluded_rays.argtypes = [vp, vp, vp, C.c_uint64, vp]
+    L.crt_occluded_rays_device.argtypes = [vp, vp, vp, C.c_uint64, vp, vp]
+    L.crt_camera_rays_device.argtypes = [vp, vp, vp]
+    L.crt_get_query_stats.argtypes = [vp, C.POINTER(QueryStats)]
     L.crt_get_kernel_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.crt_synchronize.argtypes = [vp]
     L.crt_destroy.argtypes = [vp]
@@ -511,6 +542,61 @@ class Tracer:
 
     def wait(self):
         self._check(lib().crt_wait(self.ctx))
+
+    # ---- ray queries: closest hit / occlusion for the caller's rays (include/crt_hip.h has the contract)
+    def _single(self, what):
+        if len(self.devices) > 1:
+            raise RuntimeError("%s: ray queries are not available on a multi-device tracer (devices=...); create a Tracer on one device"
+                               % what)
+
+    @staticmethod
+    def _rays_array(rays):
+        rays = np.ascontiguousarray(rays, dtype=np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise ValueError("rays: expected shape [n, 6] (origin xyz, direction xyz), got %r" % (rays.shape,))
+        return rays
+
+    def trace_rays(self, rays, ray_type=RAY_REFLECTION):
+        """Closest hit of each ray (AccelerationStructure::intersect): rays float32 [n, 6] = origin, direction (used as given, not
+        normalised) -> numpy record array of crt_hit (HIT_DTYPE)."""
+        self._single("trace_rays")
+        rays = self._rays_array(rays)
+        out = np.zeros(len(rays), dtype=HIT_DTYPE)
+        self._check(lib().crt_trace_rays(self.ctx, _p(rays), len(rays), ray_type, _p(out)))
+        return out
+
+    def occluded_rays(self, rays, max_distance):
+        """checkForIntersection(ray, max_distance) of each (shadow) ray -> bool [n]; max_distance: a number or an array [n]."""
+        self._single("occluded_rays")
+        rays = self._rays_array(rays)
+        dist = np.ascontiguousarray(np.broadcast_to(np.asarray(max_distance, dtype=np.float32), (len(rays),)))
+        out = np.zeros(len(rays), dtype=np.uint8)
+        self._check(lib().crt_occluded_rays(self.ctx, _p(rays), _p(dist), len(rays), _p(out)))
+        return out.astype(bool)
+
+    def trace_rays_device(self, d_rays_ptr, n, ray_type, d_hits_ptr, stream_ptr=None):
+        """The same on device memory (e.g. torch tensors' data_ptr(): rays float32 [n, 6], hits uint8 [n, 48]), asynchronous on the stream."""
+        self._single("trace_rays_device")
+        self._check(lib().crt_trace_rays_device(self.ctx, C.c_void_p(d_rays_ptr), n, ray_type, C.c_void_p(d_hits_ptr),
+                                                C.c_void_p(stream_ptr or 0)))
+
+    def occluded_rays_device(self, d_rays_ptr, d_max_distance_ptr, n, d_out_ptr, stream_ptr=None):
+        """rays float32 [n, 6], max_distance float32 [n], out uint8 [n]; asynchronous on the stream."""
+        self._single("occluded_rays_device")
+        self._check(lib().crt_occluded_rays_device(self.ctx, C.c_void_p(d_rays_ptr), C.c_void_p(d_max_distance_ptr), n,
+                                                   C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
+
+    def camera_rays_device(self, d_rays_ptr, stream_ptr=None):
+        """RayTracer::getRay at every pixel centre with the current camera: float32 [H * W, 6], row-major, into device memory."""
+        self._single("camera_rays_device")
+        self._check(lib().crt_camera_rays_device(self.ctx, C.c_void_p(d_rays_ptr), C.c_void_p(stream_ptr or 0)))
+
+    def query_stats(self) -> QueryStats:
+        """rays / hits / rerouted / kernel_ms of the last query call (waits for it)."""
+        self._single("query_stats")
+        s = QueryStats()
+        self._check(lib().crt_get_query_stats(self.ctx, C.byref(s)))
+        return s
 
     def kernels(self):
         """{'level0': ..., 'shadow0': ..., 'levels': ...}: the kernels a production frame runs (names as rocprofv3 prints them)."""

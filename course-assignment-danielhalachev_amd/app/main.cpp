@@ -16,7 +16,8 @@ int main(int argc, char **argv) {
   if (argc < 3) {
     std::fprintf(stderr,
                  "usage: %s scene.crtscene out.ppm [--folder DIR] [--depth N] [--mode 0..9] [--device D | --devices 0-7 | --devices 0,2,5] [--repeat K]\n"
-                 "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL [--seed S]]   (RenderOptions::USE_GI, RayTracer.h:27-30)\n",
+                 "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL [--seed S]]   (RenderOptions::USE_GI, RayTracer.h:27-30)\n"
+                 "       [--probe ROW COL]   (no render: the closest hit of that pixel's camera ray; out.ppm is not written)\n",
                  argv[0]);
     return 2;
   }
@@ -26,6 +27,8 @@ int main(int argc, char **argv) {
   std::vector<int> devices;  // --devices: the frame's tiles over several GPUs (first one gathers)
   bool useGI = false;
   unsigned giSamples = 2, raysPerPixel = 1, seed = 0;
+  bool probe = false;
+  unsigned probeRow = 0, probeCol = 0;
   for (int i = 3; i < argc; i++) {
     if (!strcmp(argv[i], "--folder") && i + 1 < argc) folder = argv[++i];
     else if (!strcmp(argv[i], "--depth") && i + 1 < argc) depth = (unsigned)atoi(argv[++i]);
@@ -46,6 +49,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--repeat") && i + 1 < argc) repeat = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--gi") && i + 2 < argc) { useGI = true; giSamples = (unsigned)atoi(argv[++i]); raysPerPixel = (unsigned)atoi(argv[++i]); }
     else if (!strcmp(argv[i], "--seed") && i + 1 < argc) seed = (unsigned)strtoul(argv[++i], nullptr, 0);
+    else if (!strcmp(argv[i], "--probe") && i + 2 < argc) { probe = true; probeRow = (unsigned)atoi(argv[++i]); probeCol = (unsigned)atoi(argv[++i]); }
   }
   try {
     crt::SceneParser parser;
@@ -54,6 +58,18 @@ int main(int argc, char **argv) {
     std::unique_ptr<crt::RayTracer> tracerPtr(devices.size() > 0 ? new crt::RayTracer(scene, devices) : new crt::RayTracer(scene, device));
     crt::RayTracer &tracer = *tracerPtr;
     auto t1 = std::chrono::high_resolution_clock::now();
+    if (probe) {
+      // picking: RayTracer::getRay at the pixel's centre (RayTracer.cpp:61-80), AccelerationStructure::intersect for it (KDTree.cpp:127-192)
+      const unsigned W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
+      if (probeRow >= H || probeCol >= W) { std::fprintf(stderr, "error: --probe %u %u is outside the %ux%u image\n", probeRow, probeCol, W, H); return 2; }
+      const crt_ray ray = tracer.cameraRays()[(size_t)probeRow * W + probeCol];
+      const crt_hit h = tracer.traceRays(std::vector<crt_ray>(1, ray), CRT_RAY_PRIMARY)[0];
+      // (%a: the floats exactly)
+      if (!h.hit) std::printf("probe row %u col %u: no hit\n", probeRow, probeCol);
+      else std::printf("probe row %u col %u: mesh %u triangle %u t %a point %a %a %a normal %a %a %a\n", probeRow, probeCol, h.mesh, h.triangle,
+                       (double)h.t, (double)h.point[0], (double)h.point[1], (double)h.point[2], (double)h.normal[0], (double)h.normal[1], (double)h.normal[2]);
+      return 0;
+    }
     crt::RenderOptions options((crt::RenderOptimization)mode, depth, useGI, giSamples, raysPerPixel);
     tracer.setGISeed(seed);  // frame r of this run uses seed + r (the reference's GI frames all differ: clock() ^ thread id)
     double best = 1e30;

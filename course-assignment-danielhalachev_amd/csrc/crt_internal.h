@@ -4,6 +4,7 @@
 //   crt_launch.hip    the kernels and one frame's launches: frame plan, queue sizing, events
 //   crt_abi.hip       the render entry points, tiles, statistics
 //   crt_multi.hip     one scene on several devices behind one call
+//   crt_query.hip     ray queries: closest hit / occlusion for the caller's rays, the camera's rays
 //   crt_testhooks.hip unit-test hooks (libcrt_hip_test.so only)
 #pragma once
 
@@ -109,6 +110,7 @@ struct crt_ctx {
     uint32_t grid_blocks = 0;
     crt_stats stats{};
     int num_cus = 0;
+    struct crt_query_state *query = nullptr;   // crt_query.hip: the ray queries' scratch and statistics, created by the first query
 };
 
 // constants that round 2 carried as crt_tuning fields (DESIGN.md section 7 has the measurements)
@@ -143,6 +145,8 @@ CRT_INTERNAL int ensure_items(crt_ctx *ctx, size_t n);
 CRT_INTERNAL int launch_render(crt_ctx *ctx, const crt_options *o, uint32_t n_items, float *d_out, uint32_t packed, hipStream_t stream);
 CRT_INTERNAL void note_overflow(crt_ctx *ctx);
 CRT_INTERNAL int fetch_counters(crt_ctx *ctx, const crt_options *o, uint64_t pixels);
+// ---- crt_query.hip
+CRT_INTERNAL void query_destroy(crt_ctx *ctx);
 // ---- crt_abi.hip
 CRT_INTERNAL uint64_t coverage_items(uint32_t width, uint32_t height, const crt_rect *rects, uint32_t n_rects, std::vector<WorkItem> &items);
 CRT_INTERNAL void launch_unpack_items(const float *packed, const WorkItem *items, uint32_t n_items, float *frame, uint32_t width, uint32_t height,

@@ -1,0 +1,258 @@
+// crt_query.hip -- ray queries (include/crt_hip.h: crt_trace_rays*, crt_occluded_rays*, crt_camera_rays_device, crt_get_query_stats):
+// closest hit and occlusion for rays the caller supplies.  Replaces AccelerationStructure::intersect (KDTree.cpp:127-192) and
+// AccelerationStructure::checkForIntersection (AccelerationStructure.cpp:56-94) as entry points of their own; the kernels are
+// csrc/kernel_query.h.  A query reads the context's scene and nothing of its frames: the scratch below is the queries' own.
+#include "crt_internal.h"
+#include "glibc_powf.h"
+
+namespace {
+
+// (the frame kernels of these headers are crt_launch.hip's: this file launches none of them)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-function"
+#include "kernel_lane.h"
+#include "kernel_stream.h"
+#include "kernel_bvh.h"
+#include "kernel_query.h"
+#pragma clang diagnostic pop
+
+// rays per launch: indices, the cursor's overshoot (claimed and dropped) and the list's length stay well inside 31 bits
+constexpr uint64_t QUERY_LAUNCH_RAYS = 1ull << 27;
+// rays per round trip of the host variants (their device copies: 24 + 48 bytes a ray)
+constexpr uint64_t QUERY_HOST_RAYS = 1ull << 22;
+
+}  // namespace
+
+struct crt_query_state {
+    FrameArgs *d_frame = nullptr;     // an all-zero frame block: the reference-order walk reads use_gi (0: shadow rays skip refractive meshes)
+    uint32_t *d_words = nullptr;      // QW_*
+    uint32_t *h_words = nullptr;      // pinned: the words of the last call, copied behind its last launch
+    uint32_t *d_list = nullptr;       // reroute list
+    uint64_t list_cap = 0;
+    uint32_t *d_spill = nullptr;      // walk-stack spill columns of the query grid (never FrameArgs::bvh_spill: a frame's kernels may run beside)
+    crt_ray *d_rays = nullptr;        // device copies of the host variants' arrays
+    float *d_dist = nullptr;
+    crt_hit *d_hits = nullptr;
+    uint8_t *d_occ = nullptr;
+    uint64_t stage_cap = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the launches of the last device call
+    hipStream_t last_stream = nullptr;
+    bool open = false;                // ... whose words and events have not been read yet
+    crt_query_stats stats{};          // of the last call
+};
+
+void query_destroy(crt_ctx *ctx) {
+    crt_query_state *q = ctx->query;
+    if (!q) return;
+    if (q->d_frame) (void)hipFree(q->d_frame);
+    if (q->d_words) (void)hipFree(q->d_words);
+    if (q->h_words) (void)hipHostFree(q->h_words);
+    if (q->d_list) (void)hipFree(q->d_list);
+    if (q->d_spill) (void)hipFree(q->d_spill);
+    if (q->d_rays) (void)hipFree(q->d_rays);
+    if (q->d_dist) (void)hipFree(q->d_dist);
+    if (q->d_hits) (void)hipFree(q->d_hits);
+    if (q->d_occ) (void)hipFree(q->d_occ);
+    if (q->ev0) (void)hipEventDestroy(q->ev0);
+    if (q->ev1) (void)hipEventDestroy(q->ev1);
+    delete q;
+    ctx->query = nullptr;
+}
+
+// the words and events of the last device call, once: waits for it
+static int query_harvest(crt_ctx *ctx) {
+    crt_query_state *q = ctx->query;
+    if (!q || !q->open) return CRT_OK;
+    CRT_HIP_CHECK(ctx, hipEventSynchronize(q->ev1));
+    q->open = false;
+    float ms = 0;
+    CRT_HIP_CHECK(ctx, hipEventElapsedTime(&ms, q->ev0, q->ev1));
+    q->stats.kernel_ms += ms;
+    memcpy(&q->stats.hits, q->h_words + QW_HITS, sizeof(uint64_t));          // (totals of the call: its launches add to the same words)
+    memcpy(&q->stats.rerouted, q->h_words + QW_REROUTED, sizeof(uint64_t));
+    return CRT_OK;
+}
+
+static bool uses_filter(const crt_ctx *ctx) { return ctx->scene.bvh_ok && ctx->tuning.bvh; }
+
+// what every query needs, allocated by the first one; the list follows the largest launch asked for
+static int query_prepare(crt_ctx *ctx, uint64_t launch_rays, hipStream_t stream) {
+    if (ctx->pending) {   // a frame enqueued by crt_render_async: finish it first, as a second crt_render_async does
+        int rc = crt_wait(ctx);
+        if (rc) return rc;
+    }
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->query) ctx->query = new (std::nothrow) crt_query_state;
+    crt_query_state *q = ctx->query;
+    if (!q) { ctx->error = "out of memory"; return CRT_ERR_NOMEM; }
+    if (!q->d_words) {
+        CRT_HIP_CHECK(ctx, hipMalloc((void **)&q->d_frame, sizeof(FrameArgs)));
+        CRT_HIP_CHECK(ctx, hipMemset(q->d_frame, 0, sizeof(FrameArgs)));
+        CRT_HIP_CHECK(ctx, hipMalloc((void **)&q->d_words, QW_WORDS * sizeof(uint32_t)));
+        CRT_HIP_CHECK(ctx, hipHostMalloc((void **)&q->h_words, QW_WORDS * sizeof(uint32_t)));
+        memset(q->h_words, 0, QW_WORDS * sizeof(uint32_t));
+        if (ctx->scene.bvh_ok && ctx->scene.bvh_stack > BVH_LDS_STACK)
+            CRT_HIP_CHECK(ctx, hipMalloc((void **)&q->d_spill, (size_t)ctx->grid_blocks * BLOCK * (ctx->scene.bvh_stack - BVH_LDS_STACK) * sizeof(uint32_t)));
+        CRT_HIP_CHECK(ctx, hipEventCreate(&q->ev0));
+        CRT_HIP_CHECK(ctx, hipEventCreate(&q->ev1));
+    }
+    // the scratch is one call's at a time: a call on another stream waits for the previous call's last launch
+    if (q->open && q->last_stream != stream) {
+        int rc = query_harvest(ctx);
+        if (rc) return rc;
+    }
+    if (uses_filter(ctx) && launch_rays > q->list_cap) {
+        CRT_HIP_CHECK(ctx, hipDeviceSynchronize());   // nothing may still be writing the old list
+        if (q->d_list) (void)hipFree(q->d_list);
+        q->d_list = nullptr;
+        q->list_cap = 0;
+        CRT_HIP_CHECK(ctx, hipMalloc((void **)&q->d_list, launch_rays * sizeof(uint32_t)));
+        q->list_cap = launch_rays;
+    }
+    return CRT_OK;
+}
+
+// one device call: n rays in launches of at most QUERY_LAUNCH_RAYS; `first`: the call's counters start at zero
+static int query_run(crt_ctx *ctx, bool occluded, const crt_ray *d_rays, const float *d_dist, uint64_t n, uint32_t ray_type, crt_hit *d_hits,
+                     uint8_t *d_occ, hipStream_t stream, bool first) {
+    int rc = query_prepare(ctx, std::min(n, QUERY_LAUNCH_RAYS), stream);
+    if (rc) return rc;
+    crt_query_state *q = ctx->query;
+    // (a previous call still under way is on the same stream: this one is ordered behind it, and supersedes its statistics)
+    if (first) {
+        q->stats = crt_query_stats{};
+        CRT_HIP_CHECK(ctx, hipMemsetAsync(q->d_words, 0, QW_WORDS * sizeof(uint32_t), stream));
+    }
+    q->stats.rays += n;
+    KernelArgs A{};
+    A.s = (scene_args_p)ctx->d_scene;
+    A.f = (frame_args_p)q->d_frame;
+    const bool filter = uses_filter(ctx);
+    CRT_HIP_CHECK(ctx, hipEventRecord(q->ev0, stream));
+    for (uint64_t done = 0; done < n; done += QUERY_LAUNCH_RAYS) {
+        const uint32_t m = (uint32_t)std::min(n - done, QUERY_LAUNCH_RAYS);
+        if (done || !first) CRT_HIP_CHECK(ctx, hipMemsetAsync(q->d_words, 0, QW_HITS * sizeof(uint32_t), stream));   // cursors and list length; the totals stay
+        QueryArgs Q{};
+        Q.rays = d_rays + done;
+        Q.max_distance = occluded ? d_dist + done : nullptr;
+        Q.hits = occluded ? nullptr : d_hits + done;
+        Q.occluded = occluded ? d_occ + done : nullptr;
+        Q.n = m;
+        Q.ray_type = ray_type;
+        Q.words = q->d_words;
+        Q.list = q->d_list;
+        Q.spill = q->d_spill;
+        Q.direct = filter ? 0u : 1u;
+        Q.chunk = std::max(64u, (ctx->tuning.fetch_chunk >> 16) & ~63u);   // (level 0's claim size, crt_tuning::fetch_chunk)
+        const uint32_t blocks = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(ctx->grid_blocks, ((uint64_t)m + BLOCK - 1) / BLOCK));
+        if (filter) {
+            if (occluded) hipLaunchKernelGGL(query_occluded<BVH_PLAIN>, dim3(blocks), dim3(BLOCK), 0, stream, A, Q);
+            else hipLaunchKernelGGL(query_closest<BVH_PLAIN>, dim3(blocks), dim3(BLOCK), 0, stream, A, Q);
+            CRT_HIP_CHECK(ctx, hipGetLastError());
+        }
+        // behind it, for what it listed (all but always nothing: the workgroups leave at once) -- or for every ray
+        if (occluded) hipLaunchKernelGGL(query_reroute<true>, dim3(blocks), dim3(BLOCK), 0, stream, A, Q);
+        else hipLaunchKernelGGL(query_reroute<false>, dim3(blocks), dim3(BLOCK), 0, stream, A, Q);
+        CRT_HIP_CHECK(ctx, hipGetLastError());
+    }
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_words, q->d_words, QW_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    CRT_HIP_CHECK(ctx, hipEventRecord(q->ev1, stream));
+    q->last_stream = stream;
+    q->open = true;
+    return CRT_OK;
+}
+
+static int query_check(crt_ctx *ctx, const void *rays, const void *extra, const void *out, uint32_t ray_type, const char *what) {
+    if (!rays || !extra || !out) { ctx->error = std::string(what) + ": NULL array with n > 0"; return CRT_ERR_INVALID; }
+    if (ray_type > (uint32_t)CRT_RAY_REFRACTION) { ctx->error = std::string(what) + ": unknown ray_type " + std::to_string(ray_type); return CRT_ERR_INVALID; }
+    return CRT_OK;
+}
+
+extern "C" int crt_trace_rays_device(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, crt_hit *d_out, void *stream) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    int rc = query_check(ctx, d_rays, d_rays, d_out, ray_type, "crt_trace_rays_device");
+    if (rc) return rc;
+    return query_run(ctx, false, d_rays, nullptr, n, ray_type, d_out, nullptr, (hipStream_t)stream, true);
+}
+
+extern "C" int crt_occluded_rays_device(crt_ctx *ctx, const crt_ray *d_rays, const float *d_max_distance, uint64_t n, uint8_t *d_out, void *stream) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    int rc = query_check(ctx, d_rays, d_max_distance, d_out, CRT_RAY_SHADOW, "crt_occluded_rays_device");
+    if (rc) return rc;
+    return query_run(ctx, true, d_rays, d_max_distance, n, CRT_RAY_SHADOW, nullptr, d_out, (hipStream_t)stream, true);
+}
+
+// the host variants: copy in, run, copy out, QUERY_HOST_RAYS at a time through device copies that are kept for the next call
+static int query_host(crt_ctx *ctx, bool occluded, const crt_ray *rays, const float *dist, uint64_t n, uint32_t ray_type, crt_hit *hits, uint8_t *occ) {
+    int rc = query_prepare(ctx, std::min(n, QUERY_HOST_RAYS), ctx->stream);
+    if (rc) return rc;
+    crt_query_state *q = ctx->query;
+    const uint64_t cap = std::min(n, QUERY_HOST_RAYS);
+    if (cap > q->stage_cap) {
+        CRT_HIP_CHECK(ctx, hipDeviceSynchronize());
+        for (void *p : {(void *)q->d_rays, (void *)q->d_dist, (void *)q->d_hits, (void *)q->d_occ}) if (p) (void)hipFree(p);
+        q->d_rays = nullptr; q->d_dist = nullptr; q->d_hits = nullptr; q->d_occ = nullptr;
+        q->stage_cap = 0;
+        CRT_HIP_CHECK(ctx, hipMalloc((void **)&q->d_rays, cap * sizeof(crt_ray)));
+        CRT_HIP_CHECK(ctx, hipMalloc((void **)&q->d_dist, cap * sizeof(float)));
+        CRT_HIP_CHECK(ctx, hipMalloc((void **)&q->d_hits, cap * sizeof(crt_hit)));
+        CRT_HIP_CHECK(ctx, hipMalloc((void **)&q->d_occ, cap));
+        q->stage_cap = cap;
+    }
+    for (uint64_t done = 0; done < n; done += QUERY_HOST_RAYS) {
+        const uint64_t m = std::min(n - done, QUERY_HOST_RAYS);
+        CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->d_rays, rays + done, m * sizeof(crt_ray), hipMemcpyHostToDevice, ctx->stream));
+        if (occluded) CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->d_dist, dist + done, m * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        rc = query_run(ctx, occluded, q->d_rays, q->d_dist, m, ray_type, q->d_hits, q->d_occ, ctx->stream, done == 0);
+        if (rc) return rc;
+        if (occluded) CRT_HIP_CHECK(ctx, hipMemcpyAsync(occ + done, q->d_occ, m, hipMemcpyDeviceToHost, ctx->stream));
+        else CRT_HIP_CHECK(ctx, hipMemcpyAsync(hits + done, q->d_hits, m * sizeof(crt_hit), hipMemcpyDeviceToHost, ctx->stream));
+        CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        rc = query_harvest(ctx);
+        if (rc) return rc;
+    }
+    return CRT_OK;
+}
+
+extern "C" int crt_trace_rays(crt_ctx *ctx, const crt_ray *rays, uint64_t n, uint32_t ray_type, crt_hit *out) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    int rc = query_check(ctx, rays, rays, out, ray_type, "crt_trace_rays");
+    if (rc) return rc;
+    return query_host(ctx, false, rays, nullptr, n, ray_type, out, nullptr);
+}
+
+extern "C" int crt_occluded_rays(crt_ctx *ctx, const crt_ray *rays, const float *max_distance, uint64_t n, uint8_t *out) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    int rc = query_check(ctx, rays, max_distance, out, CRT_RAY_SHADOW, "crt_occluded_rays");
+    if (rc) return rc;
+    return query_host(ctx, true, rays, max_distance, n, CRT_RAY_SHADOW, nullptr, out);
+}
+
+extern "C" int crt_camera_rays_device(crt_ctx *ctx, crt_ray *d_rays, void *stream) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (!d_rays) { ctx->error = "crt_camera_rays_device: d_rays is NULL"; return CRT_ERR_INVALID; }
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    QueryCamera cam;
+    memcpy(cam.pos, ctx->frame.cam_pos, sizeof(cam.pos));   // the camera of the NEXT frame: crt_set_camera's last word
+    memcpy(cam.m, ctx->frame.cam, sizeof(cam.m));
+    cam.width = ctx->width; cam.height = ctx->height;
+    const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
+    if (pixels == 0) return CRT_OK;
+    hipLaunchKernelGGL(query_camera_rays, dim3((uint32_t)((pixels + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, cam, d_rays);
+    CRT_HIP_CHECK(ctx, hipGetLastError());
+    return CRT_OK;
+}
+
+extern "C" int crt_get_query_stats(crt_ctx *ctx, crt_query_stats *out) {
+    if (!ctx || !out) return CRT_ERR_INVALID;
+    if (!ctx->query) { *out = crt_query_stats{}; return CRT_OK; }
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    int rc = query_harvest(ctx);
+    if (rc) return rc;
+    *out = ctx->query->stats;
+    return CRT_OK;
+}

@@ -573,6 +573,7 @@ extern "C" void crt_destroy(crt_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     for (void *p : ctx->allocs) (void)hipFree(p);
+    query_destroy(ctx);
     if (ctx->d_frame) (void)hipFree(ctx->d_frame);
     if (ctx->d_quant) (void)hipFree(ctx->d_quant);
     if (ctx->d_items) (void)hipFree(ctx->d_items);

@@ -185,6 +185,48 @@ const uint8_t *RayTracer::finishFrame(int slot) {
   return f.rgb8;
 }
 
+// ------------------------------------------------------------------------------------------------ ray queries
+std::vector<crt_hit> RayTracer::traceRays(const std::vector<crt_ray> &rays, unsigned int rayType) {
+  if (multi) throw std::runtime_error("traceRays: not available on a multi-device tracer");
+  std::vector<crt_hit> hits(rays.size());
+  if (crt_trace_rays(ctx, rays.data(), rays.size(), rayType, hits.data()) != CRT_OK)
+    throw std::runtime_error(std::string("traceRays failed: ") + crt_last_error(ctx));
+  return hits;
+}
+
+std::vector<unsigned char> RayTracer::occludedRays(const std::vector<crt_ray> &rays, const std::vector<float> &maxDistance) {
+  if (multi) throw std::runtime_error("occludedRays: not available on a multi-device tracer");
+  if (maxDistance.size() != rays.size()) throw std::runtime_error("occludedRays: one max distance per ray");
+  std::vector<unsigned char> out(rays.size());
+  if (crt_occluded_rays(ctx, rays.data(), maxDistance.data(), rays.size(), out.data()) != CRT_OK)
+    throw std::runtime_error(std::string("occludedRays failed: ") + crt_last_error(ctx));
+  return out;
+}
+
+std::vector<crt_ray> RayTracer::cameraRays() {
+  if (multi) throw std::runtime_error("cameraRays: not available on a multi-device tracer");
+  const size_t n = (size_t)scene.sceneSettings.image.width * scene.sceneSettings.image.height;
+  const Matrix3 &m = camera.getRotationMatrix();
+  const float pos[3] = {camera.getPosition().x, camera.getPosition().y, camera.getPosition().z};
+  // page-locked host memory is the device's to write: the rays need no device buffer of this layer's own
+  crt_ray *pinned = static_cast<crt_ray *>(crt_alloc_pinned((n ? n : 1) * sizeof(crt_ray)));
+  if (!pinned) throw std::runtime_error("out of pinned host memory");
+  int rc = crt_set_camera(ctx, pos, &m.m[0][0]);
+  if (rc == CRT_OK) rc = crt_camera_rays_device(ctx, pinned, nullptr);
+  if (rc == CRT_OK) rc = crt_synchronize(ctx);
+  std::vector<crt_ray> rays;
+  if (rc == CRT_OK) rays.assign(pinned, pinned + n);
+  crt_free_pinned(pinned);
+  if (rc != CRT_OK) throw std::runtime_error(std::string("cameraRays failed: ") + crt_last_error(ctx));
+  return rays;
+}
+
+crt_query_stats RayTracer::queryStats() const {
+  crt_query_stats s{};
+  if (!multi) crt_get_query_stats(ctx, &s);
+  return s;
+}
+
 crt_stats RayTracer::stats() const {
   crt_stats s{};
   if (multi) crt_multi_get_stats(multi, &s);

@@ -93,6 +93,15 @@ class RayTracer {
   int renderAsync(const RenderOptions &renderOptions);
   const uint8_t *finishFrame(int slot);
 
+  // ---- ray queries (crt_hip.h: crt_trace_rays / crt_occluded_rays): what AccelerationStructure::intersect and
+  // AccelerationStructure::checkForIntersection (KDTree.cpp:127-192, AccelerationStructure.cpp:56-94) answer for rays of the
+  // caller's -- directions as given, exact for every ray.  Single-device tracers only (std::runtime_error otherwise).
+  std::vector<crt_hit> traceRays(const std::vector<crt_ray> &rays, unsigned int rayType = CRT_RAY_REFLECTION);
+  std::vector<unsigned char> occludedRays(const std::vector<crt_ray> &rays, const std::vector<float> &maxDistance);
+  // RayTracer::getRay (RayTracer.cpp:61-80) at every pixel centre with the CURRENT camera, row-major
+  std::vector<crt_ray> cameraRays();
+  crt_query_stats queryStats() const;
+
   // flat access for callers that do not want the vector-of-vectors copy
   int renderFlat(const std::string &pathToImage, const RenderOptions &renderOptions, float *outRGB, unsigned int counters = 0);
   crt_ctx *context() const { return multi ? crt_multi_context(multi, 0) : ctx; }

@@ -281,6 +281,59 @@ void crt_destroy(crt_ctx *ctx);
 const char *crt_last_error(const crt_ctx *ctx);
 int crt_device_count(void);
 
+/* ---- Ray queries: closest hit and occlusion for rays the CALLER supplies -- picking, visibility and ambient-occlusion baking
+ * between arbitrary points, a depth / normal / object-id pass.  The reference has these two operations as its seam below shootRay:
+ * AccelerationStructure::intersect (KDTree.cpp:127-192) and AccelerationStructure::checkForIntersection
+ * (AccelerationStructure.cpp:56-94).  Kernels: csrc/kernel_query.h.  Single-device contexts only (not crt_multi).
+ *
+ * crt_trace_rays* returns what AccelerationStructure::intersect returns for Ray{origin, direction, ray_type}: the same winner under
+ *   the reference's collection order (the first collected hit, replaced only by a strictly smaller distance, at both tree levels:
+ *   KDTree.cpp:75-86, 156-167), the same t and point float for float (Ray.cpp:19-23), the face normal or -- for a smooth material --
+ *   the interpolated, normalised one (KDTree.cpp:180-185), (u, v) as Triangle::getBarycentricCoordinates gives them
+ *   (Triangle.cpp:63-73; computed for smooth or textured materials only, otherwise 0).  A winner with t = +inf or NaN (a ray parallel
+ *   to a triangle's plane, Ray.cpp:19) is a hit and is reported as one.  ray_type matters the way it does in the reference:
+ *   CRT_RAY_PRIMARY culls back faces (Ray.cpp:13), the other three behave alike.
+ * crt_occluded_rays* returns checkForIntersection(ray, max_distance[i]) of the non-GI build for a shadow ray
+ *   (AccelerationStructure.cpp:56-94): refractive meshes are skipped (:67-71), a mesh occludes when its closest hit lies within
+ *   length(point - origin) <= max_distance (:73-74).  max_distance may be +inf.  (The GI build's rule -- no mesh is skipped -- is not
+ *   offered.)
+ * Directions are used AS GIVEN, like the reference's Ray holds them (Ray.h): nothing is normalised (RayTracer::getRay and shootRay
+ *   normalise before they build a Ray, RayTracer.cpp:78,420, and so do callers who want that).  The candidate filter's error analysis
+ *   (csrc/kernel_bvh.h) takes |d| = 1 up to rounding, so a ray with | dx^2 + dy^2 + dz^2 - 1 | > 2^-20 (evaluated in float32; every
+ *   float32-rounded unit vector is within 2^-21: csrc/kernel_query.h, QUERY_UNIT_TOL) or with a non-finite coordinate is answered by
+ *   the reference-order walk instead.  The answer is exact for EVERY ray; only the speed differs.
+ * n == 0 is CRT_OK and touches nothing; a NULL array with n > 0 or an unknown ray_type is CRT_ERR_INVALID.  Any n that fits the
+ *   arrays works.  The host variants copy in, run, copy out and return when the result is in `out`.  The device variants are
+ *   asynchronous on `stream` (a hipStream_t, NULL = default) and allocate nothing after the first call of a given size (the scratch
+ *   is the context's: a call on ANOTHER stream than the previous query's first waits for that one).  A query on a context with a
+ *   crt_render_async frame pending first waits for it, as a second crt_render_async does.  A query leaves the persistent colour
+ *   buffer, crt_stats, the ray queues' sizing and fallback_frames exactly as they were. */
+enum { CRT_RAY_PRIMARY = 0, CRT_RAY_SHADOW = 1, CRT_RAY_REFLECTION = 2, CRT_RAY_REFRACTION = 3 };   /* enum RayType, Ray.h:14 */
+typedef struct crt_ray { float origin[3]; float direction[3]; } crt_ray;   /* 24 bytes: Ray's origin and direction (Ray.h) */
+/* Intersection (KDTree.cpp:168-190), 48 bytes */
+typedef struct crt_hit {
+    float t; float point[3]; float normal[3]; float u, v;
+    uint32_t mesh, triangle;   /* triangle: index into crt_scene_desc.triangles (global) */
+    uint32_t hit;              /* 0: the reference reports no intersection; every other field is then 0 */
+} crt_hit;
+typedef struct crt_query_stats {
+    uint64_t rays;             /* rays of the last query call */
+    uint64_t hits;             /* ... with a hit / occluded */
+    uint64_t rerouted;         /* ... answered by the reference-order walk: direction not of unit length, non-finite ray, a miss
+                                * refuted by the miss check, filter stack exhausted; all of them when the scene has no filter or
+                                * crt_tuning::bvh == 0 */
+    double kernel_ms;          /* device time of its launches (HIP events on its stream) */
+} crt_query_stats;
+int crt_trace_rays(crt_ctx *ctx, const crt_ray *rays, uint64_t n, uint32_t ray_type, crt_hit *out);
+int crt_trace_rays_device(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, crt_hit *d_out, void *stream);
+int crt_occluded_rays(crt_ctx *ctx, const crt_ray *rays, const float *max_distance, uint64_t n, uint8_t *out);
+int crt_occluded_rays_device(crt_ctx *ctx, const crt_ray *d_rays, const float *d_max_distance, uint64_t n, uint8_t *d_out, void *stream);
+/* RayTracer::getRay (RayTracer.cpp:61-80) at the centre of every pixel with the camera of crt_set_camera: H*W rays, row-major, to
+ * device memory; asynchronous on `stream`.  The direction is normalised once, as getRay returns it. */
+int crt_camera_rays_device(crt_ctx *ctx, crt_ray *d_rays, void *stream);
+/* statistics of the last query call; waits for it */
+int crt_get_query_stats(crt_ctx *ctx, crt_query_stats *out);
+
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
  * stream per listed device (a device may be listed more than once); the covered 8x8 tiles are dealt round-robin, every
