@@ -123,6 +123,9 @@ class QueryStats(C.Structure):
 HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, 3), ("normal", np.float32, 3), ("u", np.float32), ("v", np.float32),
                       ("mesh", np.uint32), ("triangle", np.uint32), ("hit", np.uint32)])
 
+# direct lighting of the caller's records (include/crt_hip.h: crt_shade_hits*, crt_light_points*): the status of a record
+SHADE_BACKGROUND, SHADE_DIFFUSE, SHADE_RECURSES, SHADE_INVALID = range(4)
+
 MODE_STREAM, MODE_LANES = range(2)
 
 
@@ -162,7 +165,7 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_tuning_defaults", "crt_create_tuned",
                   "crt_describe_kernels", "crt_debug_stream_counts", "crt_get_executed_counters", "crt_get_executed_plan_tests",
                   "crt_render_async", "crt_wait", "crt_alloc_pinned", "crt_free_pinned",
                   "crt_trace_rays", "crt_trace_rays_device", "crt_occluded_rays", "crt_occluded_rays_device", "crt_camera_rays_device",
-                  "crt_get_query_stats",
+                  "crt_get_query_stats", "crt_shade_hits", "crt_shade_hits_device", "crt_light_points", "crt_light_points_device",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -214,6 +217,10 @@ def lib():
     L.crt_occluded_rays_device.argtypes = [vp, vp, vp, C.c_uint64, vp, vp]
     L.crt_camera_rays_device.argtypes = [vp, vp, vp]
     L.crt_get_query_stats.argtypes = [vp, C.POINTER(QueryStats)]
+    L.crt_shade_hits.argtypes = [vp, vp, C.c_uint64, C.POINTER(Options), vp, vp]
+    L.crt_shade_hits_device.argtypes = [vp, vp, C.c_uint64, C.POINTER(Options), vp, vp, vp]
+    L.crt_light_points.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, vp]
+    L.crt_light_points_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, vp, vp]
     L.crt_get_kernel_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.crt_synchronize.argtypes = [vp]
     L.crt_destroy.argtypes = [vp]
@@ -590,6 +597,41 @@ class Tracer:
         """RayTracer::getRay at every pixel centre with the current camera: float32 [H * W, 6], row-major, into device memory."""
         self._single("camera_rays_device")
         self._check(lib().crt_camera_rays_device(self.ctx, C.c_void_p(d_rays_ptr), C.c_void_p(stream_ptr or 0)))
+
+    # ---- direct lighting for the caller's hit records and points (RayTracer::calculateDiffusion; include/crt_hip.h has the contract)
+    def shade_hits(self, hits, shadow_bias=1e-4):
+        """The colour shootRay returns for a ray whose closest hit is hits[i] (records as trace_rays returns them, HIT_DTYPE), wherever
+        it does not recurse -> (rgb float32 [n, 3], status uint8 [n] of SHADE_*)."""
+        self._single("shade_hits")
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE).reshape(-1)
+        rgb = np.zeros((len(hits), 3), dtype=np.float32)
+        status = np.zeros(len(hits), dtype=np.uint8)
+        self._check(lib().crt_shade_hits(self.ctx, _p(hits), len(hits), C.byref(make_options(0, shadow_bias)), _p(rgb), _p(status)))
+        return rgb, status
+
+    def light_points(self, points, normals, shadow_bias=1e-4):
+        """The sum of the unoccluded lights' factors intensity / (4 r^2 pi) * max(0, l . n) at each point: points, normals float32 [n, 3]
+        -> float32 [n] (what a white diffuse surface there is lit with)."""
+        self._single("light_points")
+        points = np.ascontiguousarray(points, dtype=np.float32)
+        normals = np.ascontiguousarray(normals, dtype=np.float32)
+        if points.ndim != 2 or points.shape[1] != 3 or normals.shape != points.shape:
+            raise ValueError("points, normals: expected two arrays of shape [n, 3], got %r and %r" % (points.shape, normals.shape))
+        out = np.zeros(len(points), dtype=np.float32)
+        self._check(lib().crt_light_points(self.ctx, _p(points), _p(normals), len(points), shadow_bias, _p(out)))
+        return out
+
+    def shade_hits_device(self, d_hits_ptr, n, d_rgb_ptr, d_status_ptr=None, shadow_bias=1e-4, stream_ptr=None):
+        """The same on device memory (data_ptr() of: hits uint8 [n, 48], rgb float32 [n, 3], status uint8 [n] or None), asynchronous."""
+        self._single("shade_hits_device")
+        self._check(lib().crt_shade_hits_device(self.ctx, C.c_void_p(d_hits_ptr), n, C.byref(make_options(0, shadow_bias)), C.c_void_p(d_rgb_ptr),
+                                                C.c_void_p(d_status_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def light_points_device(self, d_points_ptr, d_normals_ptr, n, d_out_ptr, shadow_bias=1e-4, stream_ptr=None):
+        """points, normals float32 [n, 3], out float32 [n]; asynchronous on the stream."""
+        self._single("light_points_device")
+        self._check(lib().crt_light_points_device(self.ctx, C.c_void_p(d_points_ptr), C.c_void_p(d_normals_ptr), n, shadow_bias,
+                                                  C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
 
     def query_stats(self) -> QueryStats:
         """rays / hits / rerouted / kernel_ms of the last query call (waits for it)."""

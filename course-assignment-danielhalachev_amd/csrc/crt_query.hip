@@ -1,5 +1,6 @@
 // crt_query.hip -- ray queries (include/crt_hip.h: crt_trace_rays*, crt_occluded_rays*, crt_camera_rays_device, crt_get_query_stats):
-// closest hit and occlusion for rays the caller supplies.  Replaces AccelerationStructure::intersect (KDTree.cpp:127-192) and
+// closest hit and occlusion for rays the caller supplies; and direct lighting for the caller's hit records and points (crt_shade_hits*,
+// crt_light_points*: RayTracer::calculateDiffusion, RayTracer.cpp:300-330; kernels: csrc/kernel_shade.h), on the same scratch.  Replaces AccelerationStructure::intersect (KDTree.cpp:127-192) and
 // AccelerationStructure::checkForIntersection (AccelerationStructure.cpp:56-94) as entry points of their own; the kernels are
 // csrc/kernel_query.h.  A query reads the context's scene and nothing of its frames: the scratch below is the queries' own.
 #include "crt_internal.h"
@@ -14,6 +15,7 @@ namespace {
 #include "kernel_stream.h"
 #include "kernel_bvh.h"
 #include "kernel_query.h"
+#include "kernel_shade.h"
 #pragma clang diagnostic pop
 
 // rays per launch: indices, the cursor's overshoot (claimed and dropped) and the list's length stay well inside 31 bits
@@ -184,12 +186,9 @@ extern "C" int crt_occluded_rays_device(crt_ctx *ctx, const crt_ray *d_rays, con
     return query_run(ctx, true, d_rays, d_max_distance, n, CRT_RAY_SHADOW, nullptr, d_out, (hipStream_t)stream, true);
 }
 
-// the host variants: copy in, run, copy out, QUERY_HOST_RAYS at a time through device copies that are kept for the next call
-static int query_host(crt_ctx *ctx, bool occluded, const crt_ray *rays, const float *dist, uint64_t n, uint32_t ray_type, crt_hit *hits, uint8_t *occ) {
-    int rc = query_prepare(ctx, std::min(n, QUERY_HOST_RAYS), ctx->stream);
-    if (rc) return rc;
+// the device copies of the host variants' arrays, kept for the next call: room for `cap` records
+static int query_stage(crt_ctx *ctx, const uint64_t cap) {
     crt_query_state *q = ctx->query;
-    const uint64_t cap = std::min(n, QUERY_HOST_RAYS);
     if (cap > q->stage_cap) {
         CRT_HIP_CHECK(ctx, hipDeviceSynchronize());
         for (void *p : {(void *)q->d_rays, (void *)q->d_dist, (void *)q->d_hits, (void *)q->d_occ}) if (p) (void)hipFree(p);
@@ -201,6 +200,16 @@ static int query_host(crt_ctx *ctx, bool occluded, const crt_ray *rays, const fl
         CRT_HIP_CHECK(ctx, hipMalloc((void **)&q->d_occ, cap));
         q->stage_cap = cap;
     }
+    return CRT_OK;
+}
+
+// the host variants: copy in, run, copy out, QUERY_HOST_RAYS at a time through device copies that are kept for the next call
+static int query_host(crt_ctx *ctx, bool occluded, const crt_ray *rays, const float *dist, uint64_t n, uint32_t ray_type, crt_hit *hits, uint8_t *occ) {
+    int rc = query_prepare(ctx, std::min(n, QUERY_HOST_RAYS), ctx->stream);
+    if (rc) return rc;
+    crt_query_state *q = ctx->query;
+    rc = query_stage(ctx, std::min(n, QUERY_HOST_RAYS));
+    if (rc) return rc;
     for (uint64_t done = 0; done < n; done += QUERY_HOST_RAYS) {
         const uint64_t m = std::min(n - done, QUERY_HOST_RAYS);
         CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->d_rays, rays + done, m * sizeof(crt_ray), hipMemcpyHostToDevice, ctx->stream));
@@ -230,6 +239,128 @@ extern "C" int crt_occluded_rays(crt_ctx *ctx, const crt_ray *rays, const float 
     int rc = query_check(ctx, rays, max_distance, out, CRT_RAY_SHADOW, "crt_occluded_rays");
     if (rc) return rc;
     return query_host(ctx, true, rays, max_distance, n, CRT_RAY_SHADOW, nullptr, out);
+}
+
+// ---- direct lighting (csrc/kernel_shade.h).  One device call: n records in launches of at most QUERY_LAUNCH_RAYS, on the ray queries'
+// scratch (words, list, spill columns); `points`: crt_light_points (d_a = points, d_b = normals), else crt_shade_hits (d_a = records)
+static int shade_run(crt_ctx *ctx, bool points, const void *d_a, const float *d_b, uint64_t n, float shadow_bias, float *d_out, uint8_t *d_status,
+                     hipStream_t stream, bool first) {
+    int rc = query_prepare(ctx, std::min(n, QUERY_LAUNCH_RAYS), stream);
+    if (rc) return rc;
+    crt_query_state *q = ctx->query;
+    if (first) {
+        q->stats = crt_query_stats{};
+        CRT_HIP_CHECK(ctx, hipMemsetAsync(q->d_words, 0, QW_WORDS * sizeof(uint32_t), stream));
+    }
+    q->stats.rays += n;
+    KernelArgs A{};
+    A.s = (scene_args_p)ctx->d_scene;
+    A.f = (frame_args_p)q->d_frame;   // all zero (use_gi = 0: shadow rays skip refractive meshes); the bias travels in ShadeArgs
+    const bool filter = uses_filter(ctx);
+    CRT_HIP_CHECK(ctx, hipEventRecord(q->ev0, stream));
+    for (uint64_t done = 0; done < n; done += QUERY_LAUNCH_RAYS) {
+        const uint32_t m = (uint32_t)std::min(n - done, QUERY_LAUNCH_RAYS);
+        if (done || !first) CRT_HIP_CHECK(ctx, hipMemsetAsync(q->d_words, 0, QW_HITS * sizeof(uint32_t), stream));   // cursors and list length; the totals stay
+        ShadeArgs S{};
+        S.q.n = m;
+        S.q.words = q->d_words;
+        S.q.list = q->d_list;
+        S.q.spill = q->d_spill;
+        S.q.direct = filter ? 0u : 1u;
+        S.q.chunk = std::max(64u, (ctx->tuning.fetch_chunk >> 16) & ~63u);
+        if (points) { S.points = (const float *)d_a + 3 * done; S.normals = d_b + 3 * done; S.out = d_out + done; }
+        else { S.hits = (const crt_hit *)d_a + done; S.out = d_out + 3 * done; S.status = d_status ? d_status + done : nullptr; }
+        S.shadow_bias = shadow_bias;
+        const uint32_t blocks = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(ctx->grid_blocks, ((uint64_t)m + BLOCK - 1) / BLOCK));
+        if (filter) {
+            if (points) hipLaunchKernelGGL((query_direct<BVH_PLAIN, true>), dim3(blocks), dim3(BLOCK), 0, stream, A, S);
+            else hipLaunchKernelGGL((query_direct<BVH_PLAIN, false>), dim3(blocks), dim3(BLOCK), 0, stream, A, S);
+            CRT_HIP_CHECK(ctx, hipGetLastError());
+        }
+        // behind it, for the records it listed (all but always none) -- or for every record
+        if (points) hipLaunchKernelGGL(query_direct_reroute<true>, dim3(blocks), dim3(BLOCK), 0, stream, A, S);
+        else hipLaunchKernelGGL(query_direct_reroute<false>, dim3(blocks), dim3(BLOCK), 0, stream, A, S);
+        CRT_HIP_CHECK(ctx, hipGetLastError());
+    }
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_words, q->d_words, QW_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    CRT_HIP_CHECK(ctx, hipEventRecord(q->ev1, stream));
+    q->last_stream = stream;
+    q->open = true;
+    return CRT_OK;
+}
+
+static int shade_check(crt_ctx *ctx, const void *a, const void *b, const void *out, const crt_options *options, const char *what) {
+    if (!a || !b || !out) { ctx->error = std::string(what) + ": NULL array with n > 0"; return CRT_ERR_INVALID; }
+    if (options && options->use_gi) {
+        ctx->error = std::string(what) + ": use_gi is not offered (the GI build's occlusion rule and its division by GI_SAMPLE_SIZE + 1)";
+        return CRT_ERR_INVALID;
+    }
+    return CRT_OK;
+}
+
+extern "C" int crt_shade_hits_device(crt_ctx *ctx, const crt_hit *d_hits, uint64_t n, const crt_options *options, float *d_rgb, uint8_t *d_status,
+                                     void *stream) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    int rc = shade_check(ctx, d_hits, options, d_rgb, options, "crt_shade_hits_device");
+    if (rc) return rc;
+    return shade_run(ctx, false, d_hits, nullptr, n, options->shadow_bias, d_rgb, d_status, (hipStream_t)stream, true);
+}
+
+extern "C" int crt_light_points_device(crt_ctx *ctx, const float *d_points, const float *d_normals, uint64_t n, float shadow_bias, float *d_out,
+                                       void *stream) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    int rc = shade_check(ctx, d_points, d_normals, d_out, nullptr, "crt_light_points_device");
+    if (rc) return rc;
+    return shade_run(ctx, true, d_points, d_normals, n, shadow_bias, d_out, nullptr, (hipStream_t)stream, true);
+}
+
+// The host variants, QUERY_HOST_RAYS at a time, through the ray queries' device copies: a record's 48 bytes in d_hits, its colour (12
+// bytes) in d_rays (24 a record), its status in d_occ; a point and its normal (12 + 12 bytes) in the two halves of d_rays, its sum in d_dist
+static int shade_host(crt_ctx *ctx, bool points, const void *a, const float *b, uint64_t n, float shadow_bias, float *out, uint8_t *status) {
+    int rc = query_prepare(ctx, std::min(n, QUERY_HOST_RAYS), ctx->stream);
+    if (rc) return rc;
+    crt_query_state *q = ctx->query;
+    rc = query_stage(ctx, std::min(n, QUERY_HOST_RAYS));
+    if (rc) return rc;
+    float *d_lo = reinterpret_cast<float *>(q->d_rays), *d_hi = d_lo + 3 * q->stage_cap;
+    for (uint64_t done = 0; done < n; done += QUERY_HOST_RAYS) {
+        const uint64_t m = std::min(n - done, QUERY_HOST_RAYS);
+        if (points) {
+            CRT_HIP_CHECK(ctx, hipMemcpyAsync(d_lo, (const float *)a + 3 * done, m * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            CRT_HIP_CHECK(ctx, hipMemcpyAsync(d_hi, b + 3 * done, m * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            rc = shade_run(ctx, true, d_lo, d_hi, m, shadow_bias, q->d_dist, nullptr, ctx->stream, done == 0);
+            if (rc) return rc;
+            CRT_HIP_CHECK(ctx, hipMemcpyAsync(out + done, q->d_dist, m * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        } else {
+            CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->d_hits, (const crt_hit *)a + done, m * sizeof(crt_hit), hipMemcpyHostToDevice, ctx->stream));
+            rc = shade_run(ctx, false, q->d_hits, nullptr, m, shadow_bias, d_lo, q->d_occ, ctx->stream, done == 0);
+            if (rc) return rc;
+            CRT_HIP_CHECK(ctx, hipMemcpyAsync(out + 3 * done, d_lo, m * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+            if (status) CRT_HIP_CHECK(ctx, hipMemcpyAsync(status + done, q->d_occ, m, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        rc = query_harvest(ctx);
+        if (rc) return rc;
+    }
+    return CRT_OK;
+}
+
+extern "C" int crt_shade_hits(crt_ctx *ctx, const crt_hit *hits, uint64_t n, const crt_options *options, float *out_rgb, uint8_t *out_status) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    int rc = shade_check(ctx, hits, options, out_rgb, options, "crt_shade_hits");
+    if (rc) return rc;
+    return shade_host(ctx, false, hits, nullptr, n, options->shadow_bias, out_rgb, out_status);
+}
+
+extern "C" int crt_light_points(crt_ctx *ctx, const float *points, const float *normals, uint64_t n, float shadow_bias, float *out) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    int rc = shade_check(ctx, points, normals, out, nullptr, "crt_light_points");
+    if (rc) return rc;
+    return shade_host(ctx, true, points, normals, n, shadow_bias, out, nullptr);
 }
 
 extern "C" int crt_camera_rays_device(crt_ctx *ctx, crt_ray *d_rays, void *stream) {

@@ -419,8 +419,9 @@ __device__ __forceinline__ void surface_at(const KernelArgs &A, const Ray &R, fl
 
 // One light of RayTracer::calculateDiffusion (RayTracer.cpp:308-318): the shadow ray towards it, its
 // length and the factor (intensity / sphereArea * angle) the albedo is multiplied by when it is unoccluded.
+// (shadow_bias: a frame's kernels take it from the frame's block -- the overload below --, a query from its own arguments)
 __device__ __forceinline__ void light_setup(const KernelArgs &A, uint32_t li, float hpx, float hpy, float hpz, float hnx,
-                                            float hny, float hnz, Ray &R, float &dist, float &kfac) {
+                                            float hny, float hnz, const float shadow_bias, Ray &R, float &dist, float &kfac) {
     const float4 lg = A.s->lights[li];
     float lx = lg.x - hpx, ly = lg.y - hpy, lz = lg.z - hpz;
     dist = len3(lx, ly, lz);
@@ -428,7 +429,11 @@ __device__ __forceinline__ void light_setup(const KernelArgs &A, uint32_t li, fl
     normalize3(lx, ly, lz);
     const float angle = std_max(0.0f, dot3(lx, ly, lz, hnx, hny, hnz));
     kfac = lg.w / area * angle;
-    R.ox = hpx + hnx * A.f->shadow_bias; R.oy = hpy + hny * A.f->shadow_bias; R.oz = hpz + hnz * A.f->shadow_bias;
+    R.ox = hpx + hnx * shadow_bias; R.oy = hpy + hny * shadow_bias; R.oz = hpz + hnz * shadow_bias;
     R.dx = lx; R.dy = ly; R.dz = lz;
     ray_prepare(R);
+}
+__device__ __forceinline__ void light_setup(const KernelArgs &A, uint32_t li, float hpx, float hpy, float hpz, float hnx,
+                                            float hny, float hnz, Ray &R, float &dist, float &kfac) {
+    light_setup(A, li, hpx, hpy, hpz, hnx, hny, hnz, A.f->shadow_bias, R, dist, kfac);
 }

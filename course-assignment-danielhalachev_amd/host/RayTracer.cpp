@@ -221,6 +221,26 @@ std::vector<crt_ray> RayTracer::cameraRays() {
   return rays;
 }
 
+std::vector<float> RayTracer::shadeHits(const std::vector<crt_hit> &hits, float shadowBias, std::vector<unsigned char> *status) {
+  if (multi) throw std::runtime_error("shadeHits: not available on a multi-device tracer");
+  std::vector<float> rgb(hits.size() * 3);
+  if (status) status->assign(hits.size(), 0);
+  crt_options options{};
+  options.shadow_bias = shadowBias;
+  if (crt_shade_hits(ctx, hits.data(), hits.size(), &options, rgb.data(), status ? status->data() : nullptr) != CRT_OK)
+    throw std::runtime_error(std::string("shadeHits failed: ") + crt_last_error(ctx));
+  return rgb;
+}
+
+std::vector<float> RayTracer::lightPoints(const std::vector<float> &points, const std::vector<float> &normals, float shadowBias) {
+  if (multi) throw std::runtime_error("lightPoints: not available on a multi-device tracer");
+  if (points.size() % 3 || normals.size() != points.size()) throw std::runtime_error("lightPoints: three floats per point, one normal per point");
+  std::vector<float> out(points.size() / 3);
+  if (crt_light_points(ctx, points.data(), normals.data(), out.size(), shadowBias, out.data()) != CRT_OK)
+    throw std::runtime_error(std::string("lightPoints failed: ") + crt_last_error(ctx));
+  return out;
+}
+
 crt_query_stats RayTracer::queryStats() const {
   crt_query_stats s{};
   if (!multi) crt_get_query_stats(ctx, &s);

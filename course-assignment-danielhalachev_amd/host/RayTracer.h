@@ -101,6 +101,11 @@ class RayTracer {
   // RayTracer::getRay (RayTracer.cpp:61-80) at every pixel centre with the CURRENT camera, row-major
   std::vector<crt_ray> cameraRays();
   crt_query_stats queryStats() const;
+  // ---- direct lighting (crt_hip.h: crt_shade_hits / crt_light_points): what shootRay returns for a ray whose closest hit is hits[i]
+  // wherever it does not recurse -- calculateDiffusion (RayTracer.cpp:300-330) for a diffuse hit, the background for none --, 3 floats
+  // per record, CRT_SHADE_* per record in *status when it is given; and the lights' unoccluded factors summed at points of the caller's
+  std::vector<float> shadeHits(const std::vector<crt_hit> &hits, float shadowBias = 1e-4f, std::vector<unsigned char> *status = nullptr);
+  std::vector<float> lightPoints(const std::vector<float> &points, const std::vector<float> &normals, float shadowBias = 1e-4f);
 
   // flat access for callers that do not want the vector-of-vectors copy
   int renderFlat(const std::string &pathToImage, const RenderOptions &renderOptions, float *outRGB, unsigned int counters = 0);

@@ -331,8 +331,42 @@ int crt_occluded_rays_device(crt_ctx *ctx, const crt_ray *d_rays, const float *d
 /* RayTracer::getRay (RayTracer.cpp:61-80) at the centre of every pixel with the camera of crt_set_camera: H*W rays, row-major, to
  * device memory; asynchronous on `stream`.  The direction is normalised once, as getRay returns it. */
 int crt_camera_rays_device(crt_ctx *ctx, crt_ray *d_rays, void *stream);
-/* statistics of the last query call; waits for it */
+/* statistics of the last query call (ray query or direct-lighting query); waits for it */
 int crt_get_query_stats(crt_ctx *ctx, crt_query_stats *out);
+
+/* ---- Direct lighting for hit records and points the CALLER supplies -- light baking (lightmap texels, per-vertex lighting), the colour
+ * under a picked ray, a direct-light pass over a ray set of the caller's.  The reference's one non-recursive stage below shootRay:
+ * RayTracer::calculateDiffusion of the non-GI build (RayTracer.cpp:300-330).  Kernels: csrc/kernel_shade.h.  Single-device contexts only.
+ *
+ * crt_shade_hits* returns, for record i, the colour shootRay returns for a ray whose intersect() result is hits[i] (e.g. what
+ *   crt_trace_rays* wrote), wherever shootRay does not recurse, and says which case it was in out_status[i] (may be NULL):
+ *   CRT_SHADE_BACKGROUND  hit == 0 (RayTracer.cpp:449-450) or the mesh's material is constant (:443-446): the scene's background;
+ *   CRT_SHADE_DIFFUSE     calculateDiffusion: for every light in scene order the shadow ray from point + normal * shadow_bias towards
+ *                         it, checkForIntersection(shadowRay, distanceToLight) (refractive meshes skipped), and where it is unoccluded
+ *                         colour = colour + intensity / (4 r^2 pi) * max(0, l . n) * base; base = the material's albedo or
+ *                         Texture::getColor at the record's (u, v, 1 - u - v) and triangle.  The same float for float, NaNs included: a
+ *                         record with a non-finite point (a hit at t = inf) is shaded the way the reference shades it;
+ *   CRT_SHADE_RECURSES    a reflective or refractive material: shootRay would shoot further rays, which is not offered; colour 0, 0, 0;
+ *   CRT_SHADE_INVALID     hit != 0 with mesh >= n_meshes or triangle >= n_triangles; colour 0, 0, 0.  Both indices are compared with
+ *                         the scene's counts before anything is read through them; whether the triangle BELONGS to the mesh is not
+ *                         checked (in-range indices are safe to read; the colour is then that mix's).
+ *   Of `options` only shadow_bias is read; use_gi != 0 is CRT_ERR_INVALID (the GI build's occlusion rule -- no mesh skipped -- and its
+ *   division by GI_SAMPLE_SIZE + 1 are not offered).
+ * crt_light_points* returns out[i] = the sum, in light order, of the unoccluded lights' factors intensity / (4 r^2 pi) * max(0, l . n) at
+ *   points[i] with normals[i] (3 floats each): calculateDiffusion's result for a white (1, 1, 1) untextured diffuse surface, channel
+ *   for channel.
+ * A scene without lights gives 0.  n == 0 is CRT_OK and touches nothing; a NULL required array (or options) with n > 0 is
+ *   CRT_ERR_INVALID.  Host and device variants, streams, the pending frame, what is left alone: as for the ray queries above, whose
+ *   scratch these calls share.  crt_get_query_stats: rays = n, hits = records shaded DIFFUSE (crt_light_points: n), rerouted = records
+ *   whose lights were all redone by the reference-order walk -- a shadow ray with a non-finite coordinate or a zero direction (a light
+ *   AT the point), filter stack exhausted; every DIFFUSE record when the scene has no filter or crt_tuning::bvh == 0. */
+enum { CRT_SHADE_BACKGROUND = 0, CRT_SHADE_DIFFUSE = 1, CRT_SHADE_RECURSES = 2, CRT_SHADE_INVALID = 3 };
+int crt_shade_hits(crt_ctx *ctx, const crt_hit *hits, uint64_t n, const crt_options *options, float *out_rgb, uint8_t *out_status);
+int crt_shade_hits_device(crt_ctx *ctx, const crt_hit *d_hits, uint64_t n, const crt_options *options, float *d_rgb, uint8_t *d_status,
+                          void *stream);
+int crt_light_points(crt_ctx *ctx, const float *points, const float *normals, uint64_t n, float shadow_bias, float *out);
+int crt_light_points_device(crt_ctx *ctx, const float *d_points, const float *d_normals, uint64_t n, float shadow_bias, float *d_out,
+                            void *stream);
 
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
