@@ -222,6 +222,37 @@ __device__ __forceinline__ void bvh_walk_begin(BvhWalk &W, const float tmax) {
     W.have = false; W.give_up = false; W.steps = 0;
 }
 
+// What a walk step reads, whichever kind the lane's `cur` is: seven 16-byte slots and two id words, 30 registers that the two kinds
+// share.  An inner node fills the slots with its record N[0..6] (the ids are not used); a leaf with its next two triangles, three
+// slots each (the seventh is not used), and their ids.
+typedef float bvh_f4 __attribute__((ext_vector_type(4)));   // (a 16-byte slot as ONE register tuple: it is loaded, waited for and read in place)
+struct BvhFetch { bvh_f4 f[7]; uint32_t id0, id1; };
+__device__ __forceinline__ float4 bvh_slot(const bvh_f4 v) { return make_float4(v.x, v.y, v.z, v.w); }
+// All of it is loaded HERE, before the step's branch on the kind, from per-lane selected addresses: in a wave that holds node lanes and
+// leaf lanes -- practically every step of a dense wave -- the two arms of that branch run one after the other, and loads left inside
+// them are two dependent round trips (three for a shadow walk, whose first triangle the compiler fetched only after the id's
+// refractive bit had arrived); the compiler may not hoist a load out of its arm, and sinks one back into it when it can.  A slot a
+// lane has no use for re-reads something the lane reads anyway: nothing beyond a lane's own record is touched.
+//   node lane: slots 0..6 = its record; both id words = the first word of the record's child slot
+//   leaf lane: slots 0..2 = entry `first`, 3..5 = entry `second` (`first` again when one triangle is left), 6 = slot 0 again
+__device__ __forceinline__ void bvh_fetch(const KernelArgs &A, const bool leaf, const uint32_t node, const uint32_t first, const uint32_t second, BvhFetch &F) {
+    const uint32_t *const ids = A.s->bvh_ids;
+    const char *const nrec = reinterpret_cast<const char *>(A.s->bvh_nodes + 8 * (size_t)node);
+    const char *const e0 = reinterpret_cast<const char *>(bvh_entry(A, first)), *const e1 = reinterpret_cast<const char *>(bvh_entry(A, second));
+    const bvh_f4 *const p0 = reinterpret_cast<const bvh_f4 *>(leaf ? e0 : nrec);
+    const bvh_f4 *const p1 = reinterpret_cast<const bvh_f4 *>(leaf ? e1 : nrec + 48);
+    const bvh_f4 *const p2 = reinterpret_cast<const bvh_f4 *>(leaf ? e0 : nrec + 96);
+    const uint32_t *const i0 = leaf ? ids + first : reinterpret_cast<const uint32_t *>(nrec + 96);
+    const uint32_t *const i1 = leaf ? ids + second : reinterpret_cast<const uint32_t *>(nrec + 96);
+    F.f[0] = p0[0]; F.f[1] = p0[1]; F.f[2] = p0[2];
+    F.f[3] = p1[0]; F.f[4] = p1[1]; F.f[5] = p1[2];
+    F.f[6] = p2[0];
+    F.id0 = *i0; F.id1 = *i1;
+    // the one wait: every loaded register passes through an (empty) volatile statement here, which the loads cannot sink below and
+    // which itself stays in this block
+    asm volatile("" : "+v"(F.f[0]), "+v"(F.f[1]), "+v"(F.f[2]), "+v"(F.f[3]), "+v"(F.f[4]), "+v"(F.f[5]), "+v"(F.f[6]), "+v"(F.id0), "+v"(F.id1));
+}
+
 // One step of a lane's walk: an inner node (its four children tested, the nearest taken, the others pushed) or two triangles of a
 // leaf.  false: the walk is over -- nothing left, the stack too small (give_up), or (SHADOW) an occluder found (have).
 // KIND 0: a closest-hit walk; 1: a shadow walk; 2: whichever `shadow_lane` says, lane by lane -- the level queue's waves hold both kinds
@@ -236,10 +267,19 @@ __device__ __forceinline__ bool bvh_step(const KernelArgs &A, const Ray &R, cons
         bvh_at<MODE>(A, W.sp - 1u, A.s->bvh_stack, 8);
         W.cur = bvh_pop(stack, W.sp);
     }
-    if (!(W.cur & BVH_LEAF)) {
-        const float4 *N = A.s->bvh_nodes + 8 * (size_t)bvh_at<MODE>(A, W.cur, A.s->n_bvh_nodes, 9);
-        const float4 lx = N[0], ly = N[1], lz = N[2], hx = N[3], hy = N[4], hz = N[5];
-        const float4 ch = N[6];
+    // up to TPS triangles of a leaf per step, all fetched before any is tested; what is left of the leaf stays in `cur`
+    constexpr uint32_t TPS = 2u;   // (four per step for the closest-hit walks: measured, no faster, 30 registers more)
+    const bool leaf = (W.cur & BVH_LEAF) != 0;
+    const uint32_t left = (W.cur >> 24) & 0x7Fu;  // a leaf: `left` more after the first
+    const uint32_t n_here = left + 1u < TPS ? left + 1u : TPS;
+    uint32_t node = 0, first = 0;   // (each index is checked against its own array, and only in a lane of its kind)
+    if (leaf) first = bvh_at<MODE>(A, W.cur & 0x00FFFFFFu, A.s->n_bvh_entries - (n_here - 1u), 10);
+    else node = bvh_at<MODE>(A, W.cur, A.s->n_bvh_nodes, 9);
+    BvhFetch F;
+    bvh_fetch(A, leaf, node, first, first + (n_here - 1u), F);   // (beyond the leaf: its last triangle again, not tested)
+    if (!leaf) {
+        const bvh_f4 lx = F.f[0], ly = F.f[1], lz = F.f[2], hx = F.f[3], hy = F.f[4], hz = F.f[5];
+        const bvh_f4 ch = F.f[6];
         if (MODE == BVH_TALLY) nbox += 4;
         uint32_t c0 = __float_as_uint(ch.x), c1 = __float_as_uint(ch.y), c2 = __float_as_uint(ch.z), c3 = __float_as_uint(ch.w);
         float t0, t1, t2, t3;
@@ -260,26 +300,12 @@ __device__ __forceinline__ bool bvh_step(const KernelArgs &A, const Ray &R, cons
         if (c1 != BVH_EMPTY) bvh_push(stack, W.sp, c1);
         W.cur = c0;  // (BVH_EMPTY when the nearest slot holds a miss -- nothing passed, or a NaN distance out of order: the next step pops)
     } else {
-        // up to TPS triangles of the leaf per step, all fetched before any is tested (one round trip); what is left of the leaf stays in `cur`
-        constexpr uint32_t TPS = 2u;   // (four per step for the closest-hit walks: measured, no faster, 30 registers more)
-        const uint32_t left = (W.cur >> 24) & 0x7Fu;  // `left` more after the first
-        const uint32_t n_here = left + 1u < TPS ? left + 1u : TPS;
-        const uint32_t first = bvh_at<MODE>(A, W.cur & 0x00FFFFFFu, A.s->n_bvh_entries - (n_here - 1u), 10);
-        float4 ta[TPS], tb[TPS], tc[TPS];
-        uint32_t tid[TPS];
-#pragma unroll
-        for (uint32_t k = 0; k < TPS; k++) {
-            const uint32_t e = first + (k < n_here ? k : n_here - 1u);   // (beyond the leaf: its last triangle again, not tested)
-            const float4 *T = bvh_entry(A, e);
-            ta[k] = T[0]; tb[k] = T[1]; tc[k] = T[2];
-            tid[k] = A.s->bvh_ids[e];
-        }
         W.cur = left >= TPS ? (BVH_LEAF | ((left - TPS) << 24) | (first + TPS)) : BVH_EMPTY;
 #pragma unroll
         for (uint32_t k = 0; k < TPS; k++) {
             if (k >= n_here) break;
-            const float4 &a = ta[k], &b = tb[k], &c = tc[k];
-            const uint32_t id = tid[k];
+            const float4 a = bvh_slot(F.f[3 * k]), b = bvh_slot(F.f[3 * k + 1]), c = bvh_slot(F.f[3 * k + 2]);
+            const uint32_t id = k ? F.id1 : F.id0;
             if (SHADOW && (id & BVH_ID_REFRACTIVE) && !every_mesh) continue;  // AccelerationStructure.cpp:66-71 (not in the GI mode)
             float t, px, py, pz;
             if (MODE == BVH_TALLY) ntri++;
