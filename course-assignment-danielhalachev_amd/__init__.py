@@ -119,6 +119,12 @@ class QueryStats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("hits", C.c_uint64), ("rerouted", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
+class ShootStats(C.Structure):
+    """crt_shoot_stats: the last radiance query (Tracer.shoot_rays*)"""
+    _fields_ = [("rays", C.c_uint64), ("levels", C.c_uint32), ("pad", C.c_uint32), ("level_rays", C.c_uint64 * 64),
+                ("shadow_records", C.c_uint64), ("rerouted", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
 # crt_hit as a numpy record (what Tracer.trace_rays returns, and the layout of a torch.uint8 [n, 48] output tensor)
 HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, 3), ("normal", np.float32, 3), ("u", np.float32), ("v", np.float32),
                       ("mesh", np.uint32), ("triangle", np.uint32), ("hit", np.uint32)])
@@ -166,6 +172,7 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_tuning_defaults", "crt_create_tuned",
                   "crt_render_async", "crt_wait", "crt_alloc_pinned", "crt_free_pinned",
                   "crt_trace_rays", "crt_trace_rays_device", "crt_occluded_rays", "crt_occluded_rays_device", "crt_camera_rays_device",
                   "crt_get_query_stats", "crt_shade_hits", "crt_shade_hits_device", "crt_light_points", "crt_light_points_device",
+                  "crt_shoot_rays", "crt_shoot_rays_device", "crt_get_shoot_stats",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -178,7 +185,7 @@ HOST_SYMBOLS = ["crt_host_tracer_note", "crt_host_scene_parse_file", "crt_host_s
                 "crt_host_mesh_normals", "crt_host_bucket_rects", "crt_host_camera_apply", "crt_host_tracer_create", "crt_host_tracer_create_tuned",
                 "crt_host_tracer_create_multi", "crt_host_tracer_stats",
                 "crt_host_tracer_free", "crt_host_tracer_set_camera", "crt_host_tracer_render", "crt_host_tracer_ctx", "crt_host_tracer_multi",
-                "crt_host_export_ppm", "crt_host_last_error"]
+                "crt_host_export_ppm", "crt_host_last_error", "crt_host_shoot_stats_layout"]
 
 _lib = None
 
@@ -221,6 +228,11 @@ def lib():
     L.crt_shade_hits_device.argtypes = [vp, vp, C.c_uint64, C.POINTER(Options), vp, vp, vp]
     L.crt_light_points.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, vp]
     L.crt_light_points_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, vp, vp]
+    L.crt_shoot_rays.argtypes = [vp, vp, C.c_uint64, u32, C.POINTER(Options), vp]
+    L.crt_shoot_rays_device.argtypes = [vp, vp, C.c_uint64, u32, C.POINTER(Options), vp, vp]
+    L.crt_get_shoot_stats.argtypes = [vp, C.POINTER(ShootStats)]
+    L.crt_host_shoot_stats_layout.argtypes = [C.POINTER(u32), u32]
+    L.crt_host_shoot_stats_layout.restype = u32
     L.crt_get_kernel_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.crt_synchronize.argtypes = [vp]
     L.crt_destroy.argtypes = [vp]
@@ -632,6 +644,33 @@ class Tracer:
         self._single("light_points_device")
         self._check(lib().crt_light_points_device(self.ctx, C.c_void_p(d_points_ptr), C.c_void_p(d_normals_ptr), n, shadow_bias,
                                                   C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
+
+    # ---- radiance queries: shootRay for the caller's rays (include/crt_hip.h has the contract)
+    def shoot_rays(self, rays, ray_type=RAY_REFLECTION, max_depth=5, shadow_bias=1e-4, reflection_bias=1e-4, refraction_bias=1e-4):
+        """The colour RayTracer::shootRay returns for each ray (direction normalised on entry; reflections, refractions and the Fresnel
+        mix down to max_depth): rays float32 [n, 6] -> float32 [n, 3]."""
+        self._single("shoot_rays")
+        rays = self._rays_array(rays)
+        rgb = np.zeros((len(rays), 3), dtype=np.float32)
+        o = make_options(max_depth, shadow_bias, reflection_bias, refraction_bias)
+        self._check(lib().crt_shoot_rays(self.ctx, _p(rays), len(rays), ray_type, C.byref(o), _p(rgb)))
+        return rgb
+
+    def shoot_rays_device(self, d_rays_ptr, n, d_rgb_ptr, ray_type=RAY_REFLECTION, max_depth=5, shadow_bias=1e-4, reflection_bias=1e-4,
+                          refraction_bias=1e-4, stream_ptr=None):
+        """The same on device memory (data_ptr() of: rays float32 [n, 6], rgb float32 [n, 3]) on the stream; the call waits for the
+        stream once per recursion level, so it cannot be captured into a graph."""
+        self._single("shoot_rays_device")
+        o = make_options(max_depth, shadow_bias, reflection_bias, refraction_bias)
+        self._check(lib().crt_shoot_rays_device(self.ctx, C.c_void_p(d_rays_ptr), n, ray_type, C.byref(o), C.c_void_p(d_rgb_ptr),
+                                                C.c_void_p(stream_ptr or 0)))
+
+    def shoot_stats(self) -> ShootStats:
+        """rays / levels / level_rays / shadow_records / rerouted / kernel_ms of the last radiance query (waits for it)."""
+        self._single("shoot_stats")
+        s = ShootStats()
+        self._check(lib().crt_get_shoot_stats(self.ctx, C.byref(s)))
+        return s
 
     def query_stats(self) -> QueryStats:
         """rays / hits / rerouted / kernel_ms of the last query call (waits for it)."""

@@ -1,6 +1,8 @@
 // kernel_common.h -- device-side constants, argument block and exact-arithmetic helpers shared by all render kernels.
 #pragma once
 
+#include "glibc_powf.h"   // crt_pow5: the Fresnel term of mirror_glass_children
+
 constexpr uint32_t END = CRT_LINK_END;
 constexpr uint32_t LEAF = CRT_LINK_LEAF;
 constexpr uint32_t LAST = CRT_ENTRY_LAST;
@@ -436,4 +438,53 @@ __device__ __forceinline__ void light_setup(const KernelArgs &A, uint32_t li, fl
 __device__ __forceinline__ void light_setup(const KernelArgs &A, uint32_t li, float hpx, float hpy, float hpz, float hnx,
                                             float hny, float hnz, Ray &R, float &dist, float &kfac) {
     light_setup(A, li, hpx, hpy, hpz, hnx, hny, hnz, A.f->shadow_bias, R, dist, kfac);
+}
+
+// The child rays of a mirror or glass hit and the Fresnel coefficient: calculateReflection (RayTracer.cpp:358-374) and
+// calculateRefraction (RayTracer.cpp:375-417) up to the recursive shootRay calls.  (dx, dy, dz): the ray's direction as shootRay holds
+// it (normalised on entry); (px, py, pz), (nx, ny, nz): the hit's point and normal.  Returns whether a transmission ray exists (false:
+// a reflective material, or total internal reflection); `fresnel` and the transmission ray are written only then.  The directions are
+// normalised ONCE here, as the reference builds the child Ray; shootRay's own entry normalisation is the consumer's.
+// The biases are read through pointers where the reference reads them: a frame's kernels pass addresses in their frame block (a scalar
+// load on the path that needs it), a query addresses in its own arguments.  One body for shade_hit (kernel_stream.h) and
+// radiance_scatter (kernel_radiance.h): nothing of the parity argument exists twice.
+template <typename BiasP>
+__device__ __forceinline__ bool mirror_glass_children(const bool refractive, const float ior, const float dx, const float dy, const float dz,
+                                                      const float px, const float py, const float pz, float nx, float ny, float nz,
+                                                      const BiasP reflection_bias, const BiasP refraction_bias, float &fresnel,
+                                                      float &rox, float &roy, float &roz, float &rdx, float &rdy, float &rdz,
+                                                      float &tox, float &toy, float &toz, float &tdx, float &tdy, float &tdz) {
+    bool transmit = false;
+    if (refractive) {
+        // calculateRefraction (RayTracer.cpp:375-417)
+        float eta1 = 1.0f, eta2 = ior;
+        float idn = dot3(dx, dy, dz, nx, ny, nz);
+        if (idn > 0) {
+            const float s = eta1; eta1 = eta2; eta2 = s;
+            nx = -1.0f * nx; ny = -1.0f * ny; nz = -1.0f * nz;
+            idn = -idn;
+        }
+        const float cos_a = -idn;
+        const float sin_a = sqrtf(std_max(0.0f, 1 - cos_a * cos_a));
+        const float eta_ratio = eta1 / eta2;
+        const float sin_b = eta_ratio * sin_a;
+        if (sin_b < 1.0f) {
+            const float q = (eta1 - eta2) / (eta1 + eta2);
+            const float r0 = q * q;  // std::powf(q, 2), folded to q*q by the reference's compiler at -O2
+            fresnel = r0 + (1 - r0) * crt_pow5(1.0f - cos_a);
+            const float cos_b = sqrtf(std_max(0.0f, 1 - sin_b * sin_b));
+            tdx = eta_ratio * (dx + cos_a * nx) - cos_b * nx;
+            tdy = eta_ratio * (dy + cos_a * ny) - cos_b * ny;
+            tdz = eta_ratio * (dz + cos_a * nz) - cos_b * nz;
+            normalize3(tdx, tdy, tdz);
+            tox = px - nx * *refraction_bias; toy = py - ny * *refraction_bias; toz = pz - nz * *refraction_bias;
+            transmit = true;
+        }
+    }
+    // the reflection ray (both materials): origin + n*bias, reflect(d, n) normalised (Vector.cpp:119-122)
+    const float k = 2 * dot3(dx, dy, dz, nx, ny, nz);
+    rdx = dx - k * nx; rdy = dy - k * ny; rdz = dz - k * nz;
+    normalize3(rdx, rdy, rdz);
+    rox = px + nx * *reflection_bias; roy = py + ny * *reflection_bias; roz = pz + nz * *reflection_bias;
+    return transmit;
 }

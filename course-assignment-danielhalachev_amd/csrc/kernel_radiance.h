@@ -1,0 +1,145 @@
+// kernel_radiance.h -- radiance queries (crt_shoot_rays*): what RayTracer::shootRay (RayTracer.cpp:419-451, the non-GI build) returns
+// for rays the CALLER supplies, level by level.  The walks and the direct lighting are the queries that exist (kernel_query.h:
+// query_closest / query_reroute, kernel_shade.h: query_direct / query_direct_reroute); the three small kernels here are the recursion
+// around them, and the host loop (crt_query.hip) runs them one level behind the other:
+//
+//   radiance_prepare   level 0 only: the caller's rays into the level's ray array, normalised as shootRay's entry does it;
+//   (trace, direct light: the level's crt_hit, colour and status arrays; background, constant and diffuse records are final)
+//   radiance_scatter   a lane per ray of the level; a record whose status is CRT_SHADE_RECURSES gets a node (TNode, kernel_stream.h: kind,
+//                      albedo or Fresnel coefficient, two child indices) and its child rays in level g + 1's ray array;
+//   radiance_combine   from the deepest level up: a lane per recursing record mixes its children's colours into its own.
+//
+// Every level has arrays of its own (rays, records, colours, status, nodes): a parent holds its children's indices in the next level's
+// arrays, so the ORDER in which a level's children are appended may differ between two runs and no colour does.  Nothing of a frame is
+// used: no FrameArgs queue, no level queue, no ray tree of a pixel.
+#pragma once
+
+#include "kernel_stream.h"
+#include "kernel_shade.h"
+
+struct RadianceArgs {
+    const crt_ray *in_rays;             // radiance_prepare: the caller's rays
+    crt_ray *rays;                      // this level's rays, directions as shootRay holds them (normalised on entry)
+    const crt_hit *hits;                // ... their closest hits
+    const uint8_t *status;              // ... CRT_SHADE_* of each
+    float *rgb;                         // ... colours, 3 floats a ray (level 0: the caller's output)
+    float4 *nodes;                      // ... nodes, 2 x float4 a ray; written and read for CRT_SHADE_RECURSES records only
+    crt_ray *child_rays;                // level g + 1's ray array
+    const float *child_rgb;             // level g + 1's colours (radiance_combine)
+    uint32_t *child_count;              // rays appended to level g + 1
+    unsigned long long *diffuse_total;  // CRT_SHADE_DIFFUSE records over all levels of the call
+    uint32_t n;                         // rays of this level
+    uint32_t child_cap;                 // records level g + 1's arrays hold (the host allocates 2 n before the launch: never reached)
+    uint32_t child_n;                   // radiance_combine: rays of level g + 1
+    uint32_t spawn;                     // g + 1 <= max_depth: children are traced (else CHILD_BG: background without tracing, RayTracer.cpp:427-429)
+    float reflection_bias, refraction_bias;
+};
+
+// shootRay's entry (RayTracer.cpp:420) for the caller's rays: normalize3 leaves a zero direction as it is
+__global__ __launch_bounds__(BLOCK) void radiance_prepare(const RadianceArgs G) {
+    const uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= G.n) return;
+    crt_ray q = G.in_rays[r];
+    normalize3(q.direction[0], q.direction[1], q.direction[2]);
+    G.rays[r] = q;
+}
+
+// shootRay's dispatch for a mirror or glass hit (RayTracer.cpp:437-442) up to the recursive calls: the node and the child rays.  The
+// arithmetic is shade_hit's (kernel_stream.h), in one body for both: mirror_glass_children (kernel_common.h).  A child is stored the
+// way the next level walks it: normalised once more, which is the child's own shootRay entry (stream_trace_shade does that when it
+// fetches a queued ray).  The children of a wave are appended with ONE atomic (kernel_query.h: query_append's pattern): the
+// reflection rays of its lanes first, then the transmission rays.
+__global__ __launch_bounds__(BLOCK) void radiance_scatter(const KernelArgs A, const RadianceArgs G) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;   // (every lane stays to the end: the ballots are the wave's)
+    const uint32_t status = r < G.n ? (uint32_t)G.status[r] : (uint32_t)CRT_SHADE_BACKGROUND;
+    const unsigned long long diffuse = __ballot(r < G.n && status == (uint32_t)CRT_SHADE_DIFFUSE);
+    if (lane == 0 && diffuse) atomicAdd(G.diffuse_total, (unsigned long long)__popcll(diffuse));
+    const bool recurses = r < G.n && status == (uint32_t)CRT_SHADE_RECURSES;
+    TNode N;
+    N.cx = N.cy = N.cz = 0; N.kind = TN_CONST; N.a = 0; N.b = 0; N.f = 0; N.pad = 0;
+    bool reflect = false, transmit = false;
+    float rox = 0, roy = 0, roz = 0, rdx = 0, rdy = 0, rdz = 0, tox = 0, toy = 0, toz = 0, tdx = 0, tdy = 0, tdz = 0;
+    if (recurses) {
+        const crt_ray q = G.rays[r];
+        const crt_hit h = G.hits[r];
+        // (CRT_SHADE_RECURSES: shade_load has compared h.mesh with the scene's count and found one of the two materials)
+        const DMaterial M = A.s->materials[A.s->meshes[h.mesh].material];
+        const bool refractive = M.type == CRT_MAT_REFRACTIVE;
+        const bool through = mirror_glass_children(refractive, M.ior, q.direction[0], q.direction[1], q.direction[2], h.point[0], h.point[1],
+                                                   h.point[2], h.normal[0], h.normal[1], h.normal[2], &G.reflection_bias, &G.refraction_bias,
+                                                   N.f, rox, roy, roz, rdx, rdy, rdz, tox, toy, toz, tdx, tdy, tdz);
+        if (refractive) N.kind = TN_REFRACT;
+        else {
+            N.kind = TN_REFLECT;
+            N.cx = M.ax; N.cy = M.ay; N.cz = M.az;
+        }
+        N.a = CHILD_BG;
+        N.b = refractive ? (through ? CHILD_BG : CHILD_NONE) : 0u;
+        reflect = G.spawn != 0u;
+        transmit = G.spawn != 0u && through;
+    }
+    const unsigned long long m1 = __ballot(reflect), m2 = __ballot(transmit);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const uint32_t n1 = (uint32_t)__popcll(m1), n2 = (uint32_t)__popcll(m2);
+    uint32_t base = 0;
+    if (m1) {   // (wave-uniform)
+        const uint32_t first = (uint32_t)(__ffsll((long long)m1) - 1);
+        if (lane == first) base = atomicAdd(G.child_count, n1 + n2);
+        base = __shfl(base, first);
+    }
+    if (reflect) {
+        const uint32_t i1 = base + (uint32_t)__popcll(m1 & below);
+        if (i1 < G.child_cap) {
+            crt_ray c;
+            normalize3(rdx, rdy, rdz);   // the child's shootRay entry (RayTracer.cpp:420)
+            c.origin[0] = rox; c.origin[1] = roy; c.origin[2] = roz; c.direction[0] = rdx; c.direction[1] = rdy; c.direction[2] = rdz;
+            G.child_rays[i1] = c;
+            N.a = i1;
+        }
+        if (transmit) {
+            const uint32_t i2 = base + n1 + (uint32_t)__popcll(m2 & below);
+            if (i2 < G.child_cap) {
+                crt_ray c;
+                normalize3(tdx, tdy, tdz);
+                c.origin[0] = tox; c.origin[1] = toy; c.origin[2] = toz; c.direction[0] = tdx; c.direction[1] = tdy; c.direction[2] = tdz;
+                G.child_rays[i2] = c;
+                N.b = i2;
+            }
+        }
+    }
+    if (recurses) {
+        G.nodes[2 * r] = make_float4(N.cx, N.cy, N.cz, __uint_as_float(N.kind));
+        G.nodes[2 * r + 1] = make_float4(__uint_as_float(N.a), __uint_as_float(N.b), N.f, 0.0f);
+    }
+}
+
+// the colour shootRay returned for child `index` of the next level (CHILD_BG: the depth rule, RayTracer.cpp:427-429)
+__device__ __forceinline__ void radiance_child(const KernelArgs &A, const RadianceArgs &G, const uint32_t index, float &x, float &y, float &z) {
+    x = A.s->bgx; y = A.s->bgy; z = A.s->bgz;
+    if (index < G.child_n) { x = G.child_rgb[3 * (size_t)index]; y = G.child_rgb[3 * (size_t)index + 1]; z = G.child_rgb[3 * (size_t)index + 2]; }
+}
+
+// What calculateReflection / calculateRefraction return once their recursive calls have (RayTracer.cpp:368-372, 414-416): the
+// expressions of stream_resolve (kernel_stream.h), a lane per recursing record of the level.  Level g + 1's colours are final when
+// this runs for level g.
+__global__ __launch_bounds__(BLOCK) void radiance_combine(const KernelArgs A, const RadianceArgs G) {
+    const uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= G.n || G.status[r] != (uint8_t)CRT_SHADE_RECURSES) return;
+    const float4 n0 = G.nodes[2 * r], n1 = G.nodes[2 * r + 1];
+    const uint32_t kind = __float_as_uint(n0.w) & TN_KIND_MASK;
+    float cx, cy, cz;
+    radiance_child(A, G, __float_as_uint(n1.x), cx, cy, cz);   // the reflection ray is shot first (RayTracer.cpp:366, 398-400)
+    if (kind == TN_REFLECT) {
+        cx = 0.0f + n0.x * cx; cy = 0.0f + n0.y * cy; cz = 0.0f + n0.z * cz;   // RayTracer.cpp:368-372
+    } else {
+        const uint32_t refr = __float_as_uint(n1.y);
+        if (refr != CHILD_NONE) {   // (CHILD_NONE: `return reflectionColor`, RayTracer.cpp:416)
+            float tx, ty, tz;
+            radiance_child(A, G, refr, tx, ty, tz);
+            const float f = n1.z;
+            cx = f * cx + (1 - f) * tx; cy = f * cy + (1 - f) * ty; cz = f * cz + (1 - f) * tz;   // RayTracer.cpp:414
+        }
+    }
+    G.rgb[3 * r] = cx; G.rgb[3 * r + 1] = cy; G.rgb[3 * r + 2] = cz;
+}

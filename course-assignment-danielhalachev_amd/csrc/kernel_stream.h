@@ -237,43 +237,15 @@ __device__ __forceinline__ void shade_hit(const KernelArgs &A, const uint32_t ge
             }
         } else if (S.M.type == CRT_MAT_REFLECTIVE || S.M.type == CRT_MAT_REFRACTIVE) {
             const bool refractive = S.M.type == CRT_MAT_REFRACTIVE;
-            float nx = S.nx, ny = S.ny, nz = S.nz;
-            bool transmit = false;
-            if (refractive) {
-                // calculateRefraction (RayTracer.cpp:375-417)
-                float eta1 = 1.0f, eta2 = S.M.ior;
-                float idn = dot3(R.dx, R.dy, R.dz, nx, ny, nz);
-                if (idn > 0) {
-                    const float s = eta1; eta1 = eta2; eta2 = s;
-                    nx = -1.0f * nx; ny = -1.0f * ny; nz = -1.0f * nz;
-                    idn = -idn;
-                }
-                const float cos_a = -idn;
-                const float sin_a = sqrtf(std_max(0.0f, 1 - cos_a * cos_a));
-                const float eta_ratio = eta1 / eta2;
-                const float sin_b = eta_ratio * sin_a;
-                if (sin_b < 1.0f) {
-                    const float q = (eta1 - eta2) / (eta1 + eta2);
-                    const float r0 = q * q;  // std::powf(q, 2), folded to q*q by the reference's compiler at -O2
-                    N.f = r0 + (1 - r0) * crt_pow5(1.0f - cos_a);
-                    const float cos_b = sqrtf(std_max(0.0f, 1 - sin_b * sin_b));
-                    E.tdx = eta_ratio * (R.dx + cos_a * nx) - cos_b * nx;
-                    E.tdy = eta_ratio * (R.dy + cos_a * ny) - cos_b * ny;
-                    E.tdz = eta_ratio * (R.dz + cos_a * nz) - cos_b * nz;
-                    normalize3(E.tdx, E.tdy, E.tdz);
-                    E.tox = S.px - nx * A.f->refraction_bias; E.toy = S.py - ny * A.f->refraction_bias; E.toz = S.pz - nz * A.f->refraction_bias;
-                    transmit = true;
-                }
-                N.kind = TN_REFRACT;
-            } else {
-                N.kind = TN_REFLECT;  // calculateReflection (RayTracer.cpp:358-374)
+            // calculateReflection / calculateRefraction (RayTracer.cpp:358-417): kernel_common.h, mirror_glass_children
+            const bool transmit = mirror_glass_children(refractive, S.M.ior, R.dx, R.dy, R.dz, S.px, S.py, S.pz, S.nx, S.ny, S.nz,
+                                                        &A.f->reflection_bias, &A.f->refraction_bias, N.f, E.rox, E.roy, E.roz, E.rdx, E.rdy,
+                                                        E.rdz, E.tox, E.toy, E.toz, E.tdx, E.tdy, E.tdz);
+            if (refractive) N.kind = TN_REFRACT;
+            else {
+                N.kind = TN_REFLECT;
                 N.cx = S.M.ax; N.cy = S.M.ay; N.cz = S.M.az;
             }
-            // the reflection ray (both materials): origin + n*bias, reflect(d, n) normalised (Vector.cpp:119-122)
-            const float k = 2 * dot3(R.dx, R.dy, R.dz, nx, ny, nz);
-            E.rdx = R.dx - k * nx; E.rdy = R.dy - k * ny; E.rdz = R.dz - k * nz;
-            normalize3(E.rdx, E.rdy, E.rdz);
-            E.rox = S.px + nx * A.f->reflection_bias; E.roy = S.py + ny * A.f->reflection_bias; E.roz = S.pz + nz * A.f->reflection_bias;
             N.a = CHILD_BG;
             N.b = refractive ? (transmit ? CHILD_BG : CHILD_NONE) : 0u;
             E.reflect = spawn_allowed;

@@ -241,6 +241,21 @@ std::vector<float> RayTracer::lightPoints(const std::vector<float> &points, cons
   return out;
 }
 
+std::vector<float> RayTracer::shootRays(const std::vector<crt_ray> &rays, const RenderOptions &ro, unsigned int rayType, crt_shoot_stats *stats) {
+  if (multi) throw std::runtime_error("shootRays: not available on a multi-device tracer");
+  std::vector<float> rgb(rays.size() * 3);
+  crt_options options{};
+  options.max_depth = ro.MAX_DEPTH;
+  options.shadow_bias = ro.SHADOW_BIAS;
+  options.reflection_bias = ro.REFLECTION_BIAS;
+  options.refraction_bias = ro.REFRACTION_BIAS;
+  options.use_gi = ro.USE_GI ? 1u : 0u;
+  if (crt_shoot_rays(ctx, rays.data(), rays.size(), rayType, &options, rgb.data()) != CRT_OK)
+    throw std::runtime_error(std::string("shootRays failed: ") + crt_last_error(ctx));
+  if (stats && crt_get_shoot_stats(ctx, stats) != CRT_OK) throw std::runtime_error(std::string("shootRays failed: ") + crt_last_error(ctx));
+  return rgb;
+}
+
 crt_query_stats RayTracer::queryStats() const {
   crt_query_stats s{};
   if (!multi) crt_get_query_stats(ctx, &s);

@@ -106,6 +106,11 @@ class RayTracer {
   // per record, CRT_SHADE_* per record in *status when it is given; and the lights' unoccluded factors summed at points of the caller's
   std::vector<float> shadeHits(const std::vector<crt_hit> &hits, float shadowBias = 1e-4f, std::vector<unsigned char> *status = nullptr);
   std::vector<float> lightPoints(const std::vector<float> &points, const std::vector<float> &normals, float shadowBias = 1e-4f);
+  // ---- radiance queries (crt_hip.h: crt_shoot_rays): what shootRay(Ray{origin, direction, rayType}, 0) returns for rays of the
+  // caller's -- the direction normalised on entry, reflections, refractions and the Fresnel mix down to renderOptions.MAX_DEPTH, the
+  // three biases from renderOptions (USE_GI is refused) --, 3 floats per ray; *stats: the call's crt_shoot_stats when it is given
+  std::vector<float> shootRays(const std::vector<crt_ray> &rays, const RenderOptions &renderOptions, unsigned int rayType = CRT_RAY_REFLECTION,
+                               crt_shoot_stats *stats = nullptr);
 
   // flat access for callers that do not want the vector-of-vectors copy
   int renderFlat(const std::string &pathToImage, const RenderOptions &renderOptions, float *outRGB, unsigned int counters = 0);

@@ -1,5 +1,6 @@
 // extern "C" wrappers of include/crt_host.h over the C++ host layer.  No exception leaves this file.
 #include <chrono>
+#include <cstddef>
 #include <cstring>
 #include <exception>
 #include <memory>
@@ -249,4 +250,12 @@ extern "C" int crt_host_export_ppm(const char *path, const float *rgb, uint32_t 
     crt::writePPM(path, rgb, width, height);
     return CRT_OK;
   });
+}
+
+extern "C" uint32_t crt_host_shoot_stats_layout(uint32_t *offsets, uint32_t n) {
+  const uint32_t at[6] = {(uint32_t)offsetof(crt_shoot_stats, rays),           (uint32_t)offsetof(crt_shoot_stats, levels),
+                          (uint32_t)offsetof(crt_shoot_stats, level_rays),     (uint32_t)offsetof(crt_shoot_stats, shadow_records),
+                          (uint32_t)offsetof(crt_shoot_stats, rerouted),       (uint32_t)offsetof(crt_shoot_stats, kernel_ms)};
+  for (uint32_t i = 0; offsets && i < n && i < 6; i++) offsets[i] = at[i];
+  return (uint32_t)sizeof(crt_shoot_stats);
 }

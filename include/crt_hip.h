@@ -346,7 +346,8 @@ int crt_get_query_stats(crt_ctx *ctx, crt_query_stats *out);
  *                         colour = colour + intensity / (4 r^2 pi) * max(0, l . n) * base; base = the material's albedo or
  *                         Texture::getColor at the record's (u, v, 1 - u - v) and triangle.  The same float for float, NaNs included: a
  *                         record with a non-finite point (a hit at t = inf) is shaded the way the reference shades it;
- *   CRT_SHADE_RECURSES    a reflective or refractive material: shootRay would shoot further rays, which is not offered; colour 0, 0, 0;
+ *   CRT_SHADE_RECURSES    a reflective or refractive material: shootRay would shoot further rays, which is not offered HERE (the radiance
+ *                         queries below, crt_shoot_rays*, follow them); colour 0, 0, 0;
  *   CRT_SHADE_INVALID     hit != 0 with mesh >= n_meshes or triangle >= n_triangles; colour 0, 0, 0.  Both indices are compared with
  *                         the scene's counts before anything is read through them; whether the triangle BELONGS to the mesh is not
  *                         checked (in-range indices are safe to read; the colour is then that mix's).
@@ -367,6 +368,47 @@ int crt_shade_hits_device(crt_ctx *ctx, const crt_hit *d_hits, uint64_t n, const
 int crt_light_points(crt_ctx *ctx, const float *points, const float *normals, uint64_t n, float shadow_bias, float *out);
 int crt_light_points_device(crt_ctx *ctx, const float *d_points, const float *d_normals, uint64_t n, float shadow_bias, float *d_out,
                             void *stream);
+
+/* ---- Radiance queries: the colour RayTracer::shootRay returns for rays the CALLER supplies, with its reflections, refractions and
+ * Fresnel mix -- fisheye, panoramic and stereo cameras, light probes and cube maps from arbitrary points, depth of field, the colour
+ * under a picked ray, re-shooting only a frame's changed pixels.  Kernels: csrc/kernel_radiance.h around those of the two query families
+ * above.  Single-device contexts only.
+ *
+ * out_rgb[3 i ..] is what shootRay(Ray{origin, direction, ray_type}, depth = 0) of the non-GI build returns (RayTracer.cpp:419-451):
+ *   the direction NORMALISED ON ENTRY, as shootRay does it (:420; a zero direction stays zero) -- unlike crt_trace_rays*, which walks
+ *   directions as given --, then the closest hit, the switch on the material, calculateDiffusion, calculateReflection,
+ *   calculateRefraction (the Fresnel term through the restated glibc powf) and the depth rule: a ray that would enter shootRay with
+ *   depth > max_depth is the background.  The same float for float, NaNs included.  ray_type is the caller's ray's alone
+ *   (CRT_RAY_PRIMARY culls back faces); its children are REFLECTION and REFRACTION rays, as in the reference.  A frame is the special
+ *   case of crt_camera_rays_device's rays as CRT_RAY_PRIMARY: getRay's normalisation followed by shootRay's is the frame's ray.
+ * Of `options` max_depth, shadow_bias, reflection_bias and refraction_bias are read.  use_gi != 0, max_depth + 1 > 64 (a frame's rule),
+ *   an unknown ray_type, a NULL array or NULL options with n > 0 are CRT_ERR_INVALID; n == 0 is CRT_OK and touches nothing.
+ * The evaluation is LEVEL-SYNCHRONOUS: for recursion level g = 0 .. max_depth the level's rays are traced (crt_trace_rays*' kernels) and
+ *   lit (crt_shade_hits*' kernels), the mirror and glass hits' child rays become level g + 1, and when no level is left the colours are
+ *   mixed from the deepest level up.  Every level has arrays of its own in the context's scratch, which grows and is kept: a call
+ *   allocates nothing once the context has seen a call whose levels were at least as wide.
+ * The device variant takes device pointers and enqueues on `stream`, BUT IT WAITS FOR THE STREAM ONCE PER LEVEL (and once per 2^22 rays
+ *   of n): the size of level g + 1 -- one 4-byte count -- is read back through pinned memory before that level can be launched.  Such a call
+ *   therefore CANNOT BE CAPTURED INTO A hipGraph, and it returns when its last level's launches are enqueued, not before.  The host
+ *   variant copies in, runs, copies out and returns when the colours are in out_rgb.
+ * The pending frame, what is left alone (the persistent colour buffer, crt_stats, the ray queues' sizing, fallback_frames), streams: as
+ *   for the ray queries.  crt_get_query_stats after a call: rays = n, hits = the callers' rays with a hit (level 0), rerouted and
+ *   kernel_ms as in crt_shoot_stats.  A query call after a radiance call first waits for it. */
+typedef struct crt_shoot_stats {
+    uint64_t rays;             /* n */
+    uint32_t levels;           /* recursion levels that held at least one ray */
+    uint32_t pad;
+    uint64_t level_rays[64];   /* rays traced at level g (MAX_GENERATIONS entries) */
+    uint64_t shadow_records;   /* DIFFUSE nodes over all levels: records whose lights were walked */
+    uint64_t rerouted;         /* sum of the constituent queries' rerouted counts (crt_query_stats::rerouted of every level's trace and
+                                * lighting launches) */
+    double kernel_ms;          /* HIP events on the call's stream, first launch to last: the waits between the levels are inside */
+} crt_shoot_stats;
+int crt_shoot_rays(crt_ctx *ctx, const crt_ray *rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *out_rgb);
+int crt_shoot_rays_device(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *d_rgb,
+                          void *stream);
+/* statistics of the last radiance call; waits for it */
+int crt_get_shoot_stats(crt_ctx *ctx, crt_shoot_stats *out);
 
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and

@@ -79,6 +79,9 @@ crt_multi *crt_host_tracer_multi(crt_host_tracer *tracer); /* NULL for a single-
 /* statistics of the last render (summed over the devices of a multi-device tracer) */
 int crt_host_tracer_stats(crt_host_tracer *tracer, crt_stats *out);
 int crt_host_export_ppm(const char *path, const float *rgb, uint32_t width, uint32_t height);
+/* the layout of crt_shoot_stats as this library was compiled (crt_hip.h; crt::RayTracer::shootRays fills one): returns sizeof, and
+ * writes up to n of the byte offsets of rays, levels, level_rays, shadow_records, rerouted, kernel_ms -- for bindings that restate it */
+uint32_t crt_host_shoot_stats_layout(uint32_t *offsets, uint32_t n);
 
 const char *crt_host_last_error(void);
 
