@@ -164,8 +164,9 @@ def tuning_from_string(text):
 
 
 # every symbol include/crt_hip.h and include/crt_host.h declare; the test hooks are exported by libcrt_hip_test.so only
-TEST_HOOK_SYMBOLS = ["crt_bvh_selftest", "crt_test_pow5", "crt_test_gi", "crt_debug_multi_force_staged", "crt_debug_multi_fail_next_alloc"]
-DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_tuning_defaults", "crt_create_tuned", "crt_create", "crt_set_camera", "crt_render", "crt_render_tiles_device", "crt_packed_tile_count",
+TEST_HOOK_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_stack", "crt_test_pow5", "crt_test_gi", "crt_debug_multi_force_staged",
+                     "crt_debug_multi_fail_next_alloc"]
+DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_stack", "crt_tuning_defaults", "crt_create_tuned", "crt_create", "crt_set_camera", "crt_render", "crt_render_tiles_device", "crt_packed_tile_count",
                   "crt_unpack_tiles_device", "crt_quantize_device", "crt_read_quantized", "crt_kernel_elapsed_ms", "crt_kernel_times_ms",
                   "crt_get_stats", "crt_get_kernel_counters", "crt_synchronize", "crt_destroy", "crt_last_error", "crt_device_count", "crt_test_pow5", "crt_test_gi",
                   "crt_describe_kernels", "crt_debug_stream_counts", "crt_get_executed_counters", "crt_get_executed_plan_tests",
@@ -686,6 +687,13 @@ class Tracer:
         L.crt_describe_kernels.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         self._check(L.crt_describe_kernels(self.ctx, buf, 512))
         return dict(kv.split("=", 1) for kv in buf.value.decode().split(";"))
+
+    def set_filter_stack(self, entries):
+        """Test hook (libcrt_hip_test.so): the filter walks may use `entries` stack entries from now on, clamped to [1, built size]."""
+        self._single("set_filter_stack")
+        L = lib()
+        L.crt_debug_set_filter_stack.argtypes = [C.c_void_p, C.c_uint32]
+        self._check(L.crt_debug_set_filter_stack(self.ctx, int(entries)))
 
     def stream_counts(self):
         """Diagnostics: the ray-stream pass's counter block of the last frame (SC_* layout of csrc/kernel_stream.h)."""

@@ -609,4 +609,14 @@ extern "C" int crt_bvh_selftest(const crt_scene_desc *s, const float *rays, uint
     }
     return CRT_OK;
 }
+
+extern "C" int crt_bvh_census(const crt_scene_desc *s, uint64_t out[8]) {
+    if (!s || !out) return CRT_ERR_INVALID;
+    for (int k = 0; k < 8; k++) out[k] = 0;
+    BvhHost H;
+    bvh_build(s, true, H);
+    if (!H.ok) return CRT_ERR_INVALID;
+    out[0] = H.nodes.size(); out[1] = H.ids.size(); out[2] = H.max_depth; out[3] = H.wide_depth; out[4] = H.walk_triangles;
+    return CRT_OK;
+}
 #endif  // CRT_TEST_HOOKS

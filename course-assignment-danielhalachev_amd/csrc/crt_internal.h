@@ -71,7 +71,10 @@ struct crt_ctx {
     float4 *d_hits_all = nullptr;     // a level's closest hits by ray index (kernel_plan.h: the walk-only builds)
     unsigned long long *d_lq = nullptr;   // kernel_bvh.h: the level queue (one entry per ray-tree node at most), 8 granules per ray
     uint32_t *d_lq_words = nullptr;       // ... and its counters (kernel_stream.h: LQ_*)
-    uint32_t *d_bvh_spill = nullptr;  // kernel_bvh.h: the walks' stacks beyond their LDS part: one region for the caller's stream, one for the side stream
+    uint32_t *d_bvh_spill = nullptr;  // kernel_bvh.h: the walks' stacks beyond their LDS part: BVH_SPILL_REGIONS regions of bvh_spill_words() words (crt_launch.hip: who uses which)
+    uint32_t bvh_stack_built = 0;     // SceneArgs::bvh_stack as crt_create sized it (a test hook may lower the scene's value, never this one)
+    // words of one spill region: a column of (built stack - LDS part) entries for every thread of the largest grid
+    size_t bvh_spill_words() const { return bvh_stack_built > BVH_LDS_STACK ? (size_t)grid_blocks * BLOCK * (bvh_stack_built - BVH_LDS_STACK) : 0u; }
     hipStream_t side = nullptr;       // shadow pass 0 overlaps the deeper recursion levels on this stream
     hipStream_t early = nullptr;      // the level queue's launch starts WITH level 0 on this one (crt_launch.hip)
     hipEvent_t ev_reset[EV_RING] = {}, ev_queue[EV_RING] = {};   // the frame's counters are zeroed / the level queue's launch has ended

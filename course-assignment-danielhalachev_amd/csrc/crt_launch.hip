@@ -376,7 +376,7 @@ static int launch_stream_levels(crt_ctx *ctx, const crt_options *o, FramePlan &P
             }
             CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev_s0[P.slot], where));
             // (beside the levels its persistent waves must leave wave slots on every CU for the level kernels)
-            const uint32_t blocks0 = side_per_cu ? (uint32_t)ctx->num_cus * side_per_cu : ctx->grid_blocks;
+            const uint32_t blocks0 = side_per_cu ? std::min(ctx->grid_blocks, (uint32_t)ctx->num_cus * side_per_cu) : ctx->grid_blocks;   // (a spill region holds grid_blocks workgroups' columns)
             if (P.bvh) {
                 if (P.exec_count) launch(bvh_trace_shadow<0, BVH_TALLY>, blocks0, where, S);
                 else if (ctx->tuning.bvh == 2) launch(bvh_trace_shadow<0, BVH_CHECKED>, blocks0, where, S);
@@ -510,8 +510,17 @@ static int launch_frame(crt_ctx *ctx, const crt_options *o, uint32_t n_items, fl
     F.fallback_total = ctx->d_fallback_total;
     F.s_lq_words = ctx->d_lq_words;
     F.lq_epoch = (uint32_t)(ctx->launches & 0x7FFFFFFFull) + 1u;   // the level queue's tag of this frame (this context's buffer has never seen it: tags only grow)
+    // The walks' spill regions (kernel_bvh.h: bvh_stack_of), one per stream of a frame, because these launches may run side by side:
+    //   bvh_spill        `stream`: bvh_trace_level0 / bvh_trace_shade* (lane_blocks or level_blocks <= grid_blocks workgroups), and behind
+    //                    them bvh_trace_shadow<1> (lane_blocks), which uses the side region: pass 0 has ended by then (ev_s1)
+    //   bvh_spill_side   ctx->side: bvh_trace_shadow<0> (num_cus x side_blocks, at most grid_blocks) beside the levels and the queue
+    //   bvh_spill_queue  ctx->early (or `stream` behind level 0): bvh_trace_queue (at most lane_blocks), beside level 0 and pass 0; its
+    //                    second launch runs behind the first on the same stream
+    // Frames of one context follow one another on `stream`; a query has scratch of its own (crt_query.hip).
     F.bvh_spill = ctx->d_bvh_spill;
-    F.bvh_spill_side = ctx->d_bvh_spill ? ctx->d_bvh_spill + (size_t)ctx->grid_blocks * BLOCK * (ctx->scene.bvh_stack - BVH_LDS_STACK) : nullptr;
+    F.bvh_spill_side = ctx->d_bvh_spill ? ctx->d_bvh_spill + ctx->bvh_spill_words() : nullptr;
+    F.bvh_spill_queue = ctx->d_bvh_spill ? ctx->d_bvh_spill + 2u * ctx->bvh_spill_words() : nullptr;
+    F.bvh_spill_words = ctx->d_bvh_spill ? ctx->bvh_spill_words() : 0u;
     const bool count = o->collect_counters == 1;       // the counting build: every ray walked the reference's way
     const bool exec_count = o->collect_counters == 2;  // the production kernels, tallying the tests they execute
     CRT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_sync, 0, 4 * sizeof(uint32_t), stream));

@@ -145,8 +145,11 @@ static int query_prepare(crt_ctx *ctx, uint64_t launch_rays, hipStream_t stream)
         CRT_HIP_CHECK(ctx, hipMalloc((void **)&q->d_words, QW_WORDS * sizeof(uint32_t)));
         CRT_HIP_CHECK(ctx, hipHostMalloc((void **)&q->h_words, QW_WORDS * sizeof(uint32_t)));
         memset(q->h_words, 0, QW_WORDS * sizeof(uint32_t));
-        if (ctx->scene.bvh_ok && ctx->scene.bvh_stack > BVH_LDS_STACK)
-            CRT_HIP_CHECK(ctx, hipMalloc((void **)&q->d_spill, (size_t)ctx->grid_blocks * BLOCK * (ctx->scene.bvh_stack - BVH_LDS_STACK) * sizeof(uint32_t)));
+        // one region: every filter launch of a query (query_closest / query_occluded / query_direct, the levels of crt_shoot_rays* among
+        // them) has at most grid_blocks workgroups and follows the previous one on ONE stream (query_prepare makes a call on another
+        // stream, and a pending frame, wait first): no two of them run side by side
+        if (ctx->bvh_spill_words())
+            CRT_HIP_CHECK(ctx, hipMalloc((void **)&q->d_spill, ctx->bvh_spill_words() * sizeof(uint32_t)));
         CRT_HIP_CHECK(ctx, hipEventCreate(&q->ev0));
         CRT_HIP_CHECK(ctx, hipEventCreate(&q->ev1));
     }

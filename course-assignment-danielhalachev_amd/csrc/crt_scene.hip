@@ -557,8 +557,10 @@ extern "C" int crt_create_tuned(const crt_scene_desc *s, int device, const crt_t
     CK(hipMalloc((void **)&ctx->d_counters, 3 * C_N * sizeof(unsigned long long)));  // [levels | shadow pass 0 | the rest]
     // persistent grid: 8 blocks of 256 threads per CU gives every CU its 32 waves if registers allow
     ctx->grid_blocks = (uint32_t)ctx->num_cus * 8u;
-    if (ctx->scene.bvh_ok && ctx->scene.bvh_stack > BVH_LDS_STACK)
-        CK(hipMalloc((void **)&ctx->d_bvh_spill, 2u * (size_t)ctx->grid_blocks * BLOCK * (ctx->scene.bvh_stack - BVH_LDS_STACK) * sizeof(uint32_t)));
+    // the walks' spill: one region per launch of a frame that may run beside another (kernel_bvh.h: BVH_SPILL_*), each sized for the
+    // largest grid any of them is launched with (no filter launch has more than grid_blocks workgroups: crt_launch.hip)
+    ctx->bvh_stack_built = ctx->scene.bvh_ok ? ctx->scene.bvh_stack : 0u;
+    if (ctx->bvh_spill_words()) CK(hipMalloc((void **)&ctx->d_bvh_spill, 3u * ctx->bvh_spill_words() * sizeof(uint32_t)));
     // the argument blocks (kernel_common.h): the scene's once, a slot per frame in flight for the frames'
     CK(hipMalloc((void **)&ctx->d_scene, sizeof(SceneArgs)));
     CK(hipMemcpy(ctx->d_scene, &ctx->scene, sizeof(SceneArgs), hipMemcpyHostToDevice));

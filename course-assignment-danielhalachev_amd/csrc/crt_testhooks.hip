@@ -91,3 +91,16 @@ extern "C" int crt_debug_multi_fail_next_alloc(crt_multi *M) {
     M->fail_next_alloc = true;
     return CRT_OK;
 }
+
+// Unit-test hook: lowers the number of stack entries the filter walks may use (SceneArgs::bvh_stack) on a live context -- at least 1,
+// never above what crt_create sized the spill regions for (a larger value restores it) -- so that the walks' "stack too small" exits
+// run: kernel_bvh.h, give_up.  Waits for everything the context has enqueued, then uploads the scene's argument block again.
+extern "C" int crt_debug_set_filter_stack(crt_ctx *ctx, uint32_t entries) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (!ctx->scene.bvh_ok || !ctx->bvh_stack_built) { ctx->error = "the scene has no filter"; return CRT_ERR_INVALID; }
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    CRT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    ctx->scene.bvh_stack = entries < 1u ? 1u : (entries > ctx->bvh_stack_built ? ctx->bvh_stack_built : entries);
+    CRT_HIP_CHECK(ctx, hipMemcpy(ctx->d_scene, &ctx->scene, sizeof(SceneArgs), hipMemcpyHostToDevice));
+    return CRT_OK;
+}

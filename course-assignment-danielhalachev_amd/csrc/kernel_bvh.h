@@ -35,7 +35,7 @@
 // kernels and the bulk shadow pass fit on a CU together), the rest -- rarely reached -- in a device buffer (FrameArgs::bvh_spill, one
 // column per thread of the largest grid).  SceneArgs::bvh_stack entries in all, sized by crt_create from the hierarchy's depth -- three
 // entries per inner node on a path is all a walk can push -- so that no walk outgrows it.
-struct BvhStack { uint32_t *lds; uint32_t *spill; uint32_t stride; };   // lds + threadIdx.x; spill + global thread; threads of the grid
+struct BvhStack { uint32_t *lds; uint32_t *spill; uint32_t stride; size_t room; };   // lds + threadIdx.x; spill + global thread; threads of the grid; words from `spill` to its region's end (read by the bounds-checked build only)
 __device__ __forceinline__ void bvh_push(const BvhStack &S, uint32_t &sp, const uint32_t v) {
     if (sp < BVH_LDS_STACK) S.lds[sp * BLOCK] = v;
     else S.spill[(size_t)(sp - BVH_LDS_STACK) * S.stride] = v;
@@ -45,11 +45,18 @@ __device__ __forceinline__ uint32_t bvh_pop(const BvhStack &S, uint32_t &sp) {
     sp--;
     return sp < BVH_LDS_STACK ? S.lds[sp * BLOCK] : S.spill[(size_t)(sp - BVH_LDS_STACK) * S.stride];
 }
-__device__ __forceinline__ BvhStack bvh_stack_of(const KernelArgs &A, uint32_t *stack_lds, const bool side) {
+// Two launches that may run side by side must not share spill columns: a region per stream of a frame (crt_launch.hip has the list of
+// who runs beside whom), each FrameArgs::bvh_spill_words long: room for the largest grid (crt_ctx::grid_blocks workgroups).
+enum : int { BVH_SPILL_LEVELS = 0,   // the caller's stream: level 0, the level kernels, (behind them) bvh_trace_shadow<1>
+             BVH_SPILL_SIDE = 1,     // the side stream: bvh_trace_shadow<0>, beside the levels and the level queue
+             BVH_SPILL_QUEUE = 2 };  // bvh_trace_queue: on crt_ctx::early beside level 0 and the bulk shadow pass
+__device__ __forceinline__ BvhStack bvh_stack_of(const KernelArgs &A, uint32_t *stack_lds, const int region) {
     BvhStack S;
     S.lds = stack_lds + threadIdx.x;
     S.stride = gridDim.x * BLOCK;
-    S.spill = (side ? A.f->bvh_spill_side : A.f->bvh_spill) + (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    const size_t column = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    S.spill = (region == BVH_SPILL_SIDE ? A.f->bvh_spill_side : region == BVH_SPILL_QUEUE ? A.f->bvh_spill_queue : A.f->bvh_spill) + column;
+    S.room = A.f->bvh_spill_words > column ? (size_t)A.f->bvh_spill_words - column : 0u;
     return S;
 }
 constexpr float BVH_WIDEN = 0x1p-20f;
@@ -65,6 +72,11 @@ constexpr int BVH_STEPS_QUEUE = 8;   // ... in the level queue's launch, where a
 // SC_BVH_DIAG + 2 code, the index beside it -- and index 0 is read instead: a development build that cannot fault)
 enum : int { BVH_PLAIN = 0, BVH_TALLY = 1, BVH_CHECKED = 2 };
 constexpr int SC_BVH_DIAG = SC_HEAVY_DIAG + 16;
+// (SC_BVH_DIAG + 0 .. 31: the bounds-checked build's 16 (flag, index) pairs; + 40 .. 43 and + 48 .. 77: the tallying build's walk lengths)
+constexpr int SC_BVH_MARK = SC_BVH_DIAG + 80;   // tallying and bounds-checked builds: the largest number of entries any walk's stack held in the frame
+static_assert(SC_BVH_MARK < SC_ALLOC_WORDS, "the high-water mark is a word of the frame's counter block");
+// bounds-checked build, codes of its own checks: the spill element lies in its region; a walk's pops returned what its pushes stored
+enum : uint32_t { BVH_CODE_SPILL = 11, BVH_CODE_STACK_SUM = 12 };
 template <int MODE>
 __device__ __forceinline__ uint32_t bvh_at(const KernelArgs &A, const uint32_t i, const uint32_t n, const uint32_t code) {
     if (MODE == BVH_CHECKED && i >= n) { A.f->s_counts[SC_BVH_DIAG + 2 * code] = 1u; A.f->s_counts[SC_BVH_DIAG + 2 * code + 1] = i; return 0u; }
@@ -214,12 +226,49 @@ struct BvhWalk {
     uint32_t bk2, bk3, btri, bmesh, cache_mesh, cache_k2;
     bool have, give_up;
     uint32_t steps;             // BVH_TALLY: steps of this walk (diagnostics)
+    uint32_t mark;              // BVH_TALLY, BVH_CHECKED: the most entries this walk's stack has held
+    uint32_t sum;               // BVH_CHECKED: values pushed minus values popped (mod 2^32): 0 whenever the stack is empty
 };
 __device__ __forceinline__ void bvh_walk_begin(BvhWalk &W, const float tmax) {
     W.cur = 0; W.sp = 0;  // the root is node 0
     W.best = tmax;
     W.bk2 = W.bk3 = NONE; W.btri = 0; W.bmesh = 0; W.cache_mesh = NONE; W.cache_k2 = NONE;
-    W.have = false; W.give_up = false; W.steps = 0;
+    W.have = false; W.give_up = false; W.steps = 0; W.mark = 0; W.sum = 0;
+}
+
+// The walks' pushes and pops.  The plain and the tallying build: bvh_push / bvh_pop and nothing else.  The bounds-checked build compares
+// a spilled entry's place with its region's size first (BVH_CODE_SPILL; outside: nothing is stored, the root is "popped") and keeps the
+// lane's balance of pushed and popped values: an entry that came back changed -- another launch writing into this lane's column --
+// leaves it non-zero when the stack runs empty (BVH_CODE_STACK_SUM).
+template <int MODE>
+__device__ __forceinline__ bool bvh_spill_inside(const KernelArgs &A, const BvhStack &S, const uint32_t sp) {
+    if (MODE != BVH_CHECKED || sp < BVH_LDS_STACK) return true;
+    const size_t at = (size_t)(sp - BVH_LDS_STACK) * S.stride;
+    if (at < S.room) return true;
+    A.f->s_counts[SC_BVH_DIAG + 2 * BVH_CODE_SPILL] = 1u; A.f->s_counts[SC_BVH_DIAG + 2 * BVH_CODE_SPILL + 1] = sp;
+    return false;
+}
+template <int MODE>
+__device__ __forceinline__ void bvh_walk_push(const KernelArgs &A, const BvhStack &S, BvhWalk &W, const uint32_t v) {
+    if (MODE == BVH_CHECKED) {
+        W.sum += v;
+        if (!bvh_spill_inside<MODE>(A, S, W.sp)) { W.sp++; return; }
+    }
+    bvh_push(S, W.sp, v);
+}
+template <int MODE>
+__device__ __forceinline__ uint32_t bvh_walk_pop(const KernelArgs &A, const BvhStack &S, BvhWalk &W) {
+    if (MODE != BVH_CHECKED) return bvh_pop(S, W.sp);
+    uint32_t v = 0u;
+    if (bvh_spill_inside<MODE>(A, S, W.sp - 1u)) v = bvh_pop(S, W.sp); else W.sp--;
+    W.sum -= v;
+    if (W.sp == 0u && W.sum != 0u) { A.f->s_counts[SC_BVH_DIAG + 2 * BVH_CODE_STACK_SUM] = 1u; A.f->s_counts[SC_BVH_DIAG + 2 * BVH_CODE_STACK_SUM + 1] = W.sum; W.sum = 0u; }
+    return v;
+}
+// the frame's high-water mark (SC_BVH_MARK): one atomic each time a walk's stack grows beyond what it has held before
+template <int MODE>
+__device__ __forceinline__ void bvh_walk_mark(const KernelArgs &A, BvhWalk &W) {
+    if (MODE != BVH_PLAIN && W.sp > W.mark) { W.mark = W.sp; atomicMax(A.f->s_counts + SC_BVH_MARK, W.sp); }
 }
 
 // What a walk step reads, whichever kind the lane's `cur` is: seven 16-byte slots and two id words, 30 registers that the two kinds
@@ -265,7 +314,7 @@ __device__ __forceinline__ bool bvh_step(const KernelArgs &A, const Ray &R, cons
     if (W.cur == BVH_EMPTY) {
         if (W.sp == 0) return false;
         bvh_at<MODE>(A, W.sp - 1u, A.s->bvh_stack, 8);
-        W.cur = bvh_pop(stack, W.sp);
+        W.cur = bvh_walk_pop<MODE>(A, stack, W);
     }
     // up to TPS triangles of a leaf per step, all fetched before any is tested; what is left of the leaf stays in `cur`
     constexpr uint32_t TPS = 2u;   // (four per step for the closest-hit walks: measured, no faster, 30 registers more)
@@ -295,9 +344,10 @@ __device__ __forceinline__ bool bvh_step(const KernelArgs &A, const Ray &R, cons
 #undef BVH_CSWAP
         const uint32_t n_push = (c1 != BVH_EMPTY ? 1u : 0u) + (c2 != BVH_EMPTY ? 1u : 0u) + (c3 != BVH_EMPTY ? 1u : 0u);
         if (W.sp + n_push > A.s->bvh_stack) { W.give_up = true; return false; }   // (cannot happen: the stack is sized by the depth)
-        if (c3 != BVH_EMPTY) bvh_push(stack, W.sp, c3);
-        if (c2 != BVH_EMPTY) bvh_push(stack, W.sp, c2);
-        if (c1 != BVH_EMPTY) bvh_push(stack, W.sp, c1);
+        if (c3 != BVH_EMPTY) bvh_walk_push<MODE>(A, stack, W, c3);
+        if (c2 != BVH_EMPTY) bvh_walk_push<MODE>(A, stack, W, c2);
+        if (c1 != BVH_EMPTY) bvh_walk_push<MODE>(A, stack, W, c1);
+        bvh_walk_mark<MODE>(A, W);
         W.cur = c0;  // (BVH_EMPTY when the nearest slot holds a miss -- nothing passed, or a NaN distance out of order: the next step pops)
     } else {
         W.cur = left >= TPS ? (BVH_LEAF | ((left - TPS) << 24) | (first + TPS)) : BVH_EMPTY;
@@ -365,7 +415,7 @@ __device__ __forceinline__ bool bvh_miss_step(const KernelArgs &A, const Ray &R,
     if (W.cur == BVH_EMPTY) {
         if (W.sp == 0) return false;
         bvh_at<MODE>(A, W.sp - 1u, A.s->bvh_stack, 8);
-        W.cur = bvh_pop(stack, W.sp);
+        W.cur = bvh_walk_pop<MODE>(A, stack, W);
     }
     if (!(W.cur & BVH_LEAF)) {
         const uint32_t node = bvh_at<MODE>(A, W.cur, A.s->n_bvh_nodes, 9);
@@ -383,9 +433,10 @@ __device__ __forceinline__ bool bvh_miss_step(const KernelArgs &A, const Ray &R,
         if (W.sp + n_hit > A.s->bvh_stack) { W.give_up = true; return false; }   // (cannot happen: the stack is sized by the depth)
         W.cur = BVH_EMPTY;
         if (h0) { W.cur = c0; }
-        if (h1) { if (W.cur != BVH_EMPTY) bvh_push(stack, W.sp, W.cur); W.cur = c1; }
-        if (h2) { if (W.cur != BVH_EMPTY) bvh_push(stack, W.sp, W.cur); W.cur = c2; }
-        if (h3) { if (W.cur != BVH_EMPTY) bvh_push(stack, W.sp, W.cur); W.cur = c3; }
+        if (h1) { if (W.cur != BVH_EMPTY) bvh_walk_push<MODE>(A, stack, W, W.cur); W.cur = c1; }
+        if (h2) { if (W.cur != BVH_EMPTY) bvh_walk_push<MODE>(A, stack, W, W.cur); W.cur = c2; }
+        if (h3) { if (W.cur != BVH_EMPTY) bvh_walk_push<MODE>(A, stack, W, W.cur); W.cur = c3; }
+        bvh_walk_mark<MODE>(A, W);
     } else {
         const uint32_t left = (W.cur >> 24) & 0x7Fu;
         const uint32_t first = bvh_at<MODE>(A, W.cur & 0x00FFFFFFu, A.s->n_bvh_entries - (left ? 1u : 0u), 10);
@@ -421,7 +472,7 @@ __device__ __forceinline__ void bvh_shade_level(const KernelArgs &A, const uint3
     const uint32_t node_base = stream_level_base(A, gen);
     const uint32_t child_base = node_base + count;
     const float4 *in_q = A.f->s_rayq[gen & 1u];
-    const BvhStack stack = bvh_stack_of(A, stack_lds, false);
+    const BvhStack stack = bvh_stack_of(A, stack_lds, BVH_SPILL_LEVELS);   // (level 0 runs beside the level queue's launch and the bulk shadow pass: each has its region)
     const bool primary = gen == 0;
     uint32_t nbox = 0, ntri = 0;
     Ray R;
@@ -547,7 +598,7 @@ __device__ __forceinline__ void bvh_queue_levels(const KernelArgs &A, uint32_t *
     const gu32 tail_p = (gu32)(A.f->s_lq_words + LQ_TAIL), head_p = (gu32)(A.f->s_lq_words + LQ_HEAD), done_p = (gu32)(A.f->s_lq_words + LQ_DONE),
                ovf_p = (gu32)(A.f->s_lq_words + LQ_ABORT), l0_p = (gu32)(A.f->s_lq_words + LQ_LEVEL0);
     const uint32_t count0 = stream_level_count(A, 0);
-    const BvhStack stack = bvh_stack_of(A, stack_lds, false);
+    const BvhStack stack = bvh_stack_of(A, stack_lds, BVH_SPILL_QUEUE);   // (beside level 0 and the bulk shadow pass: a region of its own)
     const unsigned long long below = (1ull << lane) - 1ull;
     uint32_t nbox = 0, ntri = 0;
     Ray R;
@@ -711,7 +762,7 @@ template <int MODE, bool CHUNKED>
 __device__ __forceinline__ void bvh_shadow_rays(const KernelArgs &A, const uint32_t first, const uint32_t total, uint32_t *cursor, uint32_t *stack_lds) {
     const uint32_t lane = threadIdx.x & 63u;
     if (A.f->s_counts[SC_OVERFLOW]) return;
-    const BvhStack stack = bvh_stack_of(A, stack_lds, true);   // (the bulk pass runs beside the level kernels: a region of its own)
+    const BvhStack stack = bvh_stack_of(A, stack_lds, BVH_SPILL_SIDE);   // (the bulk pass runs beside the level kernels and the level queue's launch: a region of its own; pass 1 runs behind pass 0 and behind the levels)
     const bool every_mesh = A.f->use_gi != 0;
     uint32_t nbox = 0, ntri = 0;
     Ray R;

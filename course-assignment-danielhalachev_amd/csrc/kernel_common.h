@@ -172,7 +172,10 @@ struct FrameArgs {
     unsigned long long *s_lq;     // kernel_bvh.h / kernel_stream.h: the level queue, 8 granules per ray
     uint32_t s_lq_cap, lq_epoch;  // its capacity in rays; this frame's tag (never 0, never a tag the buffer may still hold)
     uint32_t *s_lq_words;         // its counters (kernel_stream.h: LQ_*), zeroed before every frame
-    uint32_t *bvh_spill, *bvh_spill_side;  // kernel_bvh.h: what a walk's stack holds beyond its LDS part, one column per thread of the largest grid (level kernels / shadow passes)
+    // kernel_bvh.h: what a walk's stack holds beyond its LDS part, one column per thread of the largest grid -- a region for each launch that
+    // may run beside another one (level kernels and level 0 / bulk shadow passes / the level queue's launch), bvh_spill_words words each
+    uint32_t *bvh_spill, *bvh_spill_side, *bvh_spill_queue;
+    unsigned long long bvh_spill_words;
     uint32_t heavy_level_threshold; // a recursion level with fewer rays than this goes to heavy_trace whole
     uint32_t fixed0;              // level 0's shadow rays go to fixed, tile-ordered slots (kernel_stream.h: level0_shadow_place)
     uint32_t use_gi, gi_samples, rays_per_pixel, gi_seed;  // crt_options: the GI / multi-sample mode (kernel_stream.h, kernel_lane.h, gi_random.h)

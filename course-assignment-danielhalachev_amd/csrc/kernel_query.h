@@ -91,6 +91,7 @@ __device__ __forceinline__ BvhStack query_stack_of(const QueryArgs &Q, uint32_t 
     S.lds = stack_lds + threadIdx.x;
     S.stride = gridDim.x * BLOCK;
     S.spill = Q.spill + (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    S.room = 0;   // (read by the bounds-checked build only, and the query kernels have none)
     return S;
 }
 

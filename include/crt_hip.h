@@ -461,7 +461,8 @@ int crt_get_executed_counters(crt_ctx *ctx, uint64_t out[4]);
 int crt_get_executed_plan_tests(crt_ctx *ctx, uint64_t out[2]);
 
 /* ---- Test hooks: exported by libcrt_hip_test.so only (the product's objects + csrc/crt_testhooks.hip; libcrt_hip.so has none of them):
- * crt_test_pow5, crt_test_gi, crt_bvh_selftest, crt_debug_multi_force_staged, crt_debug_multi_fail_next_alloc. ---- */
+ * crt_test_pow5, crt_test_gi, crt_bvh_selftest, crt_bvh_census, crt_debug_set_filter_stack, crt_debug_multi_force_staged,
+ * crt_debug_multi_fail_next_alloc. ---- */
 /* Test hook: out[i] = the device build of the restated glibc powf(x[i], 5) (the Fresnel term, RayTracer.cpp:407). */
 int crt_test_pow5(int device, const float *x, float *out, uint64_t n);
 /* Test hook for the GI mode's arithmetic (csrc/glibc_sincosf.h, csrc/gi_random.h), evaluated on `device`, or by the host
@@ -475,6 +476,14 @@ int crt_test_gi(int device, uint32_t what, const uint32_t *a, const uint32_t *b,
  * a leaf the ray's line passes, of which the miss check does not reach (must be 0), nodes visited by the two walks, structural
  * errors (must be 0)}.  CRT_ERR_INVALID when the scene has no filter. */
 int crt_bvh_selftest(const crt_scene_desc *scene, const float *rays, uint32_t n_rays, int primary, uint64_t out[8]);
+/* Test hook, HOST ONLY: the shape of that filter: out = {nodes, entries, depth of the binary build, inner nodes on the longest path of
+ * the 4-wide hierarchy (a walk's stack is sized 3 x this + 1), triangles verified by the pruned tree walk (BVH_TRI_WALK), 0, 0, 0}.
+ * CRT_ERR_INVALID when the scene has no filter. */
+int crt_bvh_census(const crt_scene_desc *scene, uint64_t out[8]);
+/* Test hook: the filter walks of a live context may use `entries` stack entries from now on -- clamped to [1, what crt_create sized
+ * the stacks for], so a large value restores the built size.  Waits for the context's work; changes no pixel (a walk that runs out of
+ * stack sends its frame to the queue-less kernel -- crt_stats::fallback_frames -- and its query ray to the reference-order walk). */
+int crt_debug_set_filter_stack(crt_ctx *ctx, uint32_t entries);
 
 /* Diagnostics for the development tools under tools/ (no counterpart in the reference; not needed to render):
  * the ray-stream pass's queue counters of the last frame (rays per recursion level, walks handed to the

@@ -7,6 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import query_sets as qs
+import rare_sets as rs
 from helpers import small_case
 
 
@@ -78,3 +80,77 @@ def test_primary_rays_of_the_benchmark_scene(pkg, scenes):
     rays = np.concatenate([np.tile(cam, (200, 1)), d], axis=1)
     r = _selftest(pkg, scenes, scene, rays, primary=True)
     assert r["errors"] == 0 and r["finite_hits"] >= 200 and r["finite_missed"] == 0 and r["other_missed"] == 0
+
+
+# ---- the scenes of the rare routes (tests/rare_sets.py; the GPU side is tests/test_gpu_filter_rare.py)
+def _census(pkg, scenes, scene):
+    hs = pkg.Scene(json_text=scenes.to_json(scene))
+    L = pkg.lib()
+    L.crt_bvh_census.argtypes = [C.POINTER(pkg.SceneDesc), C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 8)()
+    assert L.crt_bvh_census(C.byref(hs.desc), out) == 0
+    return dict(zip(("nodes", "entries", "depth", "wide_depth", "walk_triangles"), [int(v) for v in out]))
+
+
+def _assert_filter_holds(r, n_rays):
+    assert r["errors"] == 0 and r["finite_missed"] == 0 and r["other_missed"] == 0
+    assert r["finite_hits"] > n_rays // 2
+
+
+def test_deep_stack_scene_census(pkg, scenes, oracle):
+    """The filter of the card scene is deep enough for its walks to outgrow the 16 stack entries held in LDS, first hits land at
+    every depth of the stack of cards, deeper levels and shadow rays exist, and the filter's two promises hold for the ray set
+    (every sixteenth ray: the brute force behind the self-test is rays x cards)."""
+    scene = rs.deep_stack_scene()
+    c = _census(pkg, scenes, scene)
+    print("deep stack: n %d census %r" % (rs.DEEP_N, c))
+    assert 3 * c["wide_depth"] + 1 > 16 and c["entries"] == rs.DEEP_N and c["walk_triangles"] == 0
+    # six levels of four children each: a walk along the line holds up to 18 entries.  Half as many cards: one level has two children,
+    # 3 x 5 + 1 = 16 entries, all in LDS (measured on the GPU: 16)
+    assert (c["depth"], c["wide_depth"]) == (12, 6) and c["nodes"] == (4 ** 6 - 1) // 3
+    half = _census(pkg, scenes, rs.deep_stack_scene(rs.DEEP_N // 2))
+    assert (half["depth"], half["wide_depth"]) == (11, 6)
+    o = oracle.OracleScene(scenes.to_blob(scene))
+    rays = rs.deep_stack_rays(o)
+    assert len(rays) == 2 * 32 * 24 + 2048
+    frame, counters = o.render(3)
+    assert len(np.unique(frame.reshape(-1, 3), axis=0)) > 300          # a hit's colour says which card it was
+    hits = qs.oracle_hits(o, scene, rays, qs.RAY_REFLECTION, pkg.HIT_DTYPE)
+    cards = rs.first_hit_cards(scene, hits)
+    quartiles = np.quantile(cards[cards >= 0], [0.25, 0.5, 0.75])
+    print("deep stack: hits %d of %d, first-hit card quartiles %r" % (int(hits["hit"].sum()), len(rays), quartiles))
+    assert quartiles[0] < rs.DEEP_N // 4 and quartiles[2] > rs.DEEP_N // 2
+    mirrors = hits["hit"].astype(bool) & (hits["mesh"] == 1)
+    assert mirrors.sum() > 200                                           # reflection children
+    _assert_filter_holds(_selftest(pkg, scenes, scene, rays[::16]), len(rays[::16]))
+
+
+def test_leaf_walk_scene_census(pkg, scenes, oracle):
+    scene, large = rs.leaf_walk_scene()
+    assert _census(pkg, scenes, scene)["walk_triangles"] >= 2
+    o = oracle.OracleScene(scenes.to_blob(scene))
+    rays = rs.leaf_walk_rays()
+    hits = qs.oracle_hits(o, scene, rays, qs.RAY_REFLECTION, pkg.HIT_DTYPE)
+    share_large, share_in_front = rs.leaf_walk_census(scene, large, rays, hits)
+    print("leaf walk: winners %d, large %.3f, small in front of a large one %.3f" % (int(hits["hit"].sum()), share_large, share_in_front))
+    assert share_large >= 0.2 and share_in_front >= 0.2
+    assert len(np.unique(hits["mesh"][hits["hit"].astype(bool)])) == 2  # cache_mesh changes along rays
+    _assert_filter_holds(_selftest(pkg, scenes, scene, rays), len(rays))
+
+
+def test_tie_scene_census(pkg, scenes, oracle):
+    """At least 100 rays per kind on which both copies are hit at the same bit pattern of t; the reversed scene names the other copy."""
+    rays = rs.tie_rays()
+    census = rs.tie_census(oracle, scenes, rays)
+    print("ties:", {k: int(v.sum()) for k, v in census.items()})
+    assert all(int(census[k].sum()) >= 100 for k in "ABC")
+    winners = {}
+    for reverse in (False, True):
+        scene, info = rs.tie_scene(reverse=reverse)
+        assert _census(pkg, scenes, scene)["walk_triangles"] >= 2
+        o = oracle.OracleScene(scenes.to_blob(scene))
+        hits = qs.oracle_hits(o, scene, rays, qs.RAY_REFLECTION, pkg.HIT_DTYPE)
+        material = np.array([ob["material_index"] for ob in scene["objects"]])[hits["mesh"]]
+        winners[reverse] = material[census["B"]]
+        _assert_filter_holds(_selftest(pkg, scenes, scene, rays), len(rays))
+    assert set(winners[False]) == {1} and set(winners[True]) == {2}     # the first copy in the scene's order, whichever it is
