@@ -164,9 +164,9 @@ def tuning_from_string(text):
 
 
 # every symbol include/crt_hip.h and include/crt_host.h declare; the test hooks are exported by libcrt_hip_test.so only
-TEST_HOOK_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_stack", "crt_test_pow5", "crt_test_gi", "crt_debug_multi_force_staged",
-                     "crt_debug_multi_fail_next_alloc"]
-DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_stack", "crt_tuning_defaults", "crt_create_tuned", "crt_create", "crt_set_camera", "crt_render", "crt_render_tiles_device", "crt_packed_tile_count",
+TEST_HOOK_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_stack", "crt_debug_set_query_chunks", "crt_test_pow5", "crt_test_gi",
+                     "crt_debug_multi_force_staged", "crt_debug_multi_fail_next_alloc"]
+DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_stack", "crt_debug_set_query_chunks", "crt_tuning_defaults", "crt_create_tuned", "crt_create", "crt_set_camera", "crt_render", "crt_render_tiles_device", "crt_packed_tile_count",
                   "crt_unpack_tiles_device", "crt_quantize_device", "crt_read_quantized", "crt_kernel_elapsed_ms", "crt_kernel_times_ms",
                   "crt_get_stats", "crt_get_kernel_counters", "crt_synchronize", "crt_destroy", "crt_last_error", "crt_device_count", "crt_test_pow5", "crt_test_gi",
                   "crt_describe_kernels", "crt_debug_stream_counts", "crt_get_executed_counters", "crt_get_executed_plan_tests",
@@ -694,6 +694,14 @@ class Tracer:
         L = lib()
         L.crt_debug_set_filter_stack.argtypes = [C.c_void_p, C.c_uint32]
         self._check(L.crt_debug_set_filter_stack(self.ctx, int(entries)))
+
+    def set_query_chunks(self, host_rays=0, launch_rays=0, pass_rays=0):
+        """Test hook (libcrt_hip_test.so): the queries' chunk sizes from now on -- rays per round trip of the host variants, per launch,
+        per pass of a radiance query; 0 restores a default, other values are clamped to [64, the default]."""
+        self._single("set_query_chunks")
+        L = lib()
+        L.crt_debug_set_query_chunks.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64]
+        self._check(L.crt_debug_set_query_chunks(self.ctx, int(host_rays), int(launch_rays), int(pass_rays)))
 
     def stream_counts(self):
         """Diagnostics: the ray-stream pass's counter block of the last frame (SC_* layout of csrc/kernel_stream.h)."""

@@ -4,7 +4,8 @@
 //   crt_launch.hip    the kernels and one frame's launches: frame plan, queue sizing, events
 //   crt_abi.hip       the render entry points, tiles, statistics
 //   crt_multi.hip     one scene on several devices behind one call
-//   crt_query.hip     ray queries: closest hit / occlusion for the caller's rays, the camera's rays
+//   crt_query.hip     the queries for what the caller supplies, behind one call path: ray queries (closest hit / occlusion, the camera's rays),
+//                     direct lighting of hit records and points, radiance queries; their scratch and statistics
 //   crt_testhooks.hip unit-test hooks (libcrt_hip_test.so only)
 #pragma once
 
@@ -29,6 +30,14 @@
 #include "kernel_common.h"
 
 #define CRT_INTERNAL __attribute__((visibility("hidden")))
+
+// crt_query.hip's chunk sizes, as a context starts with them (crt_ctx::query_launch_rays ...: a test hook may lower them).
+// rays per launch: indices, the cursor's overshoot (claimed and dropped) and the list's length stay well inside 31 bits
+constexpr uint64_t QUERY_LAUNCH_RAYS = 1ull << 27;
+// rays per round trip of the host variants (their device copies: 24 + 48 bytes a ray)
+constexpr uint64_t QUERY_HOST_RAYS = 1ull << 22;
+// radiance queries: the caller's rays per pass (every level of a pass has arrays of its own: 117 bytes a ray)
+constexpr uint64_t SHOOT_PASS_RAYS = 1ull << 22;
 
 // =================================================================================================
 // host side of the C ABI
@@ -114,6 +123,7 @@ struct crt_ctx {
     crt_stats stats{};
     int num_cus = 0;
     struct crt_query_state *query = nullptr;   // crt_query.hip: the ray queries' scratch and statistics, created by the first query
+    uint64_t query_host_rays = QUERY_HOST_RAYS, query_launch_rays = QUERY_LAUNCH_RAYS, shoot_pass_rays = SHOOT_PASS_RAYS;   // ... and its chunk sizes
 };
 
 // constants that round 2 carried as crt_tuning fields (DESIGN.md section 7 has the measurements)

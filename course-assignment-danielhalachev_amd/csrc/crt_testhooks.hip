@@ -104,3 +104,17 @@ extern "C" int crt_debug_set_filter_stack(crt_ctx *ctx, uint32_t entries) {
     CRT_HIP_CHECK(ctx, hipMemcpy(ctx->d_scene, &ctx->scene, sizeof(SceneArgs), hipMemcpyHostToDevice));
     return CRT_OK;
 }
+
+// Unit-test hook: the queries' chunk sizes (crt_ctx::query_host_rays, query_launch_rays, shoot_pass_rays) on a live context, so that a
+// few thousand rays run crt_query.hip's chunk loops.  0 restores a default; other values are clamped to [64, the default].  Waits for
+// everything the context has enqueued.
+extern "C" int crt_debug_set_query_chunks(crt_ctx *ctx, uint64_t host_rays, uint64_t launch_rays, uint64_t pass_rays) {
+    if (!ctx) return CRT_ERR_INVALID;
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    CRT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    const auto chunk = [](uint64_t v, uint64_t dflt) { return v == 0 ? dflt : std::min(std::max<uint64_t>(v, 64u), dflt); };
+    ctx->query_host_rays = chunk(host_rays, QUERY_HOST_RAYS);
+    ctx->query_launch_rays = chunk(launch_rays, QUERY_LAUNCH_RAYS);
+    ctx->shoot_pass_rays = chunk(pass_rays, SHOOT_PASS_RAYS);
+    return CRT_OK;
+}

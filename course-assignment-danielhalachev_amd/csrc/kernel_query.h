@@ -9,8 +9,8 @@
 //   * a ray comes out of the caller's array AS GIVEN (the reference's Ray holds what it is handed; camera rays and shootRay
 //     normalise before they build one) and its answer goes to the caller's array: no ray tree, no queues, no shading;
 //   * a ray the filter cannot answer -- a direction that is not of unit length (QUERY_UNIT_TOL), a non-finite coordinate, a miss
-//     that the miss check refutes, a stack that runs out -- does NOT condemn the launch, as it condemns a frame: the lane appends
-//     the ray's index to a list (one atomic per wave and round) and query_reroute, launched behind on the same stream, walks the
+//     that the miss check refutes, a stack that runs out -- does NOT condemn the launch, as it condemns a frame: the lane of
+//     query_walk appends the ray's index to a list (one atomic per wave and round) and query_reroute, launched behind on the same stream, walks the
 //     listed rays in the reference's order.  No host round trip: the device variants stay asynchronous.
 //   * the launches have scratch of their own (walk-stack spill columns, list, counter words: crt_query.hip), never a frame's.
 #pragma once
@@ -81,10 +81,22 @@ __device__ __forceinline__ void query_append(const QueryArgs &Q, const bool mine
         Q.list[base + rank] = r;
     }
 }
-__device__ __forceinline__ void query_count_hits(const QueryArgs &Q, const uint32_t n_hits, const uint32_t lane) {
-    unsigned long long h = n_hits;
-    for (int off = 32; off > 0; off >>= 1) h += __shfl_down(h, off);
-    if (lane == 0 && h) atomicAdd(reinterpret_cast<unsigned long long *>(Q.words + QW_HITS), h);
+// the wave's sum of n, added to the 64-bit counter at `word` by one atomic
+__device__ __forceinline__ void wave_add_u64(uint32_t *word, const uint32_t n, const uint32_t lane) {
+    unsigned long long v = n;
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    if (lane == 0 && v) atomicAdd(reinterpret_cast<unsigned long long *>(word), v);
+}
+// the Ray of a lane that holds none yet
+__device__ __forceinline__ Ray query_no_ray() {
+    Ray R;
+    R.ox = R.oy = R.oz = R.dx = R.dy = R.dz = R.ix = R.iy = R.iz = 0; R.parmask = 0;
+    return R;
+}
+// a walk that ended without a hit starts over as the miss check (kernel_bvh.h: bvh_miss_step)
+__device__ __forceinline__ void query_begin_miss_check(const KernelArgs &A, const Ray &R, BvhWalk &W) {
+    W.cur = 0; W.sp = 0; W.cache_mesh = NONE; W.cache_k2 = NONE;
+    bvh_line_setup(A, R, W.B);
 }
 __device__ __forceinline__ BvhStack query_stack_of(const QueryArgs &Q, uint32_t *stack_lds) {
     BvhStack S;
@@ -95,20 +107,28 @@ __device__ __forceinline__ BvhStack query_stack_of(const QueryArgs &Q, uint32_t 
     return S;
 }
 
-// Closest hit: persistent waves, a lane per ray, bvh_shade_level's state machine (kernel_bvh.h) with the shading replaced by the
-// hit's record.  Work indices are claimed per wave in chunks, as level 0 claims its primary rays; a wave looks after its free
-// lanes when BVH_BATCH of them have gathered.
-template <int MODE>
-__global__ __launch_bounds__(BLOCK) void query_closest(const KernelArgs A, const QueryArgs Q) {
+// The filter kernel of both ray queries: persistent waves, a lane per ray, bvh_shade_level's state machine (kernel_bvh.h) with the
+// shading replaced by the answer's store.  Work indices are claimed per wave in chunks, as level 0 claims its primary rays; a wave
+// looks after its free lanes when BVH_BATCH of them have gathered.
+//   closest hit (OCCLUDED = false): the walk has no end, and a ray without a hit goes through the miss check.
+//   occlusion (OCCLUDED = true): checkForIntersection(ray, max_distance) of the non-GI build for a shadow ray
+//     (AccelerationStructure.cpp:56-94): refractive meshes skipped, a mesh occludes when its closest hit lies within
+//     length(point - origin) <= max_distance.  The walk is bvh_shadow_rays' (kernel_bvh.h): it ends at max_distance (1 + 2^-16) and at
+//     the first verified occluder.  A max_distance that is not finite lets a mesh's closest hit at t = +inf count as well (length = inf
+//     <= inf), and such a hit is no candidate of the filter: those rays (and only those) go through the miss check when the walk found
+//     no occluder, like a closest-hit ray without a hit -- nothing found (all but certain): not occluded; something found: the
+//     reference-order walk decides.
+template <int MODE, bool OCCLUDED>
+__global__ __launch_bounds__(BLOCK) void query_walk(const KernelArgs A, const QueryArgs Q) {
     __shared__ uint32_t stack_lds[BVH_LDS_STACK * BLOCK];
     const uint32_t lane = threadIdx.x & 63u;
     const BvhStack stack = query_stack_of(Q, stack_lds);
-    const bool primary = Q.ray_type == (uint32_t)RAY_PRIMARY;
+    const bool primary = !OCCLUDED && Q.ray_type == (uint32_t)RAY_PRIMARY;
     uint32_t nbox = 0, ntri = 0, n_hits = 0;
-    Ray R;
-    R.ox = R.oy = R.oz = R.dx = R.dy = R.dz = R.ix = R.iy = R.iz = 0; R.parmask = 0;
+    Ray R = query_no_ray();
     BvhWalk W;
     bvh_walk_begin(W, INFINITY);
+    float light_dist = 0;   // (occlusion only)
     int state = BVH_FETCH;
     uint32_t r = 0;
     WaveChunk chunk{0u, 0u};
@@ -119,7 +139,8 @@ __global__ __launch_bounds__(BLOCK) void query_closest(const KernelArgs A, const
                 // a ray the filter cannot take, a miss refuted: the ray (not the launch) goes to the reference-order walk
                 query_append(Q, W.give_up, r, lane);
                 if (!W.give_up) {
-                    query_write_hit(A, Q, r, R, W.have, W.best, W.btri, W.bmesh);
+                    if constexpr (OCCLUDED) Q.occluded[r] = W.have ? 1 : 0;
+                    else query_write_hit(A, Q, r, R, W.have, W.best, W.btri, W.bmesh);
                     n_hits += W.have ? 1u : 0u;
                 }
                 state = BVH_FETCH;
@@ -131,7 +152,11 @@ __global__ __launch_bounds__(BLOCK) void query_closest(const KernelArgs A, const
                 if (r >= Q.n) state = BVH_OUT;
                 else {
                     query_load_ray(Q, r, R);
-                    bvh_walk_begin(W, INFINITY);
+                    if constexpr (OCCLUDED) {
+                        light_dist = Q.max_distance[r];
+                        // an occluding hit has length(d t) <= max_distance with |d| = 1 up to QUERY_UNIT_TOL: t <= max_distance (1 + 2^-16)
+                        bvh_walk_begin(W, light_dist * (1.0f + 0x1p-16f));
+                    } else bvh_walk_begin(W, INFINITY);
                     if (bvh_ray_setup(A, R, W.B) && query_direction_is_unit(R)) state = BVH_WALK;
                     else { W.give_up = true; state = BVH_FINISHED; }
                 }
@@ -140,9 +165,9 @@ __global__ __launch_bounds__(BLOCK) void query_closest(const KernelArgs A, const
         if (!__ballot(state != BVH_OUT)) break;
         if (state == BVH_WALK) {
             for (int it = 0; it < BVH_STEPS; ++it)
-                if (state == BVH_WALK && !bvh_step<0, MODE>(A, R, primary, 0.0f, false, W, stack, nbox, ntri)) {
-                    if (W.have || W.give_up) state = BVH_FINISHED;
-                    else { W.cur = 0; W.sp = 0; W.cache_mesh = NONE; W.cache_k2 = NONE; bvh_line_setup(A, R, W.B); state = BVH_MISS_CHECK; }
+                if (state == BVH_WALK && !bvh_step<OCCLUDED ? 1 : 0, MODE>(A, R, primary, light_dist, false, W, stack, nbox, ntri)) {
+                    if (W.have || W.give_up || (OCCLUDED && light_dist < INFINITY)) state = BVH_FINISHED;
+                    else { query_begin_miss_check(A, R, W); state = BVH_MISS_CHECK; }
                 }
         }
         if (state == BVH_MISS_CHECK) {
@@ -150,68 +175,7 @@ __global__ __launch_bounds__(BLOCK) void query_closest(const KernelArgs A, const
                 if (state == BVH_MISS_CHECK && !bvh_miss_step<MODE>(A, R, primary, W, stack, nbox, ntri)) state = BVH_FINISHED;
         }
     }
-    query_count_hits(Q, n_hits, lane);
-}
-
-// Occlusion: checkForIntersection(ray, max_distance) of the non-GI build for a shadow ray (AccelerationStructure.cpp:56-94):
-// refractive meshes skipped, a mesh occludes when its closest hit lies within length(point - origin) <= max_distance.  The walk is
-// bvh_shadow_rays' (kernel_bvh.h): it ends at max_distance (1 + 2^-16) and at the first verified occluder.
-// A max_distance that is not finite lets a mesh's closest hit at t = +inf count as well (length = inf <= inf), and such a hit is no
-// candidate of the filter: those rays (and only those) go through the miss check when the walk found no occluder, like a
-// closest-hit ray without a hit -- nothing found (all but certain): not occluded; something found: the reference-order walk decides.
-template <int MODE>
-__global__ __launch_bounds__(BLOCK) void query_occluded(const KernelArgs A, const QueryArgs Q) {
-    __shared__ uint32_t stack_lds[BVH_LDS_STACK * BLOCK];
-    const uint32_t lane = threadIdx.x & 63u;
-    const BvhStack stack = query_stack_of(Q, stack_lds);
-    uint32_t nbox = 0, ntri = 0, n_hits = 0;
-    Ray R;
-    R.ox = R.oy = R.oz = R.dx = R.dy = R.dz = R.ix = R.iy = R.iz = 0; R.parmask = 0;
-    BvhWalk W;
-    bvh_walk_begin(W, INFINITY);
-    float light_dist = 0;
-    int state = BVH_FETCH;
-    uint32_t r = 0;
-    WaveChunk chunk{0u, 0u};
-    for (;;) {
-        const uint32_t n_free = (uint32_t)__popcll(__ballot(state == BVH_FETCH || state == BVH_FINISHED));
-        if (n_free >= BVH_BATCH || (n_free && !__ballot(state == BVH_WALK || state == BVH_MISS_CHECK))) {
-            if (state == BVH_FINISHED) {
-                query_append(Q, W.give_up, r, lane);
-                if (!W.give_up) {
-                    Q.occluded[r] = W.have ? 1 : 0;
-                    n_hits += W.have ? 1u : 0u;
-                }
-                state = BVH_FETCH;
-            }
-            const uint32_t claimed = wave_fetch_chunked(Q.words + QW_CURSOR, lane, state == BVH_FETCH, chunk, Q.chunk, Q.n);
-            if (state == BVH_FETCH) {
-                r = claimed;
-                if (r >= Q.n) state = BVH_OUT;
-                else {
-                    query_load_ray(Q, r, R);
-                    light_dist = Q.max_distance[r];
-                    // an occluding hit has length(d t) <= max_distance with |d| = 1 up to QUERY_UNIT_TOL: t <= max_distance (1 + 2^-16)
-                    bvh_walk_begin(W, light_dist * (1.0f + 0x1p-16f));
-                    if (bvh_ray_setup(A, R, W.B) && query_direction_is_unit(R)) state = BVH_WALK;
-                    else { W.give_up = true; state = BVH_FINISHED; }
-                }
-            }
-        }
-        if (!__ballot(state != BVH_OUT)) break;
-        if (state == BVH_WALK) {
-            for (int it = 0; it < BVH_STEPS; ++it)
-                if (state == BVH_WALK && !bvh_step<1, MODE>(A, R, false, light_dist, false, W, stack, nbox, ntri)) {
-                    if (W.have || W.give_up || light_dist < INFINITY) state = BVH_FINISHED;
-                    else { W.cur = 0; W.sp = 0; W.cache_mesh = NONE; W.cache_k2 = NONE; bvh_line_setup(A, R, W.B); state = BVH_MISS_CHECK; }
-                }
-        }
-        if (state == BVH_MISS_CHECK) {
-            for (int it = 0; it < BVH_STEPS; ++it)
-                if (state == BVH_MISS_CHECK && !bvh_miss_step<MODE>(A, R, false, W, stack, nbox, ntri)) state = BVH_FINISHED;
-        }
-    }
-    query_count_hits(Q, n_hits, lane);
+    wave_add_u64(Q.words + QW_HITS, n_hits, lane);
 }
 
 // The rays the filter kernel listed (or, `direct`, every ray of the launch), walked in the reference's order, a lane per ray:
@@ -223,8 +187,7 @@ __global__ __launch_bounds__(BLOCK) void query_reroute(const KernelArgs A, const
     if (blockIdx.x == 0 && threadIdx.x == 0 && count) atomicAdd(reinterpret_cast<unsigned long long *>(Q.words + QW_REROUTED), (unsigned long long)count);
     if ((uint64_t)blockIdx.x * BLOCK >= count) return;
     const uint32_t lane = threadIdx.x & 63u;
-    Ray R;
-    R.ox = R.oy = R.oz = R.dx = R.dy = R.dz = R.ix = R.iy = R.iz = 0; R.parmask = 0;
+    Ray R = query_no_ray();
     LaneWalk L;
     traversal_begin(L, A.s->top_root);
     L.rtype = RAY_REFLECTION; L.light_dist = 0;
@@ -255,7 +218,7 @@ __global__ __launch_bounds__(BLOCK) void query_reroute(const KernelArgs A, const
                 state = ST_FETCH;
             }
     }
-    query_count_hits(Q, n_hits, lane);
+    wave_add_u64(Q.words + QW_HITS, n_hits, lane);
 }
 
 // RayTracer::getRay (RayTracer.cpp:61-80) at the pixel centre, one thread per pixel, row-major: the direction normalised ONCE, as

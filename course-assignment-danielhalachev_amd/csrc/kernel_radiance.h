@@ -1,6 +1,6 @@
 // kernel_radiance.h -- radiance queries (crt_shoot_rays*): what RayTracer::shootRay (RayTracer.cpp:419-451, the non-GI build) returns
 // for rays the CALLER supplies, level by level.  The walks and the direct lighting are the queries that exist (kernel_query.h:
-// query_closest / query_reroute, kernel_shade.h: query_direct / query_direct_reroute); the three small kernels here are the recursion
+// query_walk / query_reroute, kernel_shade.h: query_direct / query_direct_reroute); the three small kernels here are the recursion
 // around them, and the host loop (crt_query.hip) runs them one level behind the other:
 //
 //   radiance_prepare   level 0 only: the caller's rays into the level's ray array, normalised as shootRay's entry does it;

@@ -6,7 +6,7 @@
 // record the filter cannot answer goes ALONE to the reference-order walk behind it.  What is new is the light loop inside a lane:
 //   * a lane owns its record from load to store.  The reference adds the lights' contributions in scene order and float addition
 //     does not commute, so the sum stays where it is formed: one record's lights are never split over lanes;
-//   * every light is light_setup's shadow ray (kernel_common.h, the bias from the query's arguments) walked like query_occluded
+//   * every light is light_setup's shadow ray (kernel_common.h, the bias from the query's arguments) walked like query_walk<.., true>
 //     walks a caller's ray: to distance (1 + 2^-16), to the first verified occluder;
 //   * when ANY of a record's shadow rays cannot be taken by the filter -- a non-finite coordinate (a record at t = inf / NaN), a
 //     zero direction (a light AT the point), a stack that runs out -- the whole record is listed and query_direct_reroute redoes
@@ -63,13 +63,8 @@ __device__ __forceinline__ void shade_store(const KernelArgs &A, const ShadeArgs
     S.out[3 * (size_t)r] = x; S.out[3 * (size_t)r + 1] = y; S.out[3 * (size_t)r + 2] = z;
     if (S.status) S.status[r] = (uint8_t)status;
 }
-__device__ __forceinline__ void shade_count(uint32_t *word, const uint32_t n, const uint32_t lane) {
-    unsigned long long v = n;
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    if (lane == 0 && v) atomicAdd(reinterpret_cast<unsigned long long *>(word), v);
-}
 
-// query_occluded's state machine with a light index inside the lane: BVH_FETCH (wants a record), BVH_SHADOWS (between two lights:
+// query_walk<.., true>'s state machine with a light index inside the lane: BVH_FETCH (wants a record), BVH_SHADOWS (between two lights:
 // sets up the next shadow ray, or is through), BVH_WALK, BVH_FINISHED (its record is to be stored or listed), BVH_OUT.
 template <int MODE, bool POINTS>
 __global__ __launch_bounds__(BLOCK) void query_direct(const KernelArgs A, const ShadeArgs S) {
@@ -79,8 +74,7 @@ __global__ __launch_bounds__(BLOCK) void query_direct(const KernelArgs A, const 
     const BvhStack stack = query_stack_of(Q, stack_lds);
     const uint32_t n_lights = A.s->n_lights;
     uint32_t nbox = 0, ntri = 0, n_diffuse = 0;
-    Ray R;
-    R.ox = R.oy = R.oz = R.dx = R.dy = R.dz = R.ix = R.iy = R.iz = 0; R.parmask = 0;
+    Ray R = query_no_ray();
     BvhWalk W;
     bvh_walk_begin(W, INFINITY);
     ShadeRecord H;
@@ -121,7 +115,7 @@ __global__ __launch_bounds__(BLOCK) void query_direct(const KernelArgs A, const 
                 light_setup(A, li, H.px, H.py, H.pz, H.nx, H.ny, H.nz, S.shadow_bias, R, light_dist, kfac);
                 // an occluding hit has length(d t) <= distance with |d| = 1 up to rounding: t <= distance (1 + 2^-16) (NaN: no bound)
                 bvh_walk_begin(W, light_dist * (1.0f + 0x1p-16f));
-                // query_occluded's entry conditions.  A light at distance 0 leaves a zero direction (normalize3 returns it as it is), a
+                // query_walk's entry conditions.  A light at distance 0 leaves a zero direction (normalize3 returns it as it is), a
                 // non-finite point or normal a non-finite ray: neither is the filter's.
                 if (!(bvh_ray_setup(A, R, W.B) && query_direction_is_unit(R))) { reroute = true; state = BVH_FINISHED; }
                 // No walk for a factor of +-0 (the light behind the surface: angle = max(0, l . n) = 0, or intensity 0) and a finite base:
@@ -148,7 +142,7 @@ __global__ __launch_bounds__(BLOCK) void query_direct(const KernelArgs A, const 
                 }
         }
     }
-    shade_count(Q.words + QW_HITS, n_diffuse, lane);
+    wave_add_u64(Q.words + QW_HITS, n_diffuse, lane);
 }
 
 // The records query_direct listed (or, `direct`, every record of the launch: a scene without a filter, crt_tuning::bvh == 0), a lane per
@@ -161,8 +155,7 @@ __global__ __launch_bounds__(BLOCK) void query_direct_reroute(const KernelArgs A
     if ((uint64_t)blockIdx.x * BLOCK >= count) return;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t n_lights = A.s->n_lights;
-    Ray R;
-    R.ox = R.oy = R.oz = R.dx = R.dy = R.dz = R.ix = R.iy = R.iz = 0; R.parmask = 0;
+    Ray R = query_no_ray();
     LaneWalk L;
     traversal_begin(L, A.s->top_root);
     L.rtype = RAY_SHADOW; L.light_dist = 0;
@@ -209,6 +202,6 @@ __global__ __launch_bounds__(BLOCK) void query_direct_reroute(const KernelArgs A
                 next_light = true;
             }
     }
-    shade_count(Q.words + QW_HITS, n_diffuse, lane);
-    shade_count(Q.words + QW_REROUTED, n_diffuse, lane);   // (the records redone here are the DIFFUSE ones: the others need no walk)
+    wave_add_u64(Q.words + QW_HITS, n_diffuse, lane);
+    wave_add_u64(Q.words + QW_REROUTED, n_diffuse, lane);   // (the records redone here are the DIFFUSE ones: the others need no walk)
 }

@@ -461,8 +461,8 @@ int crt_get_executed_counters(crt_ctx *ctx, uint64_t out[4]);
 int crt_get_executed_plan_tests(crt_ctx *ctx, uint64_t out[2]);
 
 /* ---- Test hooks: exported by libcrt_hip_test.so only (the product's objects + csrc/crt_testhooks.hip; libcrt_hip.so has none of them):
- * crt_test_pow5, crt_test_gi, crt_bvh_selftest, crt_bvh_census, crt_debug_set_filter_stack, crt_debug_multi_force_staged,
- * crt_debug_multi_fail_next_alloc. ---- */
+ * crt_test_pow5, crt_test_gi, crt_bvh_selftest, crt_bvh_census, crt_debug_set_filter_stack, crt_debug_set_query_chunks,
+ * crt_debug_multi_force_staged, crt_debug_multi_fail_next_alloc. ---- */
 /* Test hook: out[i] = the device build of the restated glibc powf(x[i], 5) (the Fresnel term, RayTracer.cpp:407). */
 int crt_test_pow5(int device, const float *x, float *out, uint64_t n);
 /* Test hook for the GI mode's arithmetic (csrc/glibc_sincosf.h, csrc/gi_random.h), evaluated on `device`, or by the host
@@ -484,6 +484,10 @@ int crt_bvh_census(const crt_scene_desc *scene, uint64_t out[8]);
  * the stacks for], so a large value restores the built size.  Waits for the context's work; changes no pixel (a walk that runs out of
  * stack sends its frame to the queue-less kernel -- crt_stats::fallback_frames -- and its query ray to the reference-order walk). */
 int crt_debug_set_filter_stack(crt_ctx *ctx, uint32_t entries);
+/* Test hook: the chunk sizes of the queries of a live context from now on, so that a few thousand rays run their chunk loops: rays per
+ * round trip of the host variants (2^22), per launch (2^27), per pass of a radiance query (2^22).  0 restores the default; any other
+ * value is clamped to [64, the default].  Waits for the context's work; changes no answer and no statistic but kernel_ms. */
+int crt_debug_set_query_chunks(crt_ctx *ctx, uint64_t host_rays, uint64_t launch_rays, uint64_t pass_rays);
 
 /* Diagnostics for the development tools under tools/ (no counterpart in the reference; not needed to render):
  * the ray-stream pass's queue counters of the last frame (rays per recursion level, walks handed to the

@@ -39,6 +39,31 @@ def assert_same_floats(got, want, what=""):
             what, n, diff.size, idx.tolist(), got[tuple(idx[0])], want[tuple(idx[0])]))
 
 
+def assert_same_hits(got, want, what):
+    """crt_hit records (HIT_DTYPE): every integer equal, every float bit for bit"""
+    assert got.dtype == want.dtype and got.shape == want.shape
+    for field in ("hit", "mesh", "triangle"):
+        bad = np.flatnonzero(got[field] != want[field])
+        assert bad.size == 0, "%s: %s differs for %d rays, first %d: got %r want %r" % (what, field, bad.size, bad[0], got[bad[0]], want[bad[0]])
+    for field in ("t", "point", "normal", "u", "v"):
+        assert_same_floats(got[field], want[field], "%s: %s" % (what, field))
+
+
+def assert_shaded(pkg, rgb, status, want_status, want, what):
+    """colours and CRT_SHADE_* status of shaded records: exact where the record is final, +0 where it recurses or is invalid"""
+    bad = np.flatnonzero(status != want_status)
+    assert bad.size == 0, "%s: status differs for %d records, first %d: got %d want %d" % (what, bad.size, bad[0], status[bad[0]], want_status[bad[0]])
+    exact = (want_status == pkg.SHADE_BACKGROUND) | (want_status == pkg.SHADE_DIFFUSE)
+    assert_same_floats(rgb[exact], want[exact], what + ": colour")
+    zero = ~exact
+    assert np.all(rgb[zero].view(np.uint32) == 0), what + ": a record that recurses (or is invalid) is +0, 0, 0"
+
+
+def distances(n):
+    """per-ray occlusion limits of the ray-query tests"""
+    return np.random.default_rng(12).uniform(0.1, 12.0, n).astype(np.float32)
+
+
 def blob_to_scene(blob):
     """Parse a CRTS blob (oracle/scene_blob.h) back into the scene dict of scenes.py."""
     import struct

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import query_sets as qs
-from helpers import assert_same_floats, small_case
+from helpers import assert_same_floats, assert_same_hits, distances, small_case
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,15 +24,6 @@ def setup(pkg, scenes, oracle, name, tmp_path, tuning=None):
     scene, depth, folder = small_case(scenes, name, tmp_path)
     tracer = pkg.Tracer(pkg.Scene(json_text=scenes.to_json(scene), folder=folder), tuning=pkg.make_tuning(**tuning) if tuning else None)
     return scene, depth, tracer, oracle.OracleScene(scenes.to_blob(scene))
-
-
-def assert_same_hits(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape
-    for field in ("hit", "mesh", "triangle"):
-        bad = np.flatnonzero(got[field] != want[field])
-        assert bad.size == 0, "%s: %s differs for %d rays, first %d: got %r want %r" % (what, field, bad.size, bad[0], got[bad[0]], want[bad[0]])
-    for field in ("t", "point", "normal", "u", "v"):
-        assert_same_floats(got[field], want[field], "%s: %s" % (what, field))
 
 
 def check_closest(pkg, tracer, o, scene, rays, ray_type, what, rerouted):
@@ -61,10 +52,6 @@ def check_occluded(tracer, o, rays, dist, what, rerouted=None):
     if rerouted is not None:
         assert st.rerouted == rerouted, what
     return want
-
-
-def distances(n):
-    return np.random.default_rng(12).uniform(0.1, 12.0, n).astype(np.float32)
 
 
 # ---- 1. random rays: the filter path answers

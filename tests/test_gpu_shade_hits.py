@@ -9,7 +9,7 @@ import pytest
 
 import query_sets as qs
 import shade_sets as ss
-from helpers import assert_same_floats, small_case
+from helpers import assert_same_floats, assert_shaded, small_case
 
 pytestmark = pytest.mark.gpu
 _CASES = {}
@@ -36,15 +36,6 @@ def case(pkg, scenes, oracle, name, tmp_path_factory):
         hits.setflags(write=False)
         _CASES[name] = dict(scene=scene, depth=depth, folder=folder, tracer=tracer, oracle=o, rays=rays, hits=hits, status=status, want=want)
     return _CASES[name]
-
-
-def assert_shaded(pkg, rgb, status, want_status, want, what):
-    bad = np.flatnonzero(status != want_status)
-    assert bad.size == 0, "%s: status differs for %d records, first %d: got %d want %d" % (what, bad.size, bad[0], status[bad[0]], want_status[bad[0]])
-    exact = (want_status == pkg.SHADE_BACKGROUND) | (want_status == pkg.SHADE_DIFFUSE)
-    assert_same_floats(rgb[exact], want[exact], what + ": colour")
-    zero = ~exact
-    assert np.all(rgb[zero].view(np.uint32) == 0), what + ": a record that recurses (or is invalid) is +0, 0, 0"
 
 
 # ---- 1. random rays
