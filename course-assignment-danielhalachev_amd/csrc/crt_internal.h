@@ -69,6 +69,7 @@ struct crt_ctx {
     float4 *d_rayq[2] = {nullptr, nullptr};
     float4 *d_shadowq = nullptr;
     uint8_t *d_occluded = nullptr;
+    float *d_kfac = nullptr;          // the slots' light factors (same capacity)
     float4 *d_nodes = nullptr;
     uint32_t *d_scounts = nullptr;
     unsigned long long *d_exec = nullptr;           // executed-test tallies of a collect_counters == 2 render

@@ -124,7 +124,7 @@ static void adapt_queue_sizing(crt_ctx *ctx) {
 
 static uint64_t queue_bytes_for(const crt_ctx *ctx, uint64_t px, double node_mult, double ray_mult, double shadow_extra) {
     const uint64_t lights = ctx->n_lights ? ctx->n_lights : 1;
-    return (uint64_t)(px * std::max(ray_mult, 1.0)) * 16 + (uint64_t)(px * ray_mult) * (64 + 24) + (uint64_t)(px * lights * (1.0 + shadow_extra)) * 33 + (uint64_t)(px * node_mult) * 32;
+    return (uint64_t)(px * std::max(ray_mult, 1.0)) * 16 + (uint64_t)(px * ray_mult) * (64 + 24) + (uint64_t)(px * lights * (1.0 + shadow_extra)) * 37 + (uint64_t)(px * node_mult) * 32;
 }
 
 // After an attempt that overflowed (launch_render): capacities from what the attempt learnt.  The level that was emitting when a
@@ -184,7 +184,7 @@ static int ensure_stream(crt_ctx *ctx, uint32_t n_items) {
             ray_cap = std::max<uint64_t>(ray_cap, A.s_ray_cap);
             shadow_cap = std::max<uint64_t>(shadow_cap, A.s_shadow_cap);
         }
-        void **bufs[] = {(void **)&ctx->d_rayq[0], (void **)&ctx->d_rayq[1], (void **)&ctx->d_shadowq, (void **)&ctx->d_occluded,
+        void **bufs[] = {(void **)&ctx->d_rayq[0], (void **)&ctx->d_rayq[1], (void **)&ctx->d_shadowq, (void **)&ctx->d_occluded, (void **)&ctx->d_kfac,
                          (void **)&ctx->d_nodes, (void **)&ctx->d_heavy, (void **)&ctx->d_sheavy, (void **)&ctx->d_hits, (void **)&ctx->d_hits_all,
                          (void **)&ctx->d_lq};
         for (void **b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
@@ -194,6 +194,7 @@ static int ensure_stream(crt_ctx *ctx, uint32_t n_items) {
         for (int i = 0; i < 2; i++) CRT_HIP_CHECK(ctx, hipMalloc((void **)&ctx->d_rayq[i], ray_cap * 2 * sizeof(float4) + 64));
         CRT_HIP_CHECK(ctx, hipMalloc((void **)&ctx->d_shadowq, shadow_cap * 2 * sizeof(float4) + 64));
         CRT_HIP_CHECK(ctx, hipMalloc((void **)&ctx->d_occluded, shadow_cap));
+        CRT_HIP_CHECK(ctx, hipMalloc((void **)&ctx->d_kfac, shadow_cap * sizeof(float)));
         CRT_HIP_CHECK(ctx, hipMalloc((void **)&ctx->d_nodes, node_cap * 2 * sizeof(float4)));
         ctx->heavy_cap = (uint32_t)std::max<uint64_t>(floor_cap, ray_cap);  // (a full list only keeps a long walk where it is)
         CRT_HIP_CHECK(ctx, hipMalloc((void **)&ctx->d_heavy, (size_t)ctx->heavy_cap * sizeof(uint32_t) + 64));
@@ -207,10 +208,10 @@ static int ensure_stream(crt_ctx *ctx, uint32_t n_items) {
         }
         A.s_ray_cap = (uint32_t)ray_cap; A.s_shadow_cap = (uint32_t)shadow_cap; A.s_node_cap = (uint32_t)node_cap;
         ctx->stream_items = n_items;
-        ctx->queue_bytes = ray_cap * 64 + shadow_cap * 33 + node_cap * 32 + (size_t)ctx->heavy_cap * 24 + std::max<uint64_t>(ray_cap, px) * 16 + (ctx->d_lq ? node_cap * 64 : 0);
+        ctx->queue_bytes = ray_cap * 64 + shadow_cap * 37 + node_cap * 32 + (size_t)ctx->heavy_cap * 24 + std::max<uint64_t>(ray_cap, px) * 16 + (ctx->d_lq ? node_cap * 64 : 0);
     }
     A.s_rayq[0] = ctx->d_rayq[0]; A.s_rayq[1] = ctx->d_rayq[1];
-    A.s_shadowq = ctx->d_shadowq; A.s_occluded = ctx->d_occluded; A.s_nodes = ctx->d_nodes;
+    A.s_shadowq = ctx->d_shadowq; A.s_occluded = ctx->d_occluded; A.s_kfac = ctx->d_kfac; A.s_nodes = ctx->d_nodes;
     A.s_heavy = ctx->d_heavy; A.s_sheavy = ctx->d_sheavy; A.s_hits = ctx->d_hits; A.s_hits_all = ctx->d_hits_all; A.s_heavy_cap = ctx->heavy_cap;
     // (an explicit ray capacity -- crt_tuning, the tests' way to an overflow -- bounds the level queue too)
     A.s_lq = ctx->d_lq; A.s_lq_cap = ctx->d_lq ? (ctx->tuning.ray_cap ? std::min(A.s_ray_cap, A.s_node_cap) : A.s_node_cap) : 0u;

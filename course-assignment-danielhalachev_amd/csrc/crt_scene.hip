@@ -583,6 +583,7 @@ extern "C" void crt_destroy(crt_ctx *ctx) {
     for (int i = 0; i < 2; i++) if (ctx->d_rayq[i]) (void)hipFree(ctx->d_rayq[i]);
     if (ctx->d_shadowq) (void)hipFree(ctx->d_shadowq);
     if (ctx->d_occluded) (void)hipFree(ctx->d_occluded);
+    if (ctx->d_kfac) (void)hipFree(ctx->d_kfac);
     if (ctx->d_nodes) (void)hipFree(ctx->d_nodes);
     if (ctx->d_scounts) (void)hipFree(ctx->d_scounts);
     if (ctx->d_exec) (void)hipFree(ctx->d_exec);

@@ -4,6 +4,7 @@
 #include "glibc_powf.h"
 #include "glibc_sincosf.h"
 #include "gi_random.h"
+#include "shadow_place.h"
 
 namespace {
 // unit-test kernel: the device build of csrc/glibc_powf.h
@@ -116,5 +117,13 @@ extern "C" int crt_debug_set_query_chunks(crt_ctx *ctx, uint64_t host_rays, uint
     ctx->query_host_rays = chunk(host_rays, QUERY_HOST_RAYS);
     ctx->query_launch_rays = chunk(launch_rays, QUERY_LAUNCH_RAYS);
     ctx->shoot_pass_rays = chunk(pass_rays, SHOOT_PASS_RAYS);
+    return CRT_OK;
+}
+
+// Unit-test hook: level 0's fixed shadow slots (csrc/shadow_place.h) -- every slot of items x samples work items and n_lights lights through the
+// inverse placement and back through the forward one, on the host; *mismatches = the slots that do not come back.
+extern "C" int crt_test_shadow_place(uint32_t items, uint32_t samples, uint32_t n_lights, uint64_t *mismatches) {
+    if (!mismatches || !items || !samples || !n_lights || (uint64_t)items * samples * 64u * n_lights >= (1ull << 31)) return CRT_ERR_INVALID;
+    *mismatches = level0_slot_mismatches(items * samples, n_lights);
     return CRT_OK;
 }

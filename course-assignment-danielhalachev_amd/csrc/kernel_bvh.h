@@ -764,6 +764,7 @@ __device__ __forceinline__ void bvh_shadow_rays(const KernelArgs &A, const uint3
     if (A.f->s_counts[SC_OVERFLOW]) return;
     const BvhStack stack = bvh_stack_of(A, stack_lds, BVH_SPILL_SIDE);   // (the bulk pass runs beside the level kernels and the level queue's launch: a region of its own; pass 1 runs behind pass 0 and behind the levels)
     const bool every_mesh = A.f->use_gi != 0;
+    const uint32_t fixed_end = level0_fixed_slots(A);
     uint32_t nbox = 0, ntri = 0;
     Ray R;
     R.ox = R.oy = R.oz = R.dx = R.dy = R.dz = R.ix = R.iy = R.iz = 0; R.parmask = 0;
@@ -795,16 +796,22 @@ __device__ __forceinline__ void bvh_shadow_rays(const KernelArgs &A, const uint3
                 if (r >= total) state = BVH_OUT;
                 else {
                     r += first;
-                    const float4 q0 = A.f->s_shadowq[2 * (size_t)r], q1 = A.f->s_shadowq[2 * (size_t)r + 1];
-                    // an unused slot (a level-0 pixel without a diffuse hit) needs nothing.  A light behind the surface contributes +-0
-                    // times the albedo: no walk (kernel_plan.h has the argument)
-                    if (__float_as_uint(q0.w) == SHADOW_SLOT_UNUSED) {}
-                    else if (q1.w == 0.0f) A.f->s_occluded[r] = 0;
+                    float kfac;
+                    bool used;
+                    if (r < fixed_end) used = level0_shadow_ray(A, r, R, light_dist, kfac);   // a fixed slot: the ray from its pixel's record
                     else {
+                        const float4 q0 = A.f->s_shadowq[2 * (size_t)r], q1 = A.f->s_shadowq[2 * (size_t)r + 1];
+                        used = __float_as_uint(q0.w) != SHADOW_SLOT_UNUSED;
                         R.ox = q0.x; R.oy = q0.y; R.oz = q0.z;
                         R.dx = q1.x; R.dy = q1.y; R.dz = q1.z;  // already normalised once; shadow rays skip shootRay (RayTracer.cpp:313-317)
                         ray_prepare(R);
-                        light_dist = q0.w;
+                        light_dist = q0.w; kfac = q1.w;
+                    }
+                    // an unused slot (a level-0 pixel without a diffuse hit) needs nothing.  A light behind the surface contributes +-0
+                    // times the albedo: no walk (kernel_plan.h has the argument)
+                    if (!used) {}
+                    else if (kfac == 0.0f) A.f->s_occluded[r] = 0;
+                    else {
                         // an occluding hit has length(o + d t - o) <= light_dist with |d| = 1 up to two unit roundoffs: t <= light_dist (1 + 2^-16) (NaN: no bound)
                         bvh_walk_begin(W, light_dist * (1.0f + 0x1p-16f));
                         if (bvh_ray_setup(A, R, W.B)) state = BVH_WALK;

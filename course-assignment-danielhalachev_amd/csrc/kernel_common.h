@@ -157,8 +157,11 @@ struct FrameArgs {
     uint64_t frame_wave_stride;   // floats per wave
     // ray-stream buffers (kernel_stream.h)
     float4 *s_rayq[2];            // closest-hit ray queues of alternating recursion levels, 2 x float4 per ray
-    float4 *s_shadowq;            // shadow rays of all levels: {origin, light distance}, {direction, light factor}
+    float4 *s_shadowq;            // shadow rays of the levels below level 0: {origin, light distance}, {direction, light factor}, behind level 0's fixed slots' range; in the
+                                  // front of that range (fixed0) one record per level-0 ray instead: {hit point, marker} {normal, 0} (kernel_stream.h: level0_shadow_ray)
     uint8_t *s_occluded;          // one flag per shadow ray
+    float *s_kfac;                // ... and its light factor, by the same index (written by shade_hit beside a queued ray, by whoever walks a fixed slot): with the
+                                  // flag all that stream_resolve reads of a slot
     float4 *s_nodes;              // ray-tree nodes (TNode), 2 x float4 each
     uint32_t *s_counts;           // SC_WORDS counters / cursors, zeroed before every frame
     uint32_t s_ray_cap, s_shadow_cap, s_node_cap;

@@ -465,16 +465,21 @@ __device__ __forceinline__ void heavy_shadow_part(const KernelArgs &A, const uin
     TopRegs TR = heavy_top_load(A, lane);
     for (uint32_t k = first + wave; k < total; k += n_waves) {
         const uint32_t r = A.f->s_sheavy[k];
-        const float4 q0 = A.f->s_shadowq[2 * (size_t)r], q1 = A.f->s_shadowq[2 * (size_t)r + 1];
         Ray R;
-        R.ox = q0.x; R.oy = q0.y; R.oz = q0.z;
-        R.dx = q1.x; R.dy = q1.y; R.dz = q1.z;
-        ray_prepare(R);
+        float dist, kfac;
+        if (r < level0_fixed_slots(A)) (void)level0_shadow_ray(A, r, R, dist, kfac);   // (a fixed slot, evicted by a pass that found it used: the ray from its pixel's record, as there)
+        else {
+            const float4 q0 = A.f->s_shadowq[2 * (size_t)r], q1 = A.f->s_shadowq[2 * (size_t)r + 1];
+            R.ox = q0.x; R.oy = q0.y; R.oz = q0.z;
+            R.dx = q1.x; R.dy = q1.y; R.dz = q1.z;
+            ray_prepare(R);
+            dist = q0.w;
+        }
         R.parmask = __builtin_amdgcn_readfirstlane(R.parmask);
         bool have, occluded;
         float bt = 0;
         uint32_t btri = 0, bmesh = 0;
-        heavy_walk<true, EXEC>(A, TR, R, false, uniform_f(q0.w), have, bt, btri, bmesh, occluded, lane);
+        heavy_walk<true, EXEC>(A, TR, R, false, uniform_f(dist), have, bt, btri, bmesh, occluded, lane);
         if (lane == 0) A.f->s_occluded[r] = occluded ? 1 : 0;
     }
 }

@@ -92,22 +92,27 @@ __device__ __forceinline__ void shadow_plan_walks(const KernelArgs &A, const uin
                 r = wave_fetch(cursor, lane);
                 if (r >= total) { state = ST_DONE; break; }
                 r += first;
-                const float4 q0 = A.f->s_shadowq[2 * (size_t)r], q1 = A.f->s_shadowq[2 * (size_t)r + 1];
-                if (__float_as_uint(q0.w) == SHADOW_SLOT_UNUSED) continue;  // a level-0 pixel without a diffuse hit
+                float dist, kfac;
+                if (r < level0_fixed_slots(A)) {   // a fixed slot: the ray from its pixel's record
+                    if (!level0_shadow_ray(A, r, R, dist, kfac)) continue;  // a level-0 pixel without a diffuse hit
+                } else {
+                    const float4 q0 = A.f->s_shadowq[2 * (size_t)r], q1 = A.f->s_shadowq[2 * (size_t)r + 1];
+                    R.ox = q0.x; R.oy = q0.y; R.oz = q0.z;
+                    R.dx = q1.x; R.dy = q1.y; R.dz = q1.z;  // already normalised once; shadow rays skip shootRay (RayTracer.cpp:313-317)
+                    ray_prepare(R);
+                    dist = q0.w; kfac = q1.w;
+                }
                 // The light is behind the surface (angle = max(0, l . n) = 0, RayTracer.cpp:312): its contribution is
                 // intensity / area * 0 = +-0 times the albedo, and adding +-0 to the light sum -- which starts at +0 and can
                 // therefore never be -0 -- changes no bit of it (RayTracer.cpp:319-328).  Occluded or not, the pixel is the same:
                 // no walk.  (A NaN factor -- the light AT the surface -- is not zero and is walked.)
-                if (q1.w == 0.0f) { A.f->s_occluded[r] = 0; continue; }
-                R.ox = q0.x; R.oy = q0.y; R.oz = q0.z;
-                R.dx = q1.x; R.dy = q1.y; R.dz = q1.z;  // already normalised once; shadow rays skip shootRay (RayTracer.cpp:313-317)
-                ray_prepare(R);
+                if (kfac == 0.0f) { A.f->s_occluded[r] = 0; continue; }
                 if (R.parmask != 0) {  // BoundingBox.h:90-93 needs the general test: the wave-per-ray kernel has it
                     if (evict_ray(A.f->s_sheavy, A.f->s_heavy_cap, A.f->s_counts + SC_SHEAVY, r, lane)) continue;
                     A.f->s_counts[SC_OVERFLOW] = 1;
                     continue;
                 }
-                light_dist = q0.w;
+                light_dist = dist;
                 fresh = true;
                 steps = 0;
                 state = ST_TRAVERSE;

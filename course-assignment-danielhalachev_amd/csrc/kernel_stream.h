@@ -14,6 +14,16 @@
 //                                               combines the colours with the reference's own expressions, so
 //                                               every float is produced by the same operations in the same order.
 //
+// A shadow SLOT is three things under one index: its ray in s_shadowq (32 bytes: {origin, light distance} {direction, light factor},
+// what the shadow walks read), its flag in s_occluded (1 byte, what they write) and its light factor once more in s_kfac (4 bytes,
+// stored by shade_hit beside the ray).  stream_resolve reads the flag and, for a light that is not blocked, the factor: 5 bytes of a
+// slot.  Reading the factor out of the ray record brought every record's second half -- the whole queue, 265 MB of a 1080p frame --
+// through the fabric once more for one float in eight.
+// Level 0's slots are FIXED (level0_shadow_place) and hold no ray at all: level-0 ray r leaves one 32-byte record {hit point, marker} {normal, 0}
+// at s_shadowq[2 r], and whoever walks fixed slot s finds its ray and light (shadow_place.h: level0_slot_owner), rebuilds the ray with
+// light_setup -- the expressions shade_hit used to store the results of -- and stores the factor in s_kfac (level0_shadow_ray).  n_lights
+// rays of 32 bytes per pixel became one record: level 0 writes a quarter of what it did, the bulk pass reads 64 consecutive records per refill.
+//
 // All rays of a level are independent, so each launch has millions of rays of parallelism and no lane ever
 // waits for a recursion.  Queues, the ray tree and the flags live in HBM (a few hundred MB at 1080p).
 #pragma once
@@ -21,6 +31,7 @@
 #include "kernel_common.h"
 #include "kernel_lane.h"
 #include "kernel_walk.h"
+#include "shadow_place.h"
 
 struct TNode {          // one node of a pixel's ray tree, 32 bytes
     float cx, cy, cz;   // DIFFUSE: texture/albedo colour; REFLECT: albedo; after resolve of a REFRACT node: reflection colour
@@ -144,23 +155,33 @@ __device__ __forceinline__ bool evict_ray(uint32_t *list, uint32_t cap, uint32_t
 // together walk in one direction from neighbouring places (measured against tile-major, one tile's lights in turn: HW14 354 -> 367,
 // HW12 436 -> 473 Mpixels/s; blocks of 4 .. 240 tiles alike, the whole frame light by light 349 / 452).  Pixel r of light li owns slot
 // base + li * stride + (r & 63); the last block of a frame is as long as the items left.  A pixel without a diffuse hit marks its
-// slots unused (distance word all ones: no computed distance has that pattern).
+// record unused (marker word all ones), and so all its slots; nothing reads such a slot's flag or factor.
 constexpr uint32_t SHADOW_SLOT_UNUSED = 0xFFFFFFFFu;
-constexpr uint32_t LEVEL0_SHADOW_BLOCK = 16;
+// (the index arithmetic, forward and inverse: shadow_place.h)
 __device__ __forceinline__ void level0_shadow_place(const KernelArgs &A, uint32_t r, uint32_t &base, uint32_t &stride) {
-    const uint32_t item = r >> 6, total = A.f->n_items * A.f->level0_samples;
-    const uint32_t blk = item / LEVEL0_SHADOW_BLOCK, in = item - blk * LEVEL0_SHADOW_BLOCK;
-    const uint32_t left = total - blk * LEVEL0_SHADOW_BLOCK, nb = left < LEVEL0_SHADOW_BLOCK ? left : LEVEL0_SHADOW_BLOCK;
-    base = blk * LEVEL0_SHADOW_BLOCK * A.s->n_lights * 64u + in * 64u;
-    stride = nb * 64u;
+    level0_slot_place(A.f->n_items * A.f->level0_samples, A.s->n_lights, r, base, stride);
+}
+// The fixed slots hold no rays: level-0 ray r leaves ONE record, 32 bytes at s_shadowq[2 r]: {hit point, marker} {normal, 0} -- marker
+// SHADOW_SLOT_UNUSED for a ray without a diffuse hit or a pixel that is not covered -- in the front of the queue buffer (n_lights >= 1 times
+// smaller than the slots' range; the deeper levels' slots, beyond the fixed ones, keep their 32-byte rays).  Whoever walks fixed slot `slot`
+// rebuilds its ray from the record of the slot's pixel and the slot's light with light_setup, the expressions shade_hit would have used, and
+// stores the slot's light factor in s_kfac.  64 consecutive slots are 64 consecutive records.
+__device__ __forceinline__ uint32_t level0_fixed_slots(const KernelArgs &A) {   // slots below this are fixed ones
+    return A.f->fixed0 ? A.f->n_items * A.f->level0_samples * 64u * A.s->n_lights : 0u;
 }
 __device__ __forceinline__ void level0_release_shadow_slots(const KernelArgs &A, uint32_t r) {
-    if (!A.f->fixed0) return;
-    uint32_t base, stride;
-    level0_shadow_place(A, r, base, stride);
-    const size_t first = (size_t)base + (r & 63u);
-    for (uint32_t li = 0; li < A.s->n_lights; li++)
-        A.f->s_shadowq[2 * (first + (size_t)li * stride)] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(SHADOW_SLOT_UNUSED));
+    if (!A.f->fixed0 || !A.s->n_lights) return;   // (no lights: no slots, and nobody to read a record)
+    A.f->s_shadowq[2 * (size_t)r] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(SHADOW_SLOT_UNUSED));
+}
+// false: the slot is unused.  (The record and the light are loaded before either is looked at; an unused record's ray is computed and dropped.)
+__device__ __forceinline__ bool level0_shadow_ray(const KernelArgs &A, const uint32_t slot, Ray &R, float &dist, float &kfac) {
+    uint32_t r, li;
+    level0_slot_owner(A.f->n_items * A.f->level0_samples, A.s->n_lights, slot, r, li);
+    const float4 p = A.f->s_shadowq[2 * (size_t)r], n = A.f->s_shadowq[2 * (size_t)r + 1];
+    light_setup(A, li, p.x, p.y, p.z, n.x, n.y, n.z, R, dist, kfac);
+    if (__float_as_uint(p.w) == SHADOW_SLOT_UNUSED) return false;
+    A.f->s_kfac[slot] = kfac;
+    return true;
 }
 
 // shootRay's dispatch on the closest hit (RayTracer.cpp:431-450), in two steps.  shade_hit: everything but the child
@@ -225,7 +246,13 @@ __device__ __forceinline__ void shade_hit(const KernelArgs &A, const uint32_t ge
                     E.hpx = S.px; E.hpy = S.py; E.hpz = S.pz; E.hnx = S.nx; E.hny = S.ny; E.hnz = S.nz;
                 }
                 if (out_diffuse) { *out_diffuse = true; *out_first = N.a; *out_stride = cntd; }
-                for (uint32_t li = 0; li < A.s->n_lights; li++) {
+                if (gen == 0 && A.f->fixed0) {   // one record for all lights (level0_shadow_ray)
+                    if (COUNT) { cnt[C_LIGHT] += A.s->n_lights; cnt[C_SHADOW] += A.s->n_lights; }
+                    if (A.s->n_lights) {
+                        A.f->s_shadowq[2 * (size_t)r] = make_float4(S.px, S.py, S.pz, 0.0f);
+                        A.f->s_shadowq[2 * (size_t)r + 1] = make_float4(S.nx, S.ny, S.nz, 0.0f);
+                    }
+                } else for (uint32_t li = 0; li < A.s->n_lights; li++) {
                     Ray SR;
                     float dist, kfac;
                     light_setup(A, li, S.px, S.py, S.pz, S.nx, S.ny, S.nz, SR, dist, kfac);
@@ -233,6 +260,7 @@ __device__ __forceinline__ void shade_hit(const KernelArgs &A, const uint32_t ge
                     const size_t slot = (size_t)base + (size_t)li * cntd + rank;
                     A.f->s_shadowq[2 * slot] = make_float4(SR.ox, SR.oy, SR.oz, dist);
                     A.f->s_shadowq[2 * slot + 1] = make_float4(SR.dx, SR.dy, SR.dz, kfac);
+                    A.f->s_kfac[slot] = kfac;   // (resolve_leaf reads this copy, never the ray)
                 }
             }
         } else if (S.M.type == CRT_MAT_REFLECTIVE || S.M.type == CRT_MAT_REFRACTIVE) {
@@ -569,6 +597,7 @@ __global__ __launch_bounds__(BLOCK) void stream_trace_shadow(const KernelArgs A,
     const uint32_t split = A.f->s_counts[SC_SHADOW_SPLIT];
     const uint32_t first = pass == 0 ? 0u : split;
     const uint32_t total = pass == 0 ? split : A.f->s_counts[SC_SHADOW] - split;
+    const uint32_t fixed_end = level0_fixed_slots(A);
     uint32_t *cursor = A.f->s_counts + (pass == 0 ? SC_SHADOW_FETCH : SC_SHADOW_FETCH2);
     uint32_t cnt[C_N];
     if (COUNT) for (int k = 0; k < C_N; k++) cnt[k] = 0;
@@ -584,14 +613,21 @@ __global__ __launch_bounds__(BLOCK) void stream_trace_shadow(const KernelArgs A,
                 if (r >= total) state = ST_DONE;
                 else {
                     r += first;
-                    const float4 q0 = A.f->s_shadowq[2 * (size_t)r], q1 = A.f->s_shadowq[2 * (size_t)r + 1];
-                    if (__float_as_uint(q0.w) != SHADOW_SLOT_UNUSED) {  // (unused: the lane fetches again next trip)
+                    float dist, kfac;
+                    bool used;
+                    if (r < fixed_end) used = level0_shadow_ray(A, r, R, dist, kfac);
+                    else {
+                        const float4 q0 = A.f->s_shadowq[2 * (size_t)r], q1 = A.f->s_shadowq[2 * (size_t)r + 1];
+                        used = __float_as_uint(q0.w) != SHADOW_SLOT_UNUSED;
                         R.ox = q0.x; R.oy = q0.y; R.oz = q0.z;
                         R.dx = q1.x; R.dy = q1.y; R.dz = q1.z;  // already normalised once; shadow rays skip shootRay (RayTracer.cpp:313-317)
                         ray_prepare(R);
+                        dist = q0.w;
+                    }
+                    if (used) {  // (unused: the lane fetches again next trip)
                         L.rtype = RAY_SHADOW;
                         traversal_begin(L, A.s->top_root);
-                        L.light_dist = q0.w;
+                        L.light_dist = dist;
                         state = ST_TRAVERSE;
                     }
                 }
@@ -644,7 +680,7 @@ __device__ __forceinline__ void resolve_leaf(const KernelArgs &A, const float4 &
         for (uint32_t li = 0; li < A.s->n_lights; li++) {
             const size_t slot = (size_t)first + (size_t)li * stride;
             if (!A.f->s_occluded[slot]) {
-                const float k = A.f->s_shadowq[2 * slot + 1].w;
+                const float k = A.f->s_kfac[slot];
                 if (COUNT && (kind & TN_BITMAP)) cnt[C_TEXEL]++;
                 ax += k * n0.x; ay += k * n0.y; az += k * n0.z;
             }
