@@ -173,7 +173,7 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_st
                   "crt_render_async", "crt_wait", "crt_alloc_pinned", "crt_free_pinned",
                   "crt_trace_rays", "crt_trace_rays_device", "crt_occluded_rays", "crt_occluded_rays_device", "crt_camera_rays_device",
                   "crt_get_query_stats", "crt_shade_hits", "crt_shade_hits_device", "crt_light_points", "crt_light_points_device",
-                  "crt_shoot_rays", "crt_shoot_rays_device", "crt_get_shoot_stats",
+                  "crt_shoot_rays", "crt_shoot_rays_device", "crt_get_shoot_stats", "crt_shoot_rays_gi", "crt_shoot_rays_gi_device",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -232,6 +232,8 @@ def lib():
     L.crt_shoot_rays.argtypes = [vp, vp, C.c_uint64, u32, C.POINTER(Options), vp]
     L.crt_shoot_rays_device.argtypes = [vp, vp, C.c_uint64, u32, C.POINTER(Options), vp, vp]
     L.crt_get_shoot_stats.argtypes = [vp, C.POINTER(ShootStats)]
+    L.crt_shoot_rays_gi.argtypes = [vp, vp, vp, C.c_uint64, u32, C.POINTER(Options), vp]
+    L.crt_shoot_rays_gi_device.argtypes = [vp, vp, vp, C.c_uint64, u32, C.POINTER(Options), vp, vp]
     L.crt_host_shoot_stats_layout.argtypes = [C.POINTER(u32), u32]
     L.crt_host_shoot_stats_layout.restype = u32
     L.crt_get_kernel_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -665,6 +667,39 @@ class Tracer:
         o = make_options(max_depth, shadow_bias, reflection_bias, refraction_bias)
         self._check(lib().crt_shoot_rays_device(self.ctx, C.c_void_p(d_rays_ptr), n, ray_type, C.byref(o), C.c_void_p(d_rgb_ptr),
                                                 C.c_void_p(stream_ptr or 0)))
+
+    # ---- radiance queries in the GI mode (include/crt_hip.h: crt_shoot_rays_gi*)
+    @staticmethod
+    def _gi_options(options, option_fields):
+        """`options` (an Options with use_gi set) or make_options(use_gi=True, **option_fields): one of the two"""
+        if options is not None:
+            if option_fields:
+                raise TypeError("shoot_rays_gi: pass either options or option fields, not both (%s)" % ", ".join(sorted(option_fields)))
+            return options
+        return make_options(**dict(option_fields, use_gi=True))
+
+    def shoot_rays_gi(self, rays, keys=None, ray_type=RAY_REFLECTION, options=None, **option_fields):
+        """The colour shootRay of the GI build returns for each ray: rays float32 [n, 6], keys uint32 [n] (the key of each ray's shootRay
+        invocation, csrc/gi_random.h) or None for the keys of a frame's pixels 0 .. n - 1, sample 0, under options.gi_seed -> float32
+        [n, 3].  options: an Options with use_gi set, or make_options' fields by name (max_depth, gi_sample_size, gi_seed, ...)."""
+        self._single("shoot_rays_gi")
+        rays = self._rays_array(rays)
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, dtype=np.uint32)
+            if keys.shape != (len(rays),):
+                raise ValueError("keys: expected shape [%d], got %r" % (len(rays), keys.shape))
+        rgb = np.zeros((len(rays), 3), dtype=np.float32)
+        o = self._gi_options(options, option_fields)
+        self._check(lib().crt_shoot_rays_gi(self.ctx, _p(rays), _p(keys) if keys is not None else None, len(rays), ray_type, C.byref(o), _p(rgb)))
+        return rgb
+
+    def shoot_rays_gi_device(self, d_rays_ptr, n, d_rgb_ptr, d_keys_ptr=None, ray_type=RAY_REFLECTION, options=None, stream_ptr=None, **option_fields):
+        """The same on device memory (data_ptr() of: rays float32 [n, 6], rgb float32 [n, 3], keys uint32 [n] or None) on the stream; the
+        call waits for the stream once per recursion level, so it cannot be captured into a graph."""
+        self._single("shoot_rays_gi_device")
+        o = self._gi_options(options, option_fields)
+        self._check(lib().crt_shoot_rays_gi_device(self.ctx, C.c_void_p(d_rays_ptr), C.c_void_p(d_keys_ptr or 0), n, ray_type, C.byref(o),
+                                                   C.c_void_p(d_rgb_ptr), C.c_void_p(stream_ptr or 0)))
 
     def shoot_stats(self) -> ShootStats:
         """rays / levels / level_rays / shadow_records / rerouted / kernel_ms of the last radiance query (waits for it)."""

@@ -6,11 +6,13 @@
 //                      records and points; kernels: csrc/kernel_shade.h
 //   radiance queries   crt_shoot_rays*: RayTracer::shootRay (RayTracer.cpp:419-451), a host loop over the launches of the other two, one
 //                      recursion level behind the other, with three small kernels of its own around them (csrc/kernel_radiance.h): at
-//                      the end of this file
+//                      the end of this file; crt_shoot_rays_gi*: the same loop for the GI build (a key per ray, sample rays at DIFFUSE
+//                      records, no mesh skipped by a shadow ray)
 // and their statistics (crt_get_query_stats, crt_get_shoot_stats).  A query reads the context's scene and nothing of its frames: the
 // scratch below is the queries' own.
 #include "crt_internal.h"
 #include "glibc_powf.h"
+#include "gi_random.h"
 
 namespace {
 
@@ -28,6 +30,9 @@ namespace {
 // radiance queries: what a level may hold at most (a level is at most twice as wide as the one above it; indices and counts stay
 // inside 31 bits)
 constexpr uint64_t SHOOT_LEVEL_RAYS = 1ull << 30;
+// ... and in the GI mode, where a level is up to max(2, gi_sample_size) times as wide as the one above it: what the DEEPEST level of one
+// pass may hold in the worst case (every ray of every level a DIFFUSE hit); about 8 GB of level arrays.  A call's pass size follows it.
+constexpr uint64_t SHOOT_GI_DEEPEST_RAYS = 1ull << 26;
 // the radiance queries' own words (uint32 offsets): rays appended to level g at [g], the call's DIFFUSE records (64-bit) behind them
 enum : int { SW_COUNT = 0, SW_DIFFUSE = MAX_GENERATIONS + 2, SW_WORDS = MAX_GENERATIONS + 4 };
 // ... and what comes back through pinned memory (uint64 slots): a level's count, level 0's hits, the DIFFUSE records, the rerouted ones
@@ -64,6 +69,7 @@ struct ShootLevel {
     DeviceArray<float> rgb;        // 3 a ray
     DeviceArray<uint8_t> status;
     DeviceArray<float4> nodes;     // 2 a ray
+    DeviceArray<uint32_t> keys;    // crt_shoot_rays_gi*: the key of each ray's shootRay invocation (gi_random.h)
 };
 
 // One call of the ray or lighting queries: which filter / reroute kernel pair answers it, and the arrays of its n rays or records (the
@@ -82,6 +88,7 @@ struct QueryCall {
     uint8_t *status;              // Q_SHADE_HITS, or null
     uint32_t ray_type;
     float shadow_bias;
+    bool every_mesh;              // Q_SHADE_HITS: the GI build's occlusion rule (the levels of crt_shoot_rays_gi*)
 };
 QueryCall closest_call(const crt_ray *rays, uint64_t n, uint32_t ray_type, crt_hit *hits) {
     QueryCall c{};
@@ -93,9 +100,9 @@ QueryCall occluded_call(const crt_ray *rays, const float *max_distance, uint64_t
     c.kind = Q_OCCLUDED; c.n = n; c.rays = rays; c.max_distance = max_distance; c.ray_type = CRT_RAY_SHADOW; c.occluded = occluded;
     return c;
 }
-QueryCall shade_call(const crt_hit *records, uint64_t n, float shadow_bias, float *rgb, uint8_t *status) {
+QueryCall shade_call(const crt_hit *records, uint64_t n, float shadow_bias, float *rgb, uint8_t *status, bool every_mesh = false) {
     QueryCall c{};
-    c.kind = Q_SHADE_HITS; c.n = n; c.records = records; c.shadow_bias = shadow_bias; c.out = rgb; c.status = status;
+    c.kind = Q_SHADE_HITS; c.n = n; c.records = records; c.shadow_bias = shadow_bias; c.out = rgb; c.status = status; c.every_mesh = every_mesh;
     return c;
 }
 QueryCall points_call(const float *points, const float *normals, uint64_t n, float shadow_bias, float *sums) {
@@ -134,7 +141,8 @@ struct OpenCall {
 }  // namespace
 
 struct crt_query_state {
-    DeviceArray<FrameArgs> frame;     // an all-zero frame block: the reference-order walk reads use_gi (0: shadow rays skip refractive meshes)
+    DeviceArray<FrameArgs> frame;     // two frame blocks, all zero but for use_gi = 1 in the second: the reference-order walk reads use_gi
+                                      // (0: shadow rays skip refractive meshes; 1, the levels of crt_shoot_rays_gi*: they skip none)
     DeviceArray<uint32_t> words;      // QW_*
     uint32_t *h_words = nullptr;      // pinned: the words of the last call, copied behind its last launch
     DeviceArray<uint32_t> list;       // reroute list: follows the largest launch asked for
@@ -153,6 +161,7 @@ struct crt_query_state {
     // radiance queries (crt_shoot_rays*)
     ShootLevel lv[MAX_GENERATIONS];
     DeviceArray<crt_ray> shoot_in;    // the host variant's device copy of the caller's rays
+    DeviceArray<uint32_t> shoot_keys; // ... and of the caller's keys (crt_shoot_rays_gi)
     DeviceArray<uint32_t> swords;     // SW_*
     uint64_t *h_shoot = nullptr;      // pinned, SH_*
     crt_shoot_stats shoot{};          // of the last radiance call
@@ -211,8 +220,10 @@ static int query_begin(crt_ctx *ctx, hipStream_t stream, bool radiance) {
     if (!q) { ctx->error = "out of memory"; return CRT_ERR_NOMEM; }
     if (!q->h_words) {
         int rc;
-        if ((rc = q->frame.reserve(ctx, 1)) || (rc = q->words.reserve(ctx, QW_WORDS))) return rc;
-        CRT_HIP_CHECK(ctx, hipMemset(q->frame.p, 0, sizeof(FrameArgs)));
+        if ((rc = q->frame.reserve(ctx, 2)) || (rc = q->words.reserve(ctx, QW_WORDS))) return rc;
+        CRT_HIP_CHECK(ctx, hipMemset(q->frame.p, 0, 2 * sizeof(FrameArgs)));
+        const uint32_t one = 1u;
+        CRT_HIP_CHECK(ctx, hipMemcpy(&q->frame.p[1].use_gi, &one, sizeof(one), hipMemcpyHostToDevice));
         // one region: every filter launch of a query (query_walk / query_direct, the levels of crt_shoot_rays* among them) has at most
         // grid_blocks workgroups and follows the previous one on ONE stream (a call on another stream, and a pending frame, are waited
         // for first): no two of them run side by side
@@ -249,7 +260,7 @@ static int query_launches(crt_ctx *ctx, const QueryCall &C, hipStream_t stream, 
     crt_query_state *q = ctx->query;
     KernelArgs A{};
     A.s = (scene_args_p)ctx->d_scene;
-    A.f = (frame_args_p)q->frame.p;   // all zero (use_gi = 0: shadow rays skip refractive meshes); the bias travels in ShadeArgs
+    A.f = (frame_args_p)(q->frame.p + (C.every_mesh ? 1 : 0));   // all zero but for use_gi (0: shadow rays skip refractive meshes); the bias travels in ShadeArgs
     const bool filter = uses_filter(ctx);
     for (uint64_t done = 0; done < C.n; done += ctx->query_launch_rays) {
         const QueryCall c = call_part(C, done, std::min(C.n - done, ctx->query_launch_rays));
@@ -269,7 +280,10 @@ static int query_launches(crt_ctx *ctx, const QueryCall &C, hipStream_t stream, 
         switch (c.kind) {
             case Q_CLOSEST: e = launch_pair(query_walk<BVH_PLAIN, false>, query_reroute<false>, filter, blocks, stream, A, Q); break;
             case Q_OCCLUDED: e = launch_pair(query_walk<BVH_PLAIN, true>, query_reroute<true>, filter, blocks, stream, A, Q); break;
-            case Q_SHADE_HITS: e = launch_pair(query_direct<BVH_PLAIN, false>, query_direct_reroute<false>, filter, blocks, stream, A, S); break;
+            case Q_SHADE_HITS:
+                e = c.every_mesh ? launch_pair(query_direct<BVH_PLAIN, false, true>, query_direct_reroute<false>, filter, blocks, stream, A, S)
+                                 : launch_pair(query_direct<BVH_PLAIN, false>, query_direct_reroute<false>, filter, blocks, stream, A, S);
+                break;
             case Q_LIGHT_POINTS: e = launch_pair(query_direct<BVH_PLAIN, true>, query_direct_reroute<true>, filter, blocks, stream, A, S); break;
         }
         CRT_HIP_CHECK(ctx, e);
@@ -457,22 +471,48 @@ extern "C" int crt_get_query_stats(crt_ctx *ctx, crt_query_stats *out) {
 // max_depth: trace the level's rays and light their records (query_launches, twice: background, constant and diffuse records are
 // final), radiance_scatter the recursing ones into level g + 1, read that level's size back -- the one wait of a level --; then
 // radiance_combine from the deepest level up.  Level 0's colours are the caller's array.
+// crt_shoot_rays_gi*: the same loop with the kernels' GI builds.  A level has a key array beside its rays; the lighting launches skip no
+// mesh; a DIFFUSE record is not final but spawns gi_sample_size rays, so level g + 1 holds up to max(2, gi_sample_size) rays for each
+// of level g.
 
-// room for `cap` rays at level g (`own_rgb`: with colours of its own; level 0 writes the caller's array)
-static int shoot_level_reserve(crt_ctx *ctx, const uint32_t g, const uint64_t cap, const bool own_rgb) {
+// what a GI call adds to a pass's arguments (null: a plain call)
+struct ShootGi {
+    const uint32_t *d_keys;   // the pass's keys on the device, or null: those of a frame's pixels key_first ..., sample 0
+    uint32_t key_first;       // the index in the call of the pass's first ray
+};
+
+// rays of level g + 1 for each ray of level g, at most
+static uint64_t shoot_fan(const crt_options *o, const bool gi) { return gi ? std::max(2u, o->gi_sample_size) : 2u; }
+
+// GI: the rays of one pass -- as many as keep the worst-case deepest level (every hit of every level DIFFUSE) at SHOOT_GI_DEEPEST_RAYS,
+// between 64 and shoot_pass_rays; 0 when 64 rays do not fit.  *product: max(2, gi_sample_size)^max_depth (saturated above the bound).
+static uint64_t shoot_gi_pass_rays(const crt_ctx *ctx, const crt_options *o, uint64_t *product) {
+    const uint64_t fan = shoot_fan(o, true);   // (<= 64: the product below stays under 2^33)
+    uint64_t p = 1;
+    for (uint32_t d = 0; d < o->max_depth && p <= SHOOT_GI_DEEPEST_RAYS; d++) p *= fan;
+    *product = p;
+    if (64u * p > SHOOT_GI_DEEPEST_RAYS) return 0;
+    return std::min(std::max<uint64_t>(SHOOT_GI_DEEPEST_RAYS / p, 64u), ctx->shoot_pass_rays);
+}
+
+// room for `cap` rays at level g (`own_rgb`: with colours of its own; level 0 writes the caller's array; `keys`: a GI call)
+static int shoot_level_reserve(crt_ctx *ctx, const uint32_t g, const uint64_t cap, const bool own_rgb, const bool keys) {
     ShootLevel &L = ctx->query->lv[g];
     int rc;
     if ((rc = L.rays.reserve(ctx, cap)) || (rc = L.hits.reserve(ctx, cap)) || (rc = L.status.reserve(ctx, cap)) || (rc = L.nodes.reserve(ctx, 2 * cap))) return rc;
+    if (keys && (rc = L.keys.reserve(ctx, cap))) return rc;
     return own_rgb ? L.rgb.reserve(ctx, 3 * cap) : CRT_OK;
 }
 
-// one pass: m <= shoot_pass_rays rays of the caller's, every level of them; leaves the pass's numbers on their way to h_shoot
+// one pass: m rays of the caller's (at most shoot_pass_rays, or what shoot_gi_pass_rays allows), every level of them; leaves the pass's
+// numbers on their way to h_shoot
 static int shoot_pass(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t m, const uint32_t ray_type, const crt_options *o, float *d_rgb,
-                      hipStream_t stream) {
+                      hipStream_t stream, const ShootGi *gi) {
     crt_query_state *q = ctx->query;
     KernelArgs A{};
     A.s = (scene_args_p)ctx->d_scene;
     A.f = (frame_args_p)q->frame.p;
+    const uint64_t fan = shoot_fan(o, gi != nullptr);
     CRT_HIP_CHECK(ctx, hipMemsetAsync(q->words.p, 0, QW_WORDS * sizeof(uint32_t), stream));
     CRT_HIP_CHECK(ctx, hipMemsetAsync(q->swords.p, 0, SW_WORDS * sizeof(uint32_t), stream));
     uint32_t count[MAX_GENERATIONS + 1] = {m};
@@ -481,7 +521,7 @@ static int shoot_pass(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t m, con
         const uint32_t n = count[g];
         last = g;
         int rc;
-        if ((rc = query_list_reserve(ctx, n)) || (rc = shoot_level_reserve(ctx, g, n, g > 0))) return rc;   // (the list follows the widest level)
+        if ((rc = query_list_reserve(ctx, n)) || (rc = shoot_level_reserve(ctx, g, n, g > 0, gi != nullptr))) return rc;   // (the list follows the widest level)
         const ShootLevel &L = q->lv[g];
         float *rgb = g == 0 ? d_rgb : L.rgb.p;
         const uint32_t blocks = (uint32_t)(((uint64_t)n + BLOCK - 1) / BLOCK);
@@ -489,34 +529,42 @@ static int shoot_pass(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t m, con
         G.in_rays = d_rays; G.rays = L.rays.p; G.hits = L.hits.p; G.status = L.status.p; G.rgb = rgb; G.nodes = L.nodes.p; G.n = n;
         G.diffuse_total = reinterpret_cast<unsigned long long *>(q->swords.p + SW_DIFFUSE);
         G.reflection_bias = o->reflection_bias; G.refraction_bias = o->refraction_bias;
+        if (gi) {
+            G.in_keys = gi->d_keys; G.keys = L.keys.p; G.gi_samples = o->gi_sample_size; G.gi_seed = o->gi_seed; G.key_first = gi->key_first;
+            G.monte_carlo_bias = o->monte_carlo_bias;
+        }
         if (g == 0) {
-            hipLaunchKernelGGL(radiance_prepare, dim3(blocks), dim3(BLOCK), 0, stream, G);
+            if (gi) hipLaunchKernelGGL(radiance_prepare<true>, dim3(blocks), dim3(BLOCK), 0, stream, G);
+            else hipLaunchKernelGGL(radiance_prepare<false>, dim3(blocks), dim3(BLOCK), 0, stream, G);
             CRT_HIP_CHECK(ctx, hipGetLastError());
         }
         // children are REFLECTION or REFRACTION rays, which walk alike: only the caller's own ray can be PRIMARY (Ray.cpp:13)
         rc = query_launches(ctx, closest_call(L.rays.p, n, g == 0 ? ray_type : (uint32_t)CRT_RAY_REFLECTION, L.hits.p), stream, g == 0);
         if (rc) return rc;
         if (g == 0) CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_shoot + SH_HITS0, q->words.p + QW_HITS, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        rc = query_launches(ctx, shade_call(L.hits.p, n, o->shadow_bias, rgb, L.status.p), stream, false);
+        rc = query_launches(ctx, shade_call(L.hits.p, n, o->shadow_bias, rgb, L.status.p, gi != nullptr), stream, false);
         if (rc) return rc;
-        // the next level holds at most two rays for each of this one: room for that BEFORE the launch that fills it
+        // the next level holds at most `fan` rays for each of this one: room for that BEFORE the launch that fills it
         const bool spawn = g + 1 <= o->max_depth;   // a child enters shootRay with depth g + 1 (RayTracer.cpp:427)
         if (spawn) {
-            if (2ull * n > SHOOT_LEVEL_RAYS) { ctx->error = "crt_shoot_rays: a recursion level wider than 2^30 rays"; return CRT_ERR_NOMEM; }
-            rc = shoot_level_reserve(ctx, g + 1, 2ull * n, true);
+            if (fan * n > SHOOT_LEVEL_RAYS) { ctx->error = "crt_shoot_rays: a recursion level wider than 2^30 rays"; return CRT_ERR_NOMEM; }
+            rc = shoot_level_reserve(ctx, g + 1, fan * n, true, gi != nullptr);
             if (rc) return rc;
             G.child_rays = q->lv[g + 1].rays.p;
+            G.child_keys = q->lv[g + 1].keys.p;
             G.child_cap = (uint32_t)std::min<uint64_t>(q->lv[g + 1].rays.cap, SHOOT_LEVEL_RAYS);
+            if (gi) G.child_cap = (uint32_t)std::min<uint64_t>(G.child_cap, q->lv[g + 1].keys.cap);
         }
         G.child_count = q->swords.p + SW_COUNT + g + 1;
         G.spawn = spawn ? 1u : 0u;
-        hipLaunchKernelGGL(radiance_scatter, dim3(blocks), dim3(BLOCK), 0, stream, A, G);
+        if (gi) hipLaunchKernelGGL(radiance_scatter<true>, dim3(blocks), dim3(BLOCK), 0, stream, A, G);
+        else hipLaunchKernelGGL(radiance_scatter<false>, dim3(blocks), dim3(BLOCK), 0, stream, A, G);
         CRT_HIP_CHECK(ctx, hipGetLastError());
         if (!spawn) break;
         // the one wait of a level: four bytes through pinned memory, to size the next one
         CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_shoot + SH_COUNT, G.child_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));
-        count[g + 1] = (uint32_t)std::min<uint64_t>(*reinterpret_cast<const uint32_t *>(q->h_shoot + SH_COUNT), 2ull * n);
+        count[g + 1] = (uint32_t)std::min<uint64_t>(*reinterpret_cast<const uint32_t *>(q->h_shoot + SH_COUNT), fan * n);
         if (count[g + 1] == 0) break;
     }
     for (uint32_t g = 0; g <= last; g++) q->shoot.level_rays[g] += count[g];
@@ -528,7 +576,10 @@ static int shoot_pass(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t m, con
         G.status = L.status.p; G.nodes = L.nodes.p; G.rgb = g == 0 ? d_rgb : L.rgb.p; G.n = count[g];
         G.child_rgb = g < last ? q->lv[g + 1].rgb.p : nullptr;
         G.child_n = g < last ? count[g + 1] : 0u;
-        hipLaunchKernelGGL(radiance_combine, dim3((uint32_t)(((uint64_t)count[g] + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, A, G);
+        G.gi_samples = gi ? o->gi_sample_size : 0u;
+        const dim3 grid((uint32_t)(((uint64_t)count[g] + BLOCK - 1) / BLOCK));
+        if (gi) hipLaunchKernelGGL(radiance_combine<true>, grid, dim3(BLOCK), 0, stream, A, G);
+        else hipLaunchKernelGGL(radiance_combine<false>, grid, dim3(BLOCK), 0, stream, A, G);
         CRT_HIP_CHECK(ctx, hipGetLastError());
     }
     CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_shoot + SH_DIFFUSE, q->swords.p + SW_DIFFUSE, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
@@ -550,7 +601,36 @@ static int shoot_check(crt_ctx *ctx, const void *rays, const crt_options *option
     return CRT_OK;
 }
 
-static int shoot_run(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *d_rgb, hipStream_t stream) {
+// crt_shoot_rays_gi*: the arguments, and *pass = the rays of one pass
+static int shoot_gi_check(crt_ctx *ctx, const void *rays, const crt_options *options, const void *out, uint32_t ray_type, const char *what, uint64_t *pass) {
+    if (!rays || !options || !out) { ctx->error = std::string(what) + ": NULL array or options with n > 0"; return CRT_ERR_INVALID; }
+    if (ray_type > (uint32_t)CRT_RAY_REFRACTION) { ctx->error = std::string(what) + ": unknown ray_type " + std::to_string(ray_type); return CRT_ERR_INVALID; }
+    if (!options->use_gi) {
+        ctx->error = std::string(what) + ": use_gi is 0: the deterministic build's colours are crt_shoot_rays' (crt_shoot_rays_device's)";
+        return CRT_ERR_INVALID;
+    }
+    if (options->gi_sample_size > 64u) {   // (a frame's rule: crt_launch.hip)
+        ctx->error = std::string(what) + ": gi_sample_size too large: " + std::to_string(options->gi_sample_size) + ", at most 64";
+        return CRT_ERR_INVALID;
+    }
+    if ((uint64_t)options->max_depth + 1 > (uint64_t)MAX_GENERATIONS) {
+        ctx->error = std::string(what) + ": max_depth too large: " + std::to_string(options->max_depth) + " + 1 levels, at most " + std::to_string(MAX_GENERATIONS);
+        return CRT_ERR_INVALID;
+    }
+    uint64_t product = 0;
+    *pass = shoot_gi_pass_rays(ctx, options, &product);
+    if (*pass == 0) {
+        ctx->error = std::string(what) + ": the deepest level of a pass of 64 rays may hold 64 x max(2, gi_sample_size)^max_depth = 64 x " +
+                     std::to_string(shoot_fan(options, true)) + "^" + std::to_string(options->max_depth) +
+                     (product > SHOOT_GI_DEEPEST_RAYS ? " > 64 x 2^26" : " = " + std::to_string(64u * product)) + " rays, more than 2^26";
+        return CRT_ERR_INVALID;
+    }
+    return CRT_OK;
+}
+
+// one device call: n rays, `pass` at a time
+static int shoot_run(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *d_rgb, hipStream_t stream,
+                     const uint64_t pass, const ShootGi *gi) {
     int rc = query_begin(ctx, stream, true);
     if (rc) return rc;
     crt_query_state *q = ctx->query;
@@ -564,12 +644,14 @@ static int shoot_run(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t r
     q->shoot = crt_shoot_stats{};
     q->shoot.rays = n;
     CRT_HIP_CHECK(ctx, hipEventRecord(q->call.ev0, stream));
-    for (uint64_t done = 0; done < n; done += ctx->shoot_pass_rays) {
+    for (uint64_t done = 0; done < n; done += pass) {
         if (done) {   // the previous pass's numbers leave the pinned slots before this pass writes them
             CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));
             shoot_fold(q);
         }
-        rc = shoot_pass(ctx, d_rays + done, (uint32_t)std::min(n - done, ctx->shoot_pass_rays), ray_type, options, d_rgb + 3 * done, stream);
+        ShootGi part{};
+        if (gi) { part.d_keys = gi->d_keys ? gi->d_keys + done : nullptr; part.key_first = gi->key_first + (uint32_t)done; }
+        rc = shoot_pass(ctx, d_rays + done, (uint32_t)std::min(n - done, pass), ray_type, options, d_rgb + 3 * done, stream, gi ? &part : nullptr);
         if (rc) return rc;
     }
     CRT_HIP_CHECK(ctx, hipEventRecord(q->call.ev1, stream));
@@ -579,32 +661,23 @@ static int shoot_run(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t r
     return CRT_OK;
 }
 
-extern "C" int crt_shoot_rays_device(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *d_rgb,
-                                     void *stream) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
-    int rc = shoot_check(ctx, d_rays, options, d_rgb, ray_type, "crt_shoot_rays_device");
-    if (rc) return rc;
-    return shoot_run(ctx, d_rays, n, ray_type, options, d_rgb, (hipStream_t)stream);
-}
-
-// the host variant: copy in, run, copy out, shoot_pass_rays at a time; the colours' device copy is level 0's own colour array
-extern "C" int crt_shoot_rays(crt_ctx *ctx, const crt_ray *rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *out_rgb) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
-    int rc = shoot_check(ctx, rays, options, out_rgb, ray_type, "crt_shoot_rays");
-    if (rc) return rc;
-    const uint64_t m = std::min(n, ctx->shoot_pass_rays);
-    rc = query_begin(ctx, ctx->stream, true);
+// the host variants: copy in, run, copy out, `pass` rays at a time; the colours' device copy is level 0's own colour array
+static int shoot_host(crt_ctx *ctx, const crt_ray *rays, const uint32_t *keys, uint64_t n, uint32_t ray_type, const crt_options *options, float *out_rgb,
+                      const uint64_t pass, const bool gi) {
+    const uint64_t m = std::min(n, pass);
+    int rc = query_begin(ctx, ctx->stream, true);
     if (rc) return rc;
     crt_query_state *q = ctx->query;
-    if ((rc = shoot_level_reserve(ctx, 0, m, true)) || (rc = q->shoot_in.reserve(ctx, m))) return rc;
+    if ((rc = shoot_level_reserve(ctx, 0, m, true, gi)) || (rc = q->shoot_in.reserve(ctx, m))) return rc;
+    if (keys && (rc = q->shoot_keys.reserve(ctx, m))) return rc;
     crt_shoot_stats total{};
     crt_query_stats qtotal{};
-    for (uint64_t done = 0; done < n; done += ctx->shoot_pass_rays) {
-        const uint64_t k = std::min(n - done, ctx->shoot_pass_rays);
+    for (uint64_t done = 0; done < n; done += pass) {
+        const uint64_t k = std::min(n - done, pass);
         CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->shoot_in.p, rays + done, k * sizeof(crt_ray), hipMemcpyHostToDevice, ctx->stream));
-        rc = shoot_run(ctx, q->shoot_in.p, k, ray_type, options, q->lv[0].rgb.p, ctx->stream);
+        if (keys) CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->shoot_keys.p, keys + done, k * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        const ShootGi part{keys ? q->shoot_keys.p : nullptr, (uint32_t)done};
+        rc = shoot_run(ctx, q->shoot_in.p, k, ray_type, options, q->lv[0].rgb.p, ctx->stream, pass, gi ? &part : nullptr);
         if (rc) return rc;
         CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb + 3 * done, q->lv[0].rgb.p, k * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
         CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -619,6 +692,44 @@ extern "C" int crt_shoot_rays(crt_ctx *ctx, const crt_ray *rays, uint64_t n, uin
     q->shoot = total;
     q->stats = qtotal;
     return CRT_OK;
+}
+
+extern "C" int crt_shoot_rays_device(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *d_rgb,
+                                     void *stream) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    int rc = shoot_check(ctx, d_rays, options, d_rgb, ray_type, "crt_shoot_rays_device");
+    if (rc) return rc;
+    return shoot_run(ctx, d_rays, n, ray_type, options, d_rgb, (hipStream_t)stream, ctx->shoot_pass_rays, nullptr);
+}
+
+extern "C" int crt_shoot_rays(crt_ctx *ctx, const crt_ray *rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *out_rgb) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    int rc = shoot_check(ctx, rays, options, out_rgb, ray_type, "crt_shoot_rays");
+    if (rc) return rc;
+    return shoot_host(ctx, rays, nullptr, n, ray_type, options, out_rgb, ctx->shoot_pass_rays, false);
+}
+
+extern "C" int crt_shoot_rays_gi_device(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t *d_keys, uint64_t n, uint32_t ray_type,
+                                        const crt_options *options, float *d_rgb, void *stream) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    uint64_t pass = 0;
+    int rc = shoot_gi_check(ctx, d_rays, options, d_rgb, ray_type, "crt_shoot_rays_gi_device", &pass);
+    if (rc) return rc;
+    const ShootGi gi{d_keys, 0u};
+    return shoot_run(ctx, d_rays, n, ray_type, options, d_rgb, (hipStream_t)stream, pass, &gi);
+}
+
+extern "C" int crt_shoot_rays_gi(crt_ctx *ctx, const crt_ray *rays, const uint32_t *keys, uint64_t n, uint32_t ray_type, const crt_options *options,
+                                 float *out_rgb) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    uint64_t pass = 0;
+    int rc = shoot_gi_check(ctx, rays, options, out_rgb, ray_type, "crt_shoot_rays_gi", &pass);
+    if (rc) return rc;
+    return shoot_host(ctx, rays, keys, n, ray_type, options, out_rgb, pass, true);
 }
 
 extern "C" int crt_get_shoot_stats(crt_ctx *ctx, crt_shoot_stats *out) {

@@ -12,6 +12,12 @@
 // Every level has arrays of its own (rays, records, colours, status, nodes): a parent holds its children's indices in the next level's
 // arrays, so the ORDER in which a level's children are appended may differ between two runs and no colour does.  Nothing of a frame is
 // used: no FrameArgs queue, no level queue, no ray tree of a pixel.
+//
+// GI = true: the builds of crt_shoot_rays_gi*, the reference's GI mode (RayTracer.cpp:331-354; oracle/cpu_ref.c: shoot_ray with use_gi)
+// with the generator of gi_random.h.  Every ray of a level has a KEY beside it (the key of its shootRay invocation); a DIFFUSE record
+// is a node too -- its gi_samples sample rays are gi_samples CONSECUTIVE rays of level g + 1, the first one's index in the node -- and
+// the up-sweep folds it as stream_resolve does: (direct + (((0 + c_0) + c_1) + ...)) * (1 / (gi_samples + 1)).  The plain builds carry
+// none of this (as kernel_stream.h's kernels do with their GI parameter).
 #pragma once
 
 #include "kernel_stream.h"
@@ -33,22 +39,37 @@ struct RadianceArgs {
     uint32_t child_n;                   // radiance_combine: rays of level g + 1
     uint32_t spawn;                     // g + 1 <= max_depth: children are traced (else CHILD_BG: background without tracing, RayTracer.cpp:427-429)
     float reflection_bias, refraction_bias;
+    // the GI builds alone (crt_shoot_rays_gi*)
+    const uint32_t *in_keys;            // radiance_prepare<true>: the caller's keys, or null: mix(mix(gi_seed, key_first + r), 0)
+    uint32_t *keys;                     // this level's keys, one a ray
+    uint32_t *child_keys;               // level g + 1's
+    uint32_t gi_samples;                // GI_SAMPLE_SIZE
+    uint32_t gi_seed, key_first;        // in_keys == null: the seed, and the index in the CALL of this pass's first ray
+    float monte_carlo_bias;
 };
 
-// shootRay's entry (RayTracer.cpp:420) for the caller's rays: normalize3 leaves a zero direction as it is
+// shootRay's entry (RayTracer.cpp:420) for the caller's rays: normalize3 leaves a zero direction as it is.  GI: and the rays' keys --
+// the caller's, or those of a frame's pixels key_first + r, sample 0 (kernel_stream.h: level0_key).
+template <bool GI>
 __global__ __launch_bounds__(BLOCK) void radiance_prepare(const RadianceArgs G) {
     const uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (r >= G.n) return;
     crt_ray q = G.in_rays[r];
     normalize3(q.direction[0], q.direction[1], q.direction[2]);
     G.rays[r] = q;
+    if constexpr (GI) G.keys[r] = G.in_keys ? G.in_keys[r] : crt_gi_mix(crt_gi_mix(G.gi_seed, G.key_first + (uint32_t)r), 0u);
 }
 
 // shootRay's dispatch for a mirror or glass hit (RayTracer.cpp:437-442) up to the recursive calls: the node and the child rays.  The
 // arithmetic is shade_hit's (kernel_stream.h), in one body for both: mirror_glass_children (kernel_common.h).  A child is stored the
 // way the next level walks it: normalised once more, which is the child's own shootRay entry (stream_trace_shade does that when it
 // fetches a queued ray).  The children of a wave are appended with ONE atomic (kernel_query.h: query_append's pattern): the
-// reflection rays of its lanes first, then the transmission rays.
+// reflection rays of its lanes first, then the transmission rays, then -- GI -- gi_samples consecutive rays for each DIFFUSE lane.
+// GI: a DIFFUSE record's sample rays (RayTracer.cpp:333-350; the expressions of shade_and_emit<.., true>, kernel_stream.h): sample i
+// leaves point + normal * monte_carlo_bias in gi_sample_direction(incoming direction, normal, u(key, 2 + 2i), u(key, 3 + 2i)) with key
+// child_key(key, 2 + i); the mirror and glass children get child_key(key, 0) and (key, 1).  The record's node holds the first sample's
+// index (CHILD_BG: nothing is traced -- no samples, or they would enter shootRay beyond max_depth).
+template <bool GI>
 __global__ __launch_bounds__(BLOCK) void radiance_scatter(const KernelArgs A, const RadianceArgs G) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;   // (every lane stays to the end: the ballots are the wave's)
@@ -56,6 +77,10 @@ __global__ __launch_bounds__(BLOCK) void radiance_scatter(const KernelArgs A, co
     const unsigned long long diffuse = __ballot(r < G.n && status == (uint32_t)CRT_SHADE_DIFFUSE);
     if (lane == 0 && diffuse) atomicAdd(G.diffuse_total, (unsigned long long)__popcll(diffuse));
     const bool recurses = r < G.n && status == (uint32_t)CRT_SHADE_RECURSES;
+    const bool gi_record = GI && r < G.n && status == (uint32_t)CRT_SHADE_DIFFUSE;
+    const bool samples = gi_record && G.spawn != 0u && G.gi_samples > 0u;
+    uint32_t key = 0;
+    if constexpr (GI) if (recurses || samples) key = G.keys[r];
     TNode N;
     N.cx = N.cy = N.cz = 0; N.kind = TN_CONST; N.a = 0; N.b = 0; N.f = 0; N.pad = 0;
     bool reflect = false, transmit = false;
@@ -81,11 +106,12 @@ __global__ __launch_bounds__(BLOCK) void radiance_scatter(const KernelArgs A, co
     }
     const unsigned long long m1 = __ballot(reflect), m2 = __ballot(transmit);
     const unsigned long long below = (1ull << lane) - 1ull;
-    const uint32_t n1 = (uint32_t)__popcll(m1), n2 = (uint32_t)__popcll(m2);
+    const unsigned long long m3 = GI ? __ballot(samples) : 0ull;
+    const uint32_t n1 = (uint32_t)__popcll(m1), n2 = (uint32_t)__popcll(m2), n3 = GI ? (uint32_t)__popcll(m3) * G.gi_samples : 0u;
     uint32_t base = 0;
-    if (m1) {   // (wave-uniform)
-        const uint32_t first = (uint32_t)(__ffsll((long long)m1) - 1);
-        if (lane == first) base = atomicAdd(G.child_count, n1 + n2);
+    if (m1 | m3) {   // (wave-uniform)
+        const uint32_t first = (uint32_t)(__ffsll((long long)(m1 | m3)) - 1);
+        if (lane == first) base = atomicAdd(G.child_count, n1 + n2 + n3);
         base = __shfl(base, first);
     }
     if (reflect) {
@@ -95,6 +121,7 @@ __global__ __launch_bounds__(BLOCK) void radiance_scatter(const KernelArgs A, co
             normalize3(rdx, rdy, rdz);   // the child's shootRay entry (RayTracer.cpp:420)
             c.origin[0] = rox; c.origin[1] = roy; c.origin[2] = roz; c.direction[0] = rdx; c.direction[1] = rdy; c.direction[2] = rdz;
             G.child_rays[i1] = c;
+            if constexpr (GI) G.child_keys[i1] = crt_gi_child_key(key, 0u);
             N.a = i1;
         }
         if (transmit) {
@@ -104,8 +131,34 @@ __global__ __launch_bounds__(BLOCK) void radiance_scatter(const KernelArgs A, co
                 normalize3(tdx, tdy, tdz);
                 c.origin[0] = tox; c.origin[1] = toy; c.origin[2] = toz; c.direction[0] = tdx; c.direction[1] = tdy; c.direction[2] = tdz;
                 G.child_rays[i2] = c;
+                if constexpr (GI) G.child_keys[i2] = crt_gi_child_key(key, 1u);
                 N.b = i2;
             }
+        }
+    }
+    if constexpr (GI) {
+        if (gi_record) {
+            N.a = CHILD_BG;
+            // (64-bit: the block's end is compared with the capacity before anything of it is written)
+            const uint64_t i3 = (uint64_t)base + n1 + n2 + (uint64_t)__popcll(m3 & below) * G.gi_samples;
+            if (samples && i3 + G.gi_samples <= (uint64_t)G.child_cap) {
+                const crt_ray q = G.rays[r];
+                const crt_hit h = G.hits[r];
+                const float ox = h.point[0] + h.normal[0] * G.monte_carlo_bias, oy = h.point[1] + h.normal[1] * G.monte_carlo_bias,
+                            oz = h.point[2] + h.normal[2] * G.monte_carlo_bias;
+                for (uint32_t i = 0; i < G.gi_samples; i++) {
+                    float dx, dy, dz;
+                    gi_sample_direction(q.direction[0], q.direction[1], q.direction[2], h.normal[0], h.normal[1], h.normal[2],
+                                        crt_gi_uniform(key, 2u + 2u * i), crt_gi_uniform(key, 3u + 2u * i), dx, dy, dz);
+                    normalize3(dx, dy, dz);   // the child's shootRay entry
+                    crt_ray c;
+                    c.origin[0] = ox; c.origin[1] = oy; c.origin[2] = oz; c.direction[0] = dx; c.direction[1] = dy; c.direction[2] = dz;
+                    G.child_rays[i3 + i] = c;
+                    G.child_keys[i3 + i] = crt_gi_child_key(key, 2u + i);
+                }
+                N.a = (uint32_t)i3;
+            }
+            G.nodes[2 * r + 1] = make_float4(__uint_as_float(N.a), 0.0f, 0.0f, 0.0f);   // (a DIFFUSE record's node is this word alone)
         }
     }
     if (recurses) {
@@ -122,10 +175,28 @@ __device__ __forceinline__ void radiance_child(const KernelArgs &A, const Radian
 
 // What calculateReflection / calculateRefraction return once their recursive calls have (RayTracer.cpp:368-372, 414-416): the
 // expressions of stream_resolve (kernel_stream.h), a lane per recursing record of the level.  Level g + 1's colours are final when
-// this runs for level g.
+// this runs for level g.  GI: and what calculateDiffusion returns once its sample rays have (RayTracer.cpp:349-353): the record's
+// colour is its direct light until then; the samples' colours are added in sample order to an indirect sum that starts at 0, a sample
+// that was not traced is the background, and no samples at all is (direct + 0) * (1 / 1).
+template <bool GI>
 __global__ __launch_bounds__(BLOCK) void radiance_combine(const KernelArgs A, const RadianceArgs G) {
     const uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (r >= G.n || G.status[r] != (uint8_t)CRT_SHADE_RECURSES) return;
+    if (r >= G.n) return;
+    if constexpr (GI) {
+        if (G.status[r] == (uint8_t)CRT_SHADE_DIFFUSE) {
+            const uint32_t first = __float_as_uint(G.nodes[2 * r + 1].x);
+            const float gi_inv = 1.0f / (float)(G.gi_samples + 1u);
+            float ix = 0.0f, iy = 0.0f, iz = 0.0f;
+            for (uint32_t i = 0; i < G.gi_samples; i++) {
+                float cx, cy, cz;
+                radiance_child(A, G, first == CHILD_BG ? CHILD_BG : first + i, cx, cy, cz);
+                ix = ix + cx; iy = iy + cy; iz = iz + cz;
+            }
+            G.rgb[3 * r] = (G.rgb[3 * r] + ix) * gi_inv; G.rgb[3 * r + 1] = (G.rgb[3 * r + 1] + iy) * gi_inv; G.rgb[3 * r + 2] = (G.rgb[3 * r + 2] + iz) * gi_inv;
+            return;
+        }
+    }
+    if (G.status[r] != (uint8_t)CRT_SHADE_RECURSES) return;
     const float4 n0 = G.nodes[2 * r], n1 = G.nodes[2 * r + 1];
     const uint32_t kind = __float_as_uint(n0.w) & TN_KIND_MASK;
     float cx, cy, cz;

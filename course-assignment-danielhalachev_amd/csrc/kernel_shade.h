@@ -66,7 +66,9 @@ __device__ __forceinline__ void shade_store(const KernelArgs &A, const ShadeArgs
 
 // query_walk<.., true>'s state machine with a light index inside the lane: BVH_FETCH (wants a record), BVH_SHADOWS (between two lights:
 // sets up the next shadow ray, or is through), BVH_WALK, BVH_FINISHED (its record is to be stored or listed), BVH_OUT.
-template <int MODE, bool POINTS>
+// EVERY: the GI build's occlusion rule -- no mesh is skipped (AccelerationStructure.cpp:67-71) -- as a build of its own, for the levels
+// of crt_shoot_rays_gi*: the plain build is what it was, instruction for instruction.
+template <int MODE, bool POINTS, bool EVERY = false>
 __global__ __launch_bounds__(BLOCK) void query_direct(const KernelArgs A, const ShadeArgs S) {
     __shared__ uint32_t stack_lds[BVH_LDS_STACK * BLOCK];
     const uint32_t lane = threadIdx.x & 63u;
@@ -129,7 +131,7 @@ __global__ __launch_bounds__(BLOCK) void query_direct(const KernelArgs A, const 
         }
         if (state == BVH_WALK) {
             for (int it = 0; it < BVH_STEPS; ++it)
-                if (state == BVH_WALK && !bvh_step<1, MODE>(A, R, false, light_dist, false, W, stack, nbox, ntri)) {
+                if (state == BVH_WALK && !bvh_step<1, MODE>(A, R, false, light_dist, EVERY, W, stack, nbox, ntri)) {
                     if (W.give_up) { reroute = true; state = BVH_FINISHED; }
                     else {
                         if (!W.have) {   // RayTracer.cpp:319-328: color = color + k * base
@@ -147,7 +149,8 @@ __global__ __launch_bounds__(BLOCK) void query_direct(const KernelArgs A, const 
 
 // The records query_direct listed (or, `direct`, every record of the launch: a scene without a filter, crt_tuning::bvh == 0), a lane per
 // record, every light of it walked in the reference's order as render_lanes walks a diffuse hit's shadow rays (kernel_lane.h:
-// traversal_begin / traversal_step<false>, rtype SHADOW).  The grid is sized for the worst case; a workgroup without a record leaves.
+// traversal_begin / traversal_step<false>, rtype SHADOW; that walk reads the occlusion rule from the frame block, A.f->use_gi: the
+// queries have an all-zero block and one with use_gi = 1).  The grid is sized for the worst case; a workgroup without a record leaves.
 template <bool POINTS>
 __global__ __launch_bounds__(BLOCK) void query_direct_reroute(const KernelArgs A, const ShadeArgs S) {
     const QueryArgs &Q = S.q;

@@ -256,6 +256,26 @@ std::vector<float> RayTracer::shootRays(const std::vector<crt_ray> &rays, const 
   return rgb;
 }
 
+std::vector<float> RayTracer::shootRaysGI(const std::vector<crt_ray> &rays, const std::vector<uint32_t> &keys, const RenderOptions &ro, unsigned int rayType,
+                                          crt_shoot_stats *stats) {
+  if (multi) throw std::runtime_error("shootRaysGI: not available on a multi-device tracer");
+  if (!keys.empty() && keys.size() != rays.size()) throw std::runtime_error("shootRaysGI: one key per ray, or none");
+  std::vector<float> rgb(rays.size() * 3);
+  crt_options options{};
+  options.max_depth = ro.MAX_DEPTH;
+  options.shadow_bias = ro.SHADOW_BIAS;
+  options.reflection_bias = ro.REFLECTION_BIAS;
+  options.refraction_bias = ro.REFRACTION_BIAS;
+  options.use_gi = ro.USE_GI ? 1u : 0u;
+  options.gi_sample_size = ro.GI_SAMPLE_SIZE;
+  options.monte_carlo_bias = ro.MONTE_CARLO_BIAS;
+  options.gi_seed = giSeed;
+  if (crt_shoot_rays_gi(ctx, rays.data(), keys.empty() ? nullptr : keys.data(), rays.size(), rayType, &options, rgb.data()) != CRT_OK)
+    throw std::runtime_error(std::string("shootRaysGI failed: ") + crt_last_error(ctx));
+  if (stats && crt_get_shoot_stats(ctx, stats) != CRT_OK) throw std::runtime_error(std::string("shootRaysGI failed: ") + crt_last_error(ctx));
+  return rgb;
+}
+
 crt_query_stats RayTracer::queryStats() const {
   crt_query_stats s{};
   if (!multi) crt_get_query_stats(ctx, &s);

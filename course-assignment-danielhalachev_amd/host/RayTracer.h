@@ -111,6 +111,11 @@ class RayTracer {
   // three biases from renderOptions (USE_GI is refused) --, 3 floats per ray; *stats: the call's crt_shoot_stats when it is given
   std::vector<float> shootRays(const std::vector<crt_ray> &rays, const RenderOptions &renderOptions, unsigned int rayType = CRT_RAY_REFLECTION,
                                crt_shoot_stats *stats = nullptr);
+  // ... and in the GI mode (crt_hip.h: crt_shoot_rays_gi): shootRay of the GI build with the generator of csrc/gi_random.h; keys: one
+  // per ray, or empty for the keys of a frame's pixels 0 .. n - 1, sample 0, under the tracer's seed (setGISeed).  MAX_DEPTH,
+  // GI_SAMPLE_SIZE and the four biases come from renderOptions; USE_GI must be set, RAYS_PER_PIXEL is not read
+  std::vector<float> shootRaysGI(const std::vector<crt_ray> &rays, const std::vector<uint32_t> &keys, const RenderOptions &renderOptions,
+                                 unsigned int rayType = CRT_RAY_REFLECTION, crt_shoot_stats *stats = nullptr);
 
   // flat access for callers that do not want the vector-of-vectors copy
   int renderFlat(const std::string &pathToImage, const RenderOptions &renderOptions, float *outRGB, unsigned int counters = 0);

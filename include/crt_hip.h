@@ -296,7 +296,7 @@ int crt_device_count(void);
  * crt_occluded_rays* returns checkForIntersection(ray, max_distance[i]) of the non-GI build for a shadow ray
  *   (AccelerationStructure.cpp:56-94): refractive meshes are skipped (:67-71), a mesh occludes when its closest hit lies within
  *   length(point - origin) <= max_distance (:73-74).  max_distance may be +inf.  (The GI build's rule -- no mesh is skipped -- is not
- *   offered.)
+ *   offered.)  The radiance queries of the GI mode, crt_shoot_rays_gi* below, light their records by that rule.
  * Directions are used AS GIVEN, like the reference's Ray holds them (Ray.h): nothing is normalised (RayTracer::getRay and shootRay
  *   normalise before they build a Ray, RayTracer.cpp:78,420, and so do callers who want that).  The candidate filter's error analysis
  *   (csrc/kernel_bvh.h) takes |d| = 1 up to rounding, so a ray with | dx^2 + dy^2 + dz^2 - 1 | > 2^-20 (evaluated in float32; every
@@ -352,7 +352,7 @@ int crt_get_query_stats(crt_ctx *ctx, crt_query_stats *out);
  *                         the scene's counts before anything is read through them; whether the triangle BELONGS to the mesh is not
  *                         checked (in-range indices are safe to read; the colour is then that mix's).
  *   Of `options` only shadow_bias is read; use_gi != 0 is CRT_ERR_INVALID (the GI build's occlusion rule -- no mesh skipped -- and its
- *   division by GI_SAMPLE_SIZE + 1 are not offered).
+ *   division by GI_SAMPLE_SIZE + 1 are not offered).  A GI record's whole colour is crt_shoot_rays_gi*'s, below.
  * crt_light_points* returns out[i] = the sum, in light order, of the unoccluded lights' factors intensity / (4 r^2 pi) * max(0, l . n) at
  *   points[i] with normals[i] (3 floats each): calculateDiffusion's result for a white (1, 1, 1) untextured diffuse surface, channel
  *   for channel.
@@ -382,7 +382,8 @@ int crt_light_points_device(crt_ctx *ctx, const float *d_points, const float *d_
  *   (CRT_RAY_PRIMARY culls back faces); its children are REFLECTION and REFRACTION rays, as in the reference.  A frame is the special
  *   case of crt_camera_rays_device's rays as CRT_RAY_PRIMARY: getRay's normalisation followed by shootRay's is the frame's ray.
  * Of `options` max_depth, shadow_bias, reflection_bias and refraction_bias are read.  use_gi != 0, max_depth + 1 > 64 (a frame's rule),
- *   an unknown ray_type, a NULL array or NULL options with n > 0 are CRT_ERR_INVALID; n == 0 is CRT_OK and touches nothing.
+ *   an unknown ray_type, a NULL array or NULL options with n > 0 are CRT_ERR_INVALID; n == 0 is CRT_OK and touches nothing.  The GI
+ *   mode's colours are crt_shoot_rays_gi*'s, below.
  * The evaluation is LEVEL-SYNCHRONOUS: for recursion level g = 0 .. max_depth the level's rays are traced (crt_trace_rays*' kernels) and
  *   lit (crt_shade_hits*' kernels), the mirror and glass hits' child rays become level g + 1, and when no level is left the colours are
  *   mixed from the deepest level up.  Every level has arrays of its own in the context's scratch, which grows and is kept: a call
@@ -409,6 +410,43 @@ int crt_shoot_rays_device(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint3
                           void *stream);
 /* statistics of the last radiance call; waits for it */
 int crt_get_shoot_stats(crt_ctx *ctx, crt_shoot_stats *out);
+
+/* ---- Radiance queries in the GI / multi-sample mode (crt_options::use_gi) -- light probes and irradiance volumes, lightmap texels with
+ * bounce light, a fisheye, panoramic or stereo camera in the GI mode, re-shooting a GI frame's changed pixels.  Kernels: the GI builds of
+ * csrc/kernel_radiance.h.  Single-device contexts only.
+ *
+ * out_rgb[3 i ..] is what shootRay(Ray{origin, direction, ray_type}, depth = 0) of the GI build returns (RayTracer.cpp:419-451, 300-356),
+ *   with the counter-based generator of csrc/gi_random.h in place of the reference's clock-seeded one, the invocation's key being keys[i]:
+ *   a key is a ray's place in a ray tree.  keys == NULL means keys[i] = crt_gi_mix(crt_gi_mix(options->gi_seed, (uint32_t)i), 0), the key
+ *   of a frame's pixel i, sample 0: the camera's rays (crt_camera_rays_device) shot as CRT_RAY_PRIMARY are then the GI frame of that seed
+ *   with rays_per_pixel = 1, up to the frame's `0 + colour` (a -0 channel is +0 there).  A colour is a function of (scene, ray, key,
+ *   options) alone: not of n, of the ray's position in the array, of how the call is split into passes, or of the device.
+ * What the GI build changes (the rest is crt_shoot_rays*'s arithmetic):
+ *   * shadow rays skip no mesh (AccelerationStructure.cpp:67-71);
+ *   * a DIFFUSE hit, after its direct light, shoots gi_sample_size rays from point + normal * monte_carlo_bias, sample i in the direction
+ *     the reference forms from the incoming direction, the normal and the key's numbers u(key, 2 + 2 i), u(key, 3 + 2 i) (RayTracer.cpp:
+ *     333-347), as a REFLECTION ray with key crt_gi_child_key(key, 2 + i) entering shootRay at depth + 1, and returns
+ *     (direct + (((0 + c_0) + c_1) + ...)) * (1 / (float)(gi_sample_size + 1)); a sample that would enter beyond max_depth is the
+ *     background, added without tracing; no samples: (direct + 0) * (1 / 1);
+ *   * a mirror's or glass hit's children carry the keys crt_gi_child_key(key, 0) and (key, 1).
+ * Of `options` max_depth, shadow_bias, reflection_bias, refraction_bias, monte_carlo_bias and gi_sample_size are read, gi_seed when keys
+ *   is NULL.  rays_per_pixel is NOT read: averaging a pixel's samples is the caller's -- as the reference does it (RayTracer.cpp:90-104;
+ *   oracle/cpu_ref.c: render_pixel): sample s of pixel p has the key crt_gi_mix(crt_gi_mix(seed, p), s), the sum starts at 0 and takes the
+ *   samples in order from 0, times 1 / (float)n.
+ * CRT_ERR_INVALID: use_gi == 0 (those colours are crt_shoot_rays*'s), gi_sample_size > 64 (a frame's rule), max_depth + 1 > 64, an unknown
+ *   ray_type, NULL rays, options or output with n > 0 -- and a call whose levels could not be held: level g + 1 is up to
+ *   max(2, gi_sample_size) times as wide as level g, so a call is evaluated in passes of
+ *   clamp(2^26 / max(2, gi_sample_size)^max_depth, 64, 2^22) rays, which keeps the deepest level of a pass at 2^26 rays in the worst case
+ *   (about 8 GB of level arrays; what a scene needs is allocated, not the worst case); when not even 64 rays fit, the call is refused
+ *   before anything runs.  n == 0 is CRT_OK and touches nothing.
+ * Everything else is crt_shoot_rays*'s contract, above: the direction normalised on entry, the level-synchronous evaluation (a DIFFUSE
+ *   record is a node here too, its samples gi_sample_size consecutive rays of the next level), host and device variants, streams, the
+ *   pending frame, what is left alone, the device variant's ONE WAIT PER LEVEL and pass -- it cannot be captured into a hipGraph --,
+ *   crt_get_shoot_stats (level_rays, shadow_records, rerouted, kernel_ms) and crt_get_query_stats. */
+int crt_shoot_rays_gi(crt_ctx *ctx, const crt_ray *rays, const uint32_t *keys, uint64_t n, uint32_t ray_type,
+                      const crt_options *options, float *out_rgb);
+int crt_shoot_rays_gi_device(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t *d_keys, uint64_t n, uint32_t ray_type,
+                             const crt_options *options, float *d_rgb, void *stream);
 
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
