@@ -54,6 +54,7 @@ struct crt_ctx {
     FrameArgs frame{};                // host copy of the NEXT frame's block (camera, queues ...)
     SceneArgs *d_scene = nullptr;
     FrameArgs *d_frame_ring = nullptr, *h_frame_ring = nullptr;  // one slot per launch in flight (EV_RING): device, and the pinned source of its copy
+    const FrameArgs *h_frame_ring_dev = nullptr;                 // ... as the device addresses it (stream_frame_reset does the copy)
     std::vector<void *> allocs;
     float *d_frame = nullptr;
     uint8_t *d_quant = nullptr;
@@ -63,7 +64,7 @@ struct crt_ctx {
     bool cached_is_partition = false;     // ... or crt_render_tiles_device's {first, stride} (held in cached_rects[0].row / .col)
     uint32_t cached_n_items = 0;
     uint64_t cached_pixels = 0;
-    uint32_t *d_sync = nullptr;      // [0] render_lanes' pixel counter
+    uint32_t *d_sync = nullptr;      // [0] render_lanes' pixel counter (zeroed by the frame's reset launch)
     uint64_t level_counters[C_N] = {}, shadow0_counters[C_N] = {};  // of the last counted render: recursion levels, bulk shadow pass
     enum Mode { MODE_STREAM, MODE_LANES } mode = MODE_STREAM;  // crt_tuning::mode (both produce identical pixels)
     float4 *d_rayq[2] = {nullptr, nullptr};
@@ -74,7 +75,7 @@ struct crt_ctx {
     uint32_t *d_scounts = nullptr;
     unsigned long long *d_exec = nullptr;           // executed-test tallies of a collect_counters == 2 render
     unsigned long long exec_counters[6] = {0, 0, 0, 0, 0, 0};  // {box, tri} x {all but shadow pass 0, shadow pass 0}, plan tests x the same
-    uint32_t *d_fallback_total = nullptr;  // frames redone by the queue-less kernel since crt_create
+    uint32_t *d_fallback_total = nullptr;  // frames redone by the queue-less kernel since crt_create: d_scounts + SC_FALLBACK_TOTAL
     uint32_t *d_heavy = nullptr;      // evicted ray ids
     uint32_t *d_sheavy = nullptr;     // evicted shadow ray ids
     float4 *d_hits = nullptr;         // their closest hits
@@ -89,9 +90,9 @@ struct crt_ctx {
     hipStream_t early = nullptr;      // the level queue's launch starts WITH level 0 on this one (crt_launch.hip)
     hipEvent_t ev_reset[EV_RING] = {}, ev_queue[EV_RING] = {};   // the frame's counters are zeroed / the level queue's launch has ended
     // What a finished frame tells the next ones (queue sizing, launch sizes, fallback count): every frame copies its counter
-    // block and the fallback total to ITS slot of this pinned ring, and the host reads a slot only once that frame's last
+    // block, whose last word is the fallback total, to ITS slot of this pinned ring in one copy, and the host reads a slot only once that frame's last
     // event has completed (harvest_counts), so launch decisions are a function of a completed frame, never of a copy in flight.
-    static constexpr uint32_t H_SLOT_WORDS = 512 + 1;   // SC_ALLOC_WORDS + the fallback total
+    static constexpr uint32_t H_SLOT_WORDS = 512;       // SC_ALLOC_WORDS
     uint32_t *h_ring = nullptr;       // EV_RING x H_SLOT_WORDS, pinned
     uint64_t next_count_harvest = 0;  // the oldest launch whose slot has not been read
     uint32_t slot_items[EV_RING] = {};               // work items of the frame in each slot

@@ -71,8 +71,8 @@ static int ensure_frames(crt_ctx *ctx, uint32_t max_depth, bool gi) {
     return CRT_OK;
 }
 
-// What the finished frames left behind.  Every frame copies its counter block and the fallback total into its own slot of
-// the pinned ring (launch_render); a slot is read here only once the frame's last event has completed, so the host never
+// What the finished frames left behind.  Every frame copies its counter block (the fallback total is its last word) into its own slot of
+// the pinned ring (launch_frame); a slot is read here only once the frame's last event has completed, so the host never
 // reads a buffer a copy may still be writing, and what the next launch learns is a function of a COMPLETED frame.
 static void harvest_counts(crt_ctx *ctx) {
     while (ctx->next_count_harvest < ctx->launches) {
@@ -85,7 +85,7 @@ static void harvest_counts(crt_ctx *ctx) {
             ctx->last_counts.assign(h, h + SC_ALLOC_WORDS);
             ctx->last_counts_items = ctx->slot_items[slot];
             ctx->last_counts_cfg = ctx->slot_cfg[slot];
-            ctx->fallbacks_seen = h[SC_ALLOC_WORDS];
+            ctx->fallbacks_seen = h[SC_FALLBACK_TOTAL];
         }
         ctx->next_count_harvest++;
     }
@@ -257,12 +257,23 @@ struct FramePlan {
     bool last_resort;             // render_lanes behind the stream pass
 };
 
+// The one launch ahead of a frame's kernels (kernel_stream.h: stream_frame_reset): this frame's argument block from its pinned slot into its
+// device slot, render_lanes' pixel counter, and -- the ray-stream pass -- the frame's counters, the level queue's words, the tallies and
+// the two preset words.  Every path of launch_frame starts with it, on the frame's stream, so the kernels behind it see the same order.
+static void launch_frame_reset(crt_ctx *ctx, const FramePlan &P, hipStream_t stream, bool stream_pass, uint32_t shadow_preset, uint32_t split_preset) {
+    hipLaunchKernelGGL(stream_frame_reset, dim3(1), dim3(256), 0, stream, stream_pass ? ctx->d_scounts : (uint32_t *)nullptr,
+                       stream_pass && P.queue ? ctx->d_lq_words : (uint32_t *)nullptr, stream_pass && P.exec_count ? ctx->d_exec : (unsigned long long *)nullptr,
+                       shadow_preset, split_preset, ctx->d_sync, (uint32_t *)(ctx->d_frame_ring + P.slot), (const uint32_t *)(ctx->h_frame_ring_dev + P.slot));
+}
+
 // Levels 0 .. MAX_DEPTH on `stream`; after level 0 the bulk shadow pass (and the walks it gives up) on the side stream.
 static int launch_stream_levels(crt_ctx *ctx, const crt_options *o, FramePlan &P, KernelArgs &A, hipStream_t stream) {
-    // the frame's counters, the level queue's words, the tallies: zeroed (and the shadow queue's fill preset to level 0's fixed slots) in one launch
-    hipLaunchKernelGGL(stream_frame_reset, dim3(1), dim3(256), 0, stream, ctx->d_scounts, P.queue ? ctx->d_lq_words : (uint32_t *)nullptr,
-                       P.exec_count ? ctx->d_exec : (unsigned long long *)nullptr,
-                       ctx->frame.fixed0 ? (uint32_t)P.vitems * 64u * ctx->n_lights : 0u);
+    // Level 0's fixed shadow slots: the shadow queue's fill starts there.  Where the level queue runs the frame (P.queue) they are also ALL
+    // the bulk shadow pass walks -- the queue's lanes walk the deeper levels' shadow rays themselves, bvh_trace_shadow<1> is not launched --
+    // so the split mark is a value the host knows and the reset launch presets: no stream_mark_split launch between level 0 and the pass.
+    const uint32_t fixed_slots = ctx->frame.fixed0 ? (uint32_t)P.vitems * 64u * ctx->n_lights : 0u;
+    const bool split_known = P.queue && ctx->frame.fixed0;
+    launch_frame_reset(ctx, P, stream, true, fixed_slots, split_known ? fixed_slots : 0u);
     const uint32_t side_per_cu = ctx->tuning.side_blocks;  // workgroups per CU of the bulk shadow pass beside the levels
     A.exec_count = P.exec_count ? 1u : 0u;
     A.exec_counters = ctx->d_exec;
@@ -368,8 +379,8 @@ static int launch_stream_levels(crt_ctx *ctx, const crt_options *o, FramePlan &P
             else launch(stream_shade_evicted<false>, 256u, stream, A, g);
         }
         if (g == 0) {
-            // where level 0's shadow rays end; they start now, on the side stream, beside the deeper levels
-            hipLaunchKernelGGL(stream_mark_split, dim3(1), dim3(64), 0, stream, A, (uint32_t)SC_SHADOW_SPLIT, (uint32_t)SC_SHADOW);
+            // where level 0's shadow rays end (unless the reset launch has said so already); they start now, on the side stream, beside the deeper levels
+            if (!split_known) hipLaunchKernelGGL(stream_mark_split, dim3(1), dim3(64), 0, stream, A, (uint32_t)SC_SHADOW_SPLIT, (uint32_t)SC_SHADOW);
             hipStream_t where = side_per_cu ? ctx->side : stream;
             if (side_per_cu) {
                 CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork[P.slot], stream));
@@ -462,6 +473,7 @@ static int launch_stream_tail(crt_ctx *ctx, FramePlan &P, KernelArgs &A, hipStre
 
 // The whole frame by render_lanes: crt_tuning::mode = lanes, and GI frames too large for the ray-stream pass.
 static int launch_lanes_pass(crt_ctx *ctx, FramePlan &P, KernelArgs &A, hipStream_t stream) {
+    launch_frame_reset(ctx, P, stream, false, 0u, 0u);   // (the argument block and the pixel counter: this pass has no counters of the stream's)
     CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1[P.slot], stream));
     A.counters = ctx->d_counters + C_N;
     if (P.gi && P.count) launch(render_lanes<true, true>, P.lane_blocks, stream, A);
@@ -524,7 +536,6 @@ static int launch_frame(crt_ctx *ctx, const crt_options *o, uint32_t n_items, fl
     F.bvh_spill_words = ctx->d_bvh_spill ? ctx->bvh_spill_words() : 0u;
     const bool count = o->collect_counters == 1;       // the counting build: every ray walked the reference's way
     const bool exec_count = o->collect_counters == 2;  // the production kernels, tallying the tests they execute
-    CRT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_sync, 0, 4 * sizeof(uint32_t), stream));
     if (count) CRT_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_counters, 0, 3 * C_N * sizeof(unsigned long long), stream));
     harvest_counts(ctx);
     const int slot = (int)(ctx->launches % crt_ctx::EV_RING);
@@ -574,9 +585,9 @@ static int launch_frame(crt_ctx *ctx, const crt_options *o, uint32_t n_items, fl
         // level 0 owns the first n_items * 64 * n_lights slots of the shadow queue; the deeper levels append
         F.fixed0 = (uint64_t)vitems * 64u * ctx->n_lights <= F.s_shadow_cap ? 1u : 0u;
     }
-    // this frame's argument block, into its own slot (the copy is ordered on `stream` ahead of the kernels that read it)
+    // this frame's argument block, into its own pinned slot: the frame's reset launch -- the first on `stream` in either pass below --
+    // copies it to the device slot the kernels read
     ctx->h_frame_ring[slot] = F;
-    CRT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_frame_ring + slot, ctx->h_frame_ring + slot, sizeof(FrameArgs), hipMemcpyHostToDevice, stream));
     KernelArgs A{};
     A.s = (scene_args_p)ctx->d_scene;
     A.f = (frame_args_p)(ctx->d_frame_ring + slot);
@@ -585,10 +596,11 @@ static int launch_frame(crt_ctx *ctx, const crt_options *o, uint32_t n_items, fl
     rc = stream_mode ? launch_stream_levels(ctx, o, P, A, stream) : launch_lanes_pass(ctx, P, A, stream);
     if (rc == CRT_OK && stream_mode) rc = launch_stream_tail(ctx, P, A, stream);
     if (rc) return rc;
-    // what this frame leaves for the next ones: its counter block and the fallback total, into this frame's own pinned slot
+    // what this frame leaves for the next ones: its counter block, the fallback total in its last word, into this frame's own pinned slot
+    // in ONE copy (render_lanes alone leaves no counters: the total only)
     uint32_t *h = ctx->h_ring + (size_t)slot * crt_ctx::H_SLOT_WORDS;
     if (stream_mode) CRT_HIP_CHECK(ctx, hipMemcpyAsync(h, ctx->d_scounts, SC_ALLOC_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    CRT_HIP_CHECK(ctx, hipMemcpyAsync(h + SC_ALLOC_WORDS, ctx->d_fallback_total, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    else CRT_HIP_CHECK(ctx, hipMemcpyAsync(h + SC_FALLBACK_TOTAL, ctx->d_fallback_total, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     ctx->slot_items[slot] = stream_mode ? vitems : 0u;
     ctx->slot_cfg[slot] = frame_config_of(o);
     CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev3[slot], stream));

@@ -547,12 +547,11 @@ extern "C" int crt_create_tuned(const crt_scene_desc *s, int device, const crt_t
     CK(hipMemset(ctx->d_exec, 0, 6 * sizeof(unsigned long long)));
     CK(hipMalloc((void **)&ctx->d_scounts, SC_ALLOC_WORDS * sizeof(uint32_t)));
     CK(hipMemset(ctx->d_scounts, 0, SC_ALLOC_WORDS * sizeof(uint32_t)));
-    static_assert(crt_ctx::H_SLOT_WORDS == SC_ALLOC_WORDS + 1, "pinned slot = counter block + fallback total");
+    static_assert(crt_ctx::H_SLOT_WORDS == SC_ALLOC_WORDS, "pinned slot = counter block, the fallback total in its last word");
     CK(hipHostMalloc((void **)&ctx->h_ring, (size_t)crt_ctx::EV_RING * crt_ctx::H_SLOT_WORDS * sizeof(uint32_t)));
     memset(ctx->h_ring, 0, (size_t)crt_ctx::EV_RING * crt_ctx::H_SLOT_WORDS * sizeof(uint32_t));
     ctx->last_counts.assign(SC_ALLOC_WORDS, 0u);
-    CK(hipMalloc((void **)&ctx->d_fallback_total, sizeof(uint32_t)));
-    CK(hipMemset(ctx->d_fallback_total, 0, sizeof(uint32_t)));
+    ctx->d_fallback_total = ctx->d_scounts + SC_FALLBACK_TOTAL;   // (zero with the block; no frame's reset touches it)
     ctx->n_lights = s->n_lights;
     CK(hipMalloc((void **)&ctx->d_counters, 3 * C_N * sizeof(unsigned long long)));  // [levels | shadow pass 0 | the rest]
     // persistent grid: 8 blocks of 256 threads per CU gives every CU its 32 waves if registers allow
@@ -566,6 +565,7 @@ extern "C" int crt_create_tuned(const crt_scene_desc *s, int device, const crt_t
     CK(hipMemcpy(ctx->d_scene, &ctx->scene, sizeof(SceneArgs), hipMemcpyHostToDevice));
     CK(hipMalloc((void **)&ctx->d_frame_ring, (size_t)crt_ctx::EV_RING * sizeof(FrameArgs)));
     CK(hipHostMalloc((void **)&ctx->h_frame_ring, (size_t)crt_ctx::EV_RING * sizeof(FrameArgs)));
+    CK(hipHostGetDevicePointer((void **)&ctx->h_frame_ring_dev, ctx->h_frame_ring, 0));
 #undef CK
     *out = ctx;
     return CRT_OK;
@@ -598,7 +598,6 @@ extern "C" void crt_destroy(crt_ctx *ctx) {
     if (ctx->h_frame_ring) (void)hipHostFree(ctx->h_frame_ring);
     if (ctx->d_frame_ring) (void)hipFree(ctx->d_frame_ring);
     if (ctx->d_scene) (void)hipFree(ctx->d_scene);
-    if (ctx->d_fallback_total) (void)hipFree(ctx->d_fallback_total);
     if (ctx->d_counters) (void)hipFree(ctx->d_counters);
     if (ctx->d_frames) (void)hipFree(ctx->d_frames);
     for (int i = 0; i < crt_ctx::EV_RING; i++) {

@@ -74,7 +74,7 @@ enum : int { BVH_PLAIN = 0, BVH_TALLY = 1, BVH_CHECKED = 2 };
 constexpr int SC_BVH_DIAG = SC_HEAVY_DIAG + 16;
 // (SC_BVH_DIAG + 0 .. 31: the bounds-checked build's 16 (flag, index) pairs; + 40 .. 43 and + 48 .. 77: the tallying build's walk lengths)
 constexpr int SC_BVH_MARK = SC_BVH_DIAG + 80;   // tallying and bounds-checked builds: the largest number of entries any walk's stack held in the frame
-static_assert(SC_BVH_MARK < SC_ALLOC_WORDS, "the high-water mark is a word of the frame's counter block");
+static_assert(SC_BVH_MARK < SC_FALLBACK_TOTAL, "the high-water mark is a word of the frame's counter block");
 // bounds-checked build, codes of its own checks: the spill element lies in its region; a walk's pops returned what its pushes stored
 enum : uint32_t { BVH_CODE_SPILL = 11, BVH_CODE_STACK_SUM = 12 };
 template <int MODE>

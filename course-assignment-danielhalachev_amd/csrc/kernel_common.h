@@ -29,6 +29,8 @@ enum : int { SC_COUNT = 0, SC_FETCH = MAX_GENERATIONS, SC_HEAVY = 2 * MAX_GENERA
              SC_SHEAVY_FETCH, SC_SHEAVY_FETCH2, SC_GUARD, SC_SHADOW_SPLIT, SC_SHADOW_FETCH2, SC_SHEAVY_SPLIT,
              SC_WORDS,
              SC_HEAVY_DIAG = 384,  // diagnostics of a collect_counters == 2 render (kernel_heavy.h): 8 words closest-hit walks, 8 words shadow walks
+             SC_FALLBACK_TOTAL = 511,  // frames redone by the queue-less kernel since crt_create: the one word a frame's reset leaves alone (it
+                                       // lives here so that the frame's one device-to-host copy of the block carries it)
              SC_ALLOC_WORDS = 512 };
 // kernel_bvh.h, the level queue's words (FrameArgs::s_lq_words): rays reserved / claimed / finished, and a copy of the overflow word for
 // the waves that wait -- 64 KB apart: hundreds of waves poll them, and words that share a memory channel share its request rate (with
@@ -163,9 +165,9 @@ struct FrameArgs {
     float *s_kfac;                // ... and its light factor, by the same index (written by shade_hit beside a queued ray, by whoever walks a fixed slot): with the
                                   // flag all that stream_resolve reads of a slot
     float4 *s_nodes;              // ray-tree nodes (TNode), 2 x float4 each
-    uint32_t *s_counts;           // SC_WORDS counters / cursors, zeroed before every frame
+    uint32_t *s_counts;           // SC_WORDS counters / cursors, zeroed before every frame (all of the block but SC_FALLBACK_TOTAL)
     uint32_t s_ray_cap, s_shadow_cap, s_node_cap;
-    uint32_t *fallback_total;     // frames redone by the queue-less kernel since crt_create (never reset)
+    uint32_t *fallback_total;     // frames redone by the queue-less kernel since crt_create (never reset): s_counts + SC_FALLBACK_TOTAL
     uint32_t *s_heavy;            // evicted ray ids of the current recursion level
     uint32_t *s_sheavy;           // evicted shadow ray ids (same capacity)
     uint32_t s_heavy_cap;

@@ -569,11 +569,24 @@ __global__ __launch_bounds__(BLOCK) void stream_shade_all(const KernelArgs A, co
     }
 }
 
-// What a frame zeroes before its first launch -- the counter block, the level queue's five words (each with three neighbours), the tallies --
-// and the one word it presets (level 0's fixed shadow slots), in ONE launch: as eight memsets they were eight tiny launches of ~7 us
-// each on the frame's stream, 60 us of a 2.6 ms frame.
-__global__ void stream_frame_reset(uint32_t *counts, uint32_t *lq_words, unsigned long long *exec, const uint32_t shadow_preset) {
-    for (uint32_t i = threadIdx.x; i < (uint32_t)SC_ALLOC_WORDS; i += blockDim.x) counts[i] = (i == (uint32_t)SC_SHADOW) ? shadow_preset : 0u;
+// What a frame does before its first launch, in ONE launch: it zeroes the counter block (but for SC_FALLBACK_TOTAL, which counts since
+// crt_create), the level queue's five words (each with three neighbours), the tallies and render_lanes' pixel counter, presets the words the
+// host already knows -- level 0's fixed shadow slots as the shadow queue's fill and, where the bulk shadow pass walks exactly those slots
+// (crt_launch.hip), as its split mark -- and copies the frame's argument block from its pinned slot (`src`, the host-mapped pointer) to
+// its device slot.  As eight memsets the zeroing was eight tiny launches of ~7 us each on the frame's stream, 60 us of a 2.6 ms frame;
+// the pixel counter's memset and the block's host-to-device copy were two more.
+// Nobody reads `dst` in this launch.  The kernels that read it -- through scalar loads, constant address space -- are launches of their
+// own behind this one on its stream, or behind an event recorded behind it (ev_reset): this launch's end releases its stores, their
+// start invalidates the scalar and vector caches, as for the counter block; no fence is needed in here.  The host writes the pinned slot
+// before it enqueues this launch and reuses it only once the slot's previous frame has completed (crt_launch.hip: ev4).
+__global__ void stream_frame_reset(uint32_t *counts, uint32_t *lq_words, unsigned long long *exec, const uint32_t shadow_preset, const uint32_t split_preset,
+                                   uint32_t *sync, uint32_t *dst, const uint32_t *src) {
+    static_assert(sizeof(FrameArgs) % sizeof(uint32_t) == 0, "the argument block is copied word by word");
+    for (uint32_t i = threadIdx.x; i < (uint32_t)(sizeof(FrameArgs) / sizeof(uint32_t)); i += blockDim.x) dst[i] = src[i];
+    if (threadIdx.x < 4u) sync[threadIdx.x] = 0u;
+    if (counts)
+        for (uint32_t i = threadIdx.x; i < (uint32_t)SC_ALLOC_WORDS; i += blockDim.x)
+            if (i != (uint32_t)SC_FALLBACK_TOTAL) counts[i] = (i == (uint32_t)SC_SHADOW) ? shadow_preset : (i == (uint32_t)SC_SHADOW_SPLIT) ? split_preset : 0u;
     if (lq_words && threadIdx.x < 20u) {
         const int line[5] = {LQ_TAIL, LQ_HEAD, LQ_DONE, LQ_ABORT, LQ_LEVEL0};
         lq_words[line[threadIdx.x >> 2] + (threadIdx.x & 3u)] = 0u;
