@@ -539,6 +539,32 @@ extern "C" int crt_bvh_selftest(const crt_scene_desc *s, const float *rays, uint
         }
         return true;
     };
+    // ... and for a triangle without a leaf list (BVH_TRI_WALK): the reference's own descent of the mesh's tree (KDTree.cpp:127-167), a
+    // node's children only where its box passes.  (Such a triangle was counted as visited by EVERY ray once: but a ray with d . n == 0
+    // in floats is "accepted" by it wherever the ray runs -- t = inf, every edge function NaN --, also where the reference never
+    // comes near a leaf listing it, and there the miss check owes nothing.)
+    std::vector<uint32_t> descent;
+    auto ref_visits = [&](const HRay &R, uint32_t mesh, uint32_t tri) {
+        descent.assign(1, s->meshes[mesh].root);
+        while (!descent.empty()) {
+            const uint32_t i = descent.back();
+            descent.pop_back();
+            if (i >= s->n_nodes) continue;
+            const crt_node &n = s->nodes[i];
+            if (!ref_slab(R, n.lo, n.hi) || n.link == CRT_LINK_END) continue;
+            if (is_leaf_link(n.link)) {
+                for (uint64_t e = n.link & ~CRT_LINK_LEAF; e < s->n_leaf_triangles; e++) {
+                    if ((s->leaf_triangles[e] & ~CRT_ENTRY_LAST) == tri) return true;
+                    if (s->leaf_triangles[e] & CRT_ENTRY_LAST) break;
+                }
+                continue;
+            }
+            descent.push_back(n.link);
+            const uint32_t c2 = s->nodes[n.link].miss;
+            if (c2 != n.miss && c2 != CRT_LINK_END) descent.push_back(c2);
+        }
+        return false;
+    };
     std::vector<uint32_t> stack;
     std::vector<char> reached(n_entries);
     for (uint32_t r = 0; r < n_rays; r++) {
@@ -599,7 +625,7 @@ extern "C" int crt_bvh_selftest(const crt_scene_desc *s, const float *rays, uint
             // would the reference test it?  one of its leaves' boxes must pass the reference's slab test
             const uint32_t tri = H.ids[e] & ~BVH_ID_REFRACTIVE;
             bool visited = false;
-            if (H.tri_mesh[tri] & BVH_TRI_WALK) visited = true;   // (no list: count it as visited -- the stricter demand)
+            if (H.tri_mesh[tri] & BVH_TRI_WALK) visited = ref_visits(R, H.tri_mesh[tri] & ~BVH_TRI_WALK, tri);   // (no list: the mesh's tree itself)
             for (uint32_t j = H.tri_leaf_first[tri]; j < H.tri_leaf_first[tri + 1] && !visited; j++)
                 visited = ref_slab(R, &H.tri_leaf_list[8 * (size_t)j], &H.tri_leaf_list[8 * (size_t)j + 4]);
             if (!visited) continue;

@@ -21,9 +21,11 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import scale_sets  # noqa: E402
 from helpers import small_case  # noqa: E402
 from oracle import oracle_api as oa  # noqa: E402
 
+os.environ.setdefault("CRT_TEST_HOOKS", "1")   # the test library: the product's objects + crt_bvh_census (scale_cases below)
 sc = importlib.import_module("course-assignment-danielhalachev_amd").scenes
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -125,9 +127,64 @@ def gi_stats():
     np.savez_compressed(os.path.join(HERE, "gi_stats.npz"), **out)
 
 
+# The scale tests (tests/scale_sets.py).  scale_cases.json: per base scene the two scales that bracket the loss of the candidate
+# filter, by the library's own verdict (crt_bvh_census of the test library, on the CPU), at most a factor 1.25 apart, with the
+# scene's shortest edge at each.  tests/test_scale_filter.py re-derives the two verdicts: when the margin rule changes, the
+# bracket moves, that test fails, and this has to be run again on purpose.
+def has_filter(scene):
+    import ctypes as C
+    pkg = importlib.import_module("course-assignment-danielhalachev_amd")
+    L = pkg.lib()
+    L.crt_bvh_census.argtypes = [C.POINTER(pkg.SceneDesc), C.POINTER(C.c_uint64)]
+    hs = pkg.Scene(json_text=sc.to_json(scene))
+    out = (C.c_uint64 * 8)()
+    rc = L.crt_bvh_census(C.byref(hs.desc), out)
+    assert rc in (pkg.CRT_OK, pkg.CRT_ERR_INVALID)
+    return rc == pkg.CRT_OK
+
+
+def scale_cases():
+    import json
+    out = {}
+    for base in scale_sets.BASES:
+        scene = scale_sets.base_scene(sc, base)
+        lo, hi = 1.0e-4, 1.0
+        assert has_filter(scale_sets.transformed(scene, hi)) and not has_filter(scale_sets.transformed(scene, lo))
+        while hi / lo > 1.25:
+            mid = float("%.3g" % (lo * hi) ** 0.5)
+            if has_filter(scale_sets.transformed(scene, mid)):
+                hi = mid
+            else:
+                lo = mid
+        out[base] = {"S_hi": hi, "S_lo": lo, "triangles": sc.triangle_count(scene),
+                     "shortest_edge_hi": scale_sets.shortest_edge(scale_sets.transformed(scene, hi)),
+                     "shortest_edge_lo": scale_sets.shortest_edge(scale_sets.transformed(scene, lo))}
+        print("scale bracket", base, out[base])
+    with open(scale_sets.CASES_JSON, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+def scale_frames():
+    """The real reference's frame (48x27, depth 3) of four cases of the hw11-like scene: what pins the oracle away from unit scale."""
+    oa.build()
+    for case in scale_sets.FIXTURE_CASES:
+        scene = scale_sets.make_case(sc, "hw11", case, width=48, height=27)
+        blob = sc.to_blob(scene)
+        rgb, _ = oa.reference_render(blob, max_depth=3)
+        np.savez_compressed(os.path.join(HERE, "scale_%s.npz" % case), blob=np.frombuffer(blob, dtype=np.uint8), depth=np.int32(3), rgb=rgb)
+        print("scale", case, scale_sets.case_params("hw11", case), rgb.shape, "blob", len(blob), "bytes, distinct colours",
+              len(np.unique(rgb.reshape(-1, 3), axis=0)))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "gi":
         gi_stats()
+    elif len(sys.argv) > 1 and sys.argv[1] == "scale":
+        scale_cases()
+        scale_frames()
     else:
         main()
         gi_stats()
+        scale_cases()
+        scale_frames()

@@ -5,7 +5,8 @@ import pytest
 
 from helpers import assert_same_floats, blob_to_scene, load_golden
 
-CASES = ["hw07", "hw08", "hw11", "hw14", "hw12", "coverage", "uvwrap"]
+# scale_*: the hw11-like scene of tests/scale_sets.py at the two scales around the loss of the filter, at s = 1e3 and far from the origin
+CASES = ["hw07", "hw08", "hw11", "hw14", "hw12", "coverage", "uvwrap", "scale_hi", "scale_lo", "scale_s1e3", "scale_offset"]
 
 
 @pytest.mark.parametrize("name", CASES)

@@ -4,6 +4,7 @@ binary); skipped elsewhere."""
 import numpy as np
 import pytest
 
+import scale_sets
 from helpers import assert_same_floats
 
 
@@ -30,6 +31,19 @@ def test_restatement_is_bit_exact(oracle, scenes, name, w, h, detail, depth):
     want, _ = oracle.reference_render(blob, max_depth=depth)
     got, _ = oracle.OracleScene(blob).render(depth)
     assert_same_floats(got, want, name)
+
+
+# the scenes of the scale tests (tests/scale_sets.py), at another frame size than their fixtures in tests/golden/
+@pytest.mark.parametrize("base,case", [("hw11", "hi"), ("hw11", "lo"), ("hw11", "s1e3"), ("hw11", "offset"), ("hw11", "combined"), ("hw11", "s1e6"),
+                                       ("hw14", "hi"), ("hw14", "lo")])
+def test_restatement_is_bit_exact_at_scale(oracle, scenes, base, case):
+    if not _have(oracle, False):
+        pytest.skip("oracle/_ref not built here")
+    blob = scenes.to_blob(scale_sets.make_case(scenes, base, case, width=80, height=45))
+    want, _ = oracle.reference_render(blob, max_depth=3)
+    got, _ = oracle.OracleScene(blob).render(3)
+    assert len(np.unique(want.reshape(-1, 3), axis=0)) > 50          # a picture, not a blank frame
+    assert_same_floats(got, want, "%s %s" % (base, case))
 
 
 def test_camera_change_matches_reference(oracle, scenes):
