@@ -125,6 +125,12 @@ class ShootStats(C.Structure):
                 ("shadow_records", C.c_uint64), ("rerouted", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
+class ShootReport(C.Structure):
+    """crt_shoot_report: what the device writes for a Tracer.shoot_rays*_enqueue call"""
+    _fields_ = [("levels", C.c_uint32), ("overflow", C.c_uint32), ("dropped", C.c_uint64), ("level_rays", C.c_uint64 * 64),
+                ("hits", C.c_uint64), ("shadow_records", C.c_uint64), ("rerouted", C.c_uint64)]
+
+
 # crt_hit as a numpy record (what Tracer.trace_rays returns, and the layout of a torch.uint8 [n, 48] output tensor)
 HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, 3), ("normal", np.float32, 3), ("u", np.float32), ("v", np.float32),
                       ("mesh", np.uint32), ("triangle", np.uint32), ("hit", np.uint32)])
@@ -174,6 +180,7 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_st
                   "crt_trace_rays", "crt_trace_rays_device", "crt_occluded_rays", "crt_occluded_rays_device", "crt_camera_rays_device",
                   "crt_get_query_stats", "crt_shade_hits", "crt_shade_hits_device", "crt_light_points", "crt_light_points_device",
                   "crt_shoot_rays", "crt_shoot_rays_device", "crt_get_shoot_stats", "crt_shoot_rays_gi", "crt_shoot_rays_gi_device",
+                  "crt_shoot_rays_enqueue", "crt_shoot_rays_gi_enqueue", "crt_get_shoot_report", "crt_query_scratch_generation",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -234,6 +241,11 @@ def lib():
     L.crt_get_shoot_stats.argtypes = [vp, C.POINTER(ShootStats)]
     L.crt_shoot_rays_gi.argtypes = [vp, vp, vp, C.c_uint64, u32, C.POINTER(Options), vp]
     L.crt_shoot_rays_gi_device.argtypes = [vp, vp, vp, C.c_uint64, u32, C.POINTER(Options), vp, vp]
+    L.crt_shoot_rays_enqueue.argtypes = [vp, vp, C.c_uint64, u32, C.POINTER(Options), vp, vp, vp, vp]
+    L.crt_shoot_rays_gi_enqueue.argtypes = [vp, vp, vp, C.c_uint64, u32, C.POINTER(Options), vp, vp, vp, vp]
+    L.crt_get_shoot_report.argtypes = [vp, C.POINTER(ShootReport)]
+    L.crt_query_scratch_generation.argtypes = [vp]
+    L.crt_query_scratch_generation.restype = C.c_uint64
     L.crt_host_shoot_stats_layout.argtypes = [C.POINTER(u32), u32]
     L.crt_host_shoot_stats_layout.restype = u32
     L.crt_get_kernel_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -700,6 +712,52 @@ class Tracer:
         o = self._gi_options(options, option_fields)
         self._check(lib().crt_shoot_rays_gi_device(self.ctx, C.c_void_p(d_rays_ptr), C.c_void_p(d_keys_ptr or 0), n, ray_type, C.byref(o),
                                                    C.c_void_p(d_rgb_ptr), C.c_void_p(stream_ptr or 0)))
+
+    # ---- radiance queries with no host wait (include/crt_hip.h: crt_shoot_rays*_enqueue)
+    @staticmethod
+    def _level_cap(level_cap, max_depth):
+        """None, or the capacities as the uint32 array of max_depth + 1 entries the call reads ([0] is ignored)"""
+        if level_cap is None:
+            return None
+        caps = np.ascontiguousarray(level_cap, dtype=np.uint32)
+        if caps.shape != (max_depth + 1,):
+            raise ValueError("level_cap: expected %d entries (levels 0 .. max_depth), got shape %r" % (max_depth + 1, caps.shape))
+        return caps
+
+    def shoot_rays_enqueue(self, d_rays_ptr, n, d_rgb_ptr, ray_type=RAY_REFLECTION, max_depth=5, shadow_bias=1e-4, reflection_bias=1e-4,
+                           refraction_bias=1e-4, level_cap=None, d_report_ptr=None, stream_ptr=None):
+        """shoot_rays_device's colours from a call that only enqueues on the stream -- no wait, so it can be captured into a graph.
+        level_cap: rays each level may hold (max_depth + 1 entries), or None for what the context's level arrays hold now (size them
+        with one shoot_rays_device call); d_report_ptr: device memory for a ShootReport, or None.  A child that does not fit is the
+        background, and the report says so (overflow, dropped)."""
+        self._single("shoot_rays_enqueue")
+        o = make_options(max_depth, shadow_bias, reflection_bias, refraction_bias)
+        caps = self._level_cap(level_cap, max_depth)
+        self._check(lib().crt_shoot_rays_enqueue(self.ctx, C.c_void_p(d_rays_ptr), n, ray_type, C.byref(o), C.c_void_p(d_rgb_ptr),
+                                                 _p(caps) if caps is not None else None, C.c_void_p(d_report_ptr or 0),
+                                                 C.c_void_p(stream_ptr or 0)))
+
+    def shoot_rays_gi_enqueue(self, d_rays_ptr, n, d_rgb_ptr, d_keys_ptr=None, ray_type=RAY_REFLECTION, options=None, level_cap=None,
+                              d_report_ptr=None, stream_ptr=None, **option_fields):
+        """shoot_rays_gi_device's colours from a call that only enqueues (see shoot_rays_enqueue)."""
+        self._single("shoot_rays_gi_enqueue")
+        o = self._gi_options(options, option_fields)
+        caps = self._level_cap(level_cap, o.max_depth)
+        self._check(lib().crt_shoot_rays_gi_enqueue(self.ctx, C.c_void_p(d_rays_ptr), C.c_void_p(d_keys_ptr or 0), n, ray_type, C.byref(o),
+                                                    C.c_void_p(d_rgb_ptr), _p(caps) if caps is not None else None,
+                                                    C.c_void_p(d_report_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def shoot_report(self) -> ShootReport:
+        """The report of the last shoot_rays*_enqueue call outside a capture (waits for it)."""
+        self._single("shoot_report")
+        r = ShootReport()
+        self._check(lib().crt_get_shoot_report(self.ctx, C.byref(r)))
+        return r
+
+    def query_scratch_generation(self) -> int:
+        """Changes whenever a query scratch array is reallocated: a graph captured from an enqueue call is valid while it stays."""
+        self._single("query_scratch_generation")
+        return int(lib().crt_query_scratch_generation(self.ctx))
 
     def shoot_stats(self) -> ShootStats:
         """rays / levels / level_rays / shadow_records / rerouted / kernel_ms of the last radiance query (waits for it)."""

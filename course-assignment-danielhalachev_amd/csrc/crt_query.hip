@@ -13,6 +13,9 @@
 #include "crt_internal.h"
 #include "glibc_powf.h"
 #include "gi_random.h"
+#include "shoot_caps.h"
+
+static void query_scratch_changed(crt_ctx *ctx);   // (below crt_query_state)
 
 namespace {
 
@@ -27,9 +30,8 @@ namespace {
 #include "kernel_radiance.h"
 #pragma clang diagnostic pop
 
-// radiance queries: what a level may hold at most (a level is at most twice as wide as the one above it; indices and counts stay
-// inside 31 bits)
-constexpr uint64_t SHOOT_LEVEL_RAYS = 1ull << 30;
+// radiance queries: what a level may hold at most is SHOOT_LEVEL_RAYS (shoot_caps.h: a level is at most twice as wide as the one above
+// it; indices and counts stay inside 31 bits)
 // ... and in the GI mode, where a level is up to max(2, gi_sample_size) times as wide as the one above it: what the DEEPEST level of one
 // pass may hold in the worst case (every ray of every level a DIFFUSE hit); about 8 GB of level arrays.  A call's pass size follows it.
 constexpr uint64_t SHOOT_GI_DEEPEST_RAYS = 1ull << 26;
@@ -53,6 +55,7 @@ struct DeviceArray {
         release();
         CRT_HIP_CHECK(ctx, hipMalloc((void **)&p, n * sizeof(T)));
         cap = n;
+        query_scratch_changed(ctx);   // a graph captured from an enqueue call holds the old pointer (crt_query_scratch_generation)
         return CRT_OK;
     }
     void release() {
@@ -89,6 +92,11 @@ struct QueryCall {
     uint32_t ray_type;
     float shadow_bias;
     bool every_mesh;              // Q_SHADE_HITS: the GI build's occlusion rule (the levels of crt_shoot_rays_gi*)
+    // a level of crt_shoot_rays*_enqueue (Q_CLOSEST, Q_SHADE_HITS): n is the level's CAPACITY, and the kernels read how many rays it
+    // holds from this device word (null: n rays); record `count_first` of the level is the first of this call's arrays
+    const uint32_t *d_count;
+    uint32_t count_first;
+    bool kernels_only;            // an enqueue call: the words are cleared by query_reset, not by hipMemsetAsync (level 0 as well)
 };
 QueryCall closest_call(const crt_ray *rays, uint64_t n, uint32_t ray_type, crt_hit *hits) {
     QueryCall c{};
@@ -122,6 +130,7 @@ QueryCall call_part(QueryCall c, const uint64_t first, const uint64_t m) {
     if (c.normals) c.normals += 3 * first;
     if (c.out) c.out += (c.kind == Q_LIGHT_POINTS ? 1 : 3) * first;
     if (c.status) c.status += first;
+    c.count_first += (uint32_t)first;   // (a level holds at most 2^30 rays)
     return c;
 }
 
@@ -134,6 +143,7 @@ QueryCall call_part(QueryCall c, const uint64_t first, const uint64_t m) {
 //   * a radiance call after any call harvests that one first, for the same reason.
 struct OpenCall {
     bool open = false, radiance = false;
+    bool enqueue = false;   // a radiance call of the enqueue kind: its numbers are the report's (h_report), not h_shoot's
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around its launches
 };
@@ -165,13 +175,24 @@ struct crt_query_state {
     DeviceArray<uint32_t> swords;     // SW_*
     uint64_t *h_shoot = nullptr;      // pinned, SH_*
     crt_shoot_stats shoot{};          // of the last radiance call
+    // crt_shoot_rays*_enqueue
+    DeviceArray<crt_shoot_report> d_report;   // what radiance_report writes for the library's own statistics (outside a capture)
+    DeviceArray<unsigned long long> d_hits0;  // level 0's hits: QW_HITS as the level's trace left it (the lighting launches add to that word)
+    crt_shoot_report *h_report = nullptr;     // pinned: d_report, copied behind the last launch
+    crt_shoot_report report{};                // of the last enqueue call outside a capture
+    uint64_t generation = 0;                  // crt_query_scratch_generation
     ~crt_query_state() {
         if (h_words) (void)hipHostFree(h_words);
         if (h_shoot) (void)hipHostFree(h_shoot);
+        if (h_report) (void)hipHostFree(h_report);
         if (call.ev0) (void)hipEventDestroy(call.ev0);
         if (call.ev1) (void)hipEventDestroy(call.ev1);
     }
 };
+
+static void query_scratch_changed(crt_ctx *ctx) {
+    if (ctx->query) ctx->query->generation++;
+}
 
 void query_destroy(crt_ctx *ctx) {
     delete ctx->query;
@@ -195,7 +216,14 @@ static int query_harvest(crt_ctx *ctx) {
     CRT_HIP_CHECK(ctx, hipEventElapsedTime(&ms, q->call.ev0, q->call.ev1));
     if (q->call.radiance) {   // its last pass's numbers, and what crt_get_query_stats says of it
         q->shoot.kernel_ms = ms;
-        shoot_fold(q);
+        if (q->call.enqueue) {   // (one pass, and the device has done the sums)
+            q->report = *q->h_report;
+            q->shoot.levels = q->report.levels;
+            memcpy(q->shoot.level_rays, q->report.level_rays, sizeof(q->shoot.level_rays));
+            q->shoot.shadow_records = q->report.shadow_records;
+            q->shoot.rerouted = q->report.rerouted;
+            q->stats.hits = q->report.hits;
+        } else shoot_fold(q);
         q->stats.rerouted = q->shoot.rerouted;
         q->stats.kernel_ms = q->shoot.kernel_ms;
     } else {
@@ -209,7 +237,7 @@ static int query_harvest(crt_ctx *ctx) {
 static bool uses_filter(const crt_ctx *ctx) { return ctx->scene.bvh_ok && ctx->tuning.bvh; }
 
 // before a call on `stream`: the waiting rules (OpenCall), and what every query needs, allocated by the first one
-static int query_begin(crt_ctx *ctx, hipStream_t stream, bool radiance) {
+static int query_begin(crt_ctx *ctx, hipStream_t stream, bool radiance, bool enqueue = false) {
     if (ctx->pending) {
         int rc = crt_wait(ctx);
         if (rc) return rc;
@@ -233,6 +261,9 @@ static int query_begin(crt_ctx *ctx, hipStream_t stream, bool radiance) {
         CRT_HIP_CHECK(ctx, hipHostMalloc((void **)&q->h_words, QW_WORDS * sizeof(uint32_t)));
         memset(q->h_words, 0, QW_WORDS * sizeof(uint32_t));
     }
+    // (an enqueue call behind an enqueue call on the same stream is ordered behind it and supersedes its statistics, which come through
+    // a report of their own, not through the words: no wait)
+    if (q->call.open && enqueue && q->call.radiance && q->call.enqueue && q->call.stream == stream) return CRT_OK;
     if (q->call.open && (q->call.stream != stream || q->call.radiance || radiance)) return query_harvest(ctx);
     return CRT_OK;
 }
@@ -240,6 +271,13 @@ static int query_begin(crt_ctx *ctx, hipStream_t stream, bool radiance) {
 // room in the reroute list for the largest launch of n rays or records: before the call's first event, so that growing it is no part of kernel_ms
 static int query_list_reserve(crt_ctx *ctx, const uint64_t n) {
     return uses_filter(ctx) ? ctx->query->list.reserve(ctx, std::min(n, ctx->query_launch_rays)) : CRT_OK;
+}
+
+// query_reset (kernel_query.h): dst = src, then a[0 .. na) = b[0 .. nb) = 0
+static void launch_reset(uint32_t *a, uint32_t na, uint32_t *b, uint32_t nb, const unsigned long long *src, unsigned long long *dst, hipStream_t stream) {
+    ResetArgs P{};
+    P.a = a; P.na = na; P.b = b; P.nb = nb; P.src = src; P.dst = dst;
+    hipLaunchKernelGGL(query_reset, dim3(1), dim3(BLOCK), 0, stream, P);
 }
 
 template <typename Args>
@@ -262,9 +300,15 @@ static int query_launches(crt_ctx *ctx, const QueryCall &C, hipStream_t stream, 
     A.s = (scene_args_p)ctx->d_scene;
     A.f = (frame_args_p)(q->frame.p + (C.every_mesh ? 1 : 0));   // all zero but for use_gi (0: shadow rays skip refractive meshes); the bias travels in ShadeArgs
     const bool filter = uses_filter(ctx);
-    for (uint64_t done = 0; done < C.n; done += ctx->query_launch_rays) {
-        const QueryCall c = call_part(C, done, std::min(C.n - done, ctx->query_launch_rays));
-        if (done || !clean) CRT_HIP_CHECK(ctx, hipMemsetAsync(q->words.p, 0, QW_HITS * sizeof(uint32_t), stream));   // cursors and list length; the totals stay
+    // (an enqueue call grows nothing inside a capture: its parts are what the reroute list holds)
+    const uint64_t part = C.d_count && filter ? std::min<uint64_t>(ctx->query_launch_rays, q->list.cap) : ctx->query_launch_rays;
+    if (part == 0) { ctx->error = "query_launches: no reroute list"; return CRT_ERR_INVALID; }
+    for (uint64_t done = 0; done < C.n; done += part) {
+        const QueryCall c = call_part(C, done, std::min(C.n - done, part));
+        if ((done || !clean) && C.kernels_only) {
+            launch_reset(q->words.p, QW_HITS, nullptr, 0, nullptr, nullptr, stream);
+            CRT_HIP_CHECK(ctx, hipGetLastError());
+        } else if (done || !clean) CRT_HIP_CHECK(ctx, hipMemsetAsync(q->words.p, 0, QW_HITS * sizeof(uint32_t), stream));   // cursors and list length; the totals stay
         ShadeArgs S{};   // (the ray queries' arguments are its first member)
         QueryArgs &Q = S.q;
         Q.n = (uint32_t)c.n;
@@ -274,10 +318,16 @@ static int query_launches(crt_ctx *ctx, const QueryCall &C, hipStream_t stream, 
         Q.direct = filter ? 0u : 1u;
         Q.chunk = std::max(64u, (ctx->tuning.fetch_chunk >> 16) & ~63u);   // (level 0's claim size, crt_tuning::fetch_chunk)
         Q.rays = c.rays; Q.max_distance = c.max_distance; Q.hits = c.hits; Q.occluded = c.occluded; Q.ray_type = c.ray_type;
+        Q.count = c.d_count; Q.first = c.count_first;
         S.hits = c.records; S.points = c.points; S.normals = c.normals; S.out = c.out; S.status = c.status; S.shadow_bias = c.shadow_bias;
         const uint32_t blocks = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(ctx->grid_blocks, (c.n + BLOCK - 1) / BLOCK));
         hipError_t e = hipSuccess;
-        switch (c.kind) {
+        if (c.d_count) {   // the DEVN builds: the levels of crt_shoot_rays*_enqueue
+            if (c.kind == Q_CLOSEST) e = launch_pair(query_walk<BVH_PLAIN, false, true>, query_reroute<false, true>, filter, blocks, stream, A, Q);
+            else if (c.kind != Q_SHADE_HITS) e = hipErrorInvalidValue;
+            else if (c.every_mesh) e = launch_pair(query_direct<BVH_PLAIN, false, true, true>, query_direct_reroute<false, true>, filter, blocks, stream, A, S);
+            else e = launch_pair(query_direct<BVH_PLAIN, false, false, true>, query_direct_reroute<false, true>, filter, blocks, stream, A, S);
+        } else switch (c.kind) {
             case Q_CLOSEST: e = launch_pair(query_walk<BVH_PLAIN, false>, query_reroute<false>, filter, blocks, stream, A, Q); break;
             case Q_OCCLUDED: e = launch_pair(query_walk<BVH_PLAIN, true>, query_reroute<true>, filter, blocks, stream, A, Q); break;
             case Q_SHADE_HITS:
@@ -308,7 +358,7 @@ static int query_run(crt_ctx *ctx, const QueryCall &C, hipStream_t stream, bool 
     CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_words, q->words.p, QW_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     CRT_HIP_CHECK(ctx, hipEventRecord(q->call.ev1, stream));
     q->call.stream = stream;
-    q->call.radiance = false;
+    q->call.radiance = q->call.enqueue = false;
     q->call.open = true;
     return CRT_OK;
 }
@@ -504,24 +554,39 @@ static int shoot_level_reserve(crt_ctx *ctx, const uint32_t g, const uint64_t ca
     return own_rgb ? L.rgb.reserve(ctx, 3 * cap) : CRT_OK;
 }
 
+// what crt_shoot_rays*_enqueue adds to a pass's arguments (null: the host reads every level's size back): the levels' capacities, in
+// place of the sizes.  The scratch holds them already (shoot_enqueue has seen to it): the pass reserves, waits for and reads nothing.
+struct ShootDev {
+    uint32_t cap[MAX_GENERATIONS];   // shoot_level_caps (shoot_caps.h)
+    crt_shoot_report *d_report;      // the caller's, or null
+    bool capturing;                  // the stream is being captured: the library's own copy of the report is not made
+};
+
 // one pass: m rays of the caller's (at most shoot_pass_rays, or what shoot_gi_pass_rays allows), every level of them; leaves the pass's
-// numbers on their way to h_shoot
+// numbers on their way to h_shoot (dev: to h_report)
 static int shoot_pass(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t m, const uint32_t ray_type, const crt_options *o, float *d_rgb,
-                      hipStream_t stream, const ShootGi *gi) {
+                      hipStream_t stream, const ShootGi *gi, const ShootDev *dev = nullptr) {
     crt_query_state *q = ctx->query;
     KernelArgs A{};
     A.s = (scene_args_p)ctx->d_scene;
     A.f = (frame_args_p)q->frame.p;
     const uint64_t fan = shoot_fan(o, gi != nullptr);
-    CRT_HIP_CHECK(ctx, hipMemsetAsync(q->words.p, 0, QW_WORDS * sizeof(uint32_t), stream));
-    CRT_HIP_CHECK(ctx, hipMemsetAsync(q->swords.p, 0, SW_WORDS * sizeof(uint32_t), stream));
-    uint32_t count[MAX_GENERATIONS + 1] = {m};
+    if (dev) {   // (kernel launches alone: shoot_enqueue)
+        launch_reset(q->words.p, QW_WORDS, q->swords.p, SW_WORDS, nullptr, nullptr, stream);
+        CRT_HIP_CHECK(ctx, hipGetLastError());
+    } else {
+        CRT_HIP_CHECK(ctx, hipMemsetAsync(q->words.p, 0, QW_WORDS * sizeof(uint32_t), stream));
+        CRT_HIP_CHECK(ctx, hipMemsetAsync(q->swords.p, 0, SW_WORDS * sizeof(uint32_t), stream));
+    }
+    uint32_t count[MAX_GENERATIONS + 1] = {m};   // dev: the capacities -- what the launches are sized for
+    uint32_t *const d_count = q->swords.p + SW_COUNT;   // [g]: rays appended to level g
     uint32_t last = 0;
     for (uint32_t g = 0; g <= o->max_depth; g++) {
         const uint32_t n = count[g];
         last = g;
         int rc;
-        if ((rc = query_list_reserve(ctx, n)) || (rc = shoot_level_reserve(ctx, g, n, g > 0, gi != nullptr))) return rc;   // (the list follows the widest level)
+        if (!dev && ((rc = query_list_reserve(ctx, n)) || (rc = shoot_level_reserve(ctx, g, n, g > 0, gi != nullptr)))) return rc;   // (the list follows the widest level)
+        const bool devn = dev && g > 0;   // (level 0's size is the caller's n: its launches are those of the other calls)
         const ShootLevel &L = q->lv[g];
         float *rgb = g == 0 ? d_rgb : L.rgb.p;
         const uint32_t blocks = (uint32_t)(((uint64_t)n + BLOCK - 1) / BLOCK);
@@ -533,42 +598,61 @@ static int shoot_pass(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t m, con
             G.in_keys = gi->d_keys; G.keys = L.keys.p; G.gi_samples = o->gi_sample_size; G.gi_seed = o->gi_seed; G.key_first = gi->key_first;
             G.monte_carlo_bias = o->monte_carlo_bias;
         }
+        if (devn) G.n_dev = d_count + g;
         if (g == 0) {
             if (gi) hipLaunchKernelGGL(radiance_prepare<true>, dim3(blocks), dim3(BLOCK), 0, stream, G);
             else hipLaunchKernelGGL(radiance_prepare<false>, dim3(blocks), dim3(BLOCK), 0, stream, G);
             CRT_HIP_CHECK(ctx, hipGetLastError());
         }
         // children are REFLECTION or REFRACTION rays, which walk alike: only the caller's own ray can be PRIMARY (Ray.cpp:13)
-        rc = query_launches(ctx, closest_call(L.rays.p, n, g == 0 ? ray_type : (uint32_t)CRT_RAY_REFLECTION, L.hits.p), stream, g == 0);
+        QueryCall trace = closest_call(L.rays.p, n, g == 0 ? ray_type : (uint32_t)CRT_RAY_REFLECTION, L.hits.p);
+        QueryCall light = shade_call(L.hits.p, n, o->shadow_bias, rgb, L.status.p, gi != nullptr);
+        if (devn) trace.d_count = light.d_count = d_count + g;
+        trace.kernels_only = light.kernels_only = dev != nullptr;
+        rc = query_launches(ctx, trace, stream, g == 0);
         if (rc) return rc;
-        if (g == 0) CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_shoot + SH_HITS0, q->words.p + QW_HITS, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        rc = query_launches(ctx, shade_call(L.hits.p, n, o->shadow_bias, rgb, L.status.p, gi != nullptr), stream, false);
+        if (g == 0 && dev) {
+            launch_reset(nullptr, 0, nullptr, 0, reinterpret_cast<const unsigned long long *>(q->words.p + QW_HITS), q->d_hits0.p, stream);
+            CRT_HIP_CHECK(ctx, hipGetLastError());
+        } else if (g == 0) CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_shoot + SH_HITS0, q->words.p + QW_HITS, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        rc = query_launches(ctx, light, stream, false);
         if (rc) return rc;
         // the next level holds at most `fan` rays for each of this one: room for that BEFORE the launch that fills it
         const bool spawn = g + 1 <= o->max_depth;   // a child enters shootRay with depth g + 1 (RayTracer.cpp:427)
         if (spawn) {
-            if (fan * n > SHOOT_LEVEL_RAYS) { ctx->error = "crt_shoot_rays: a recursion level wider than 2^30 rays"; return CRT_ERR_NOMEM; }
-            rc = shoot_level_reserve(ctx, g + 1, fan * n, true, gi != nullptr);
-            if (rc) return rc;
+            if (!dev) {
+                if (fan * n > SHOOT_LEVEL_RAYS) { ctx->error = "crt_shoot_rays: a recursion level wider than 2^30 rays"; return CRT_ERR_NOMEM; }
+                rc = shoot_level_reserve(ctx, g + 1, fan * n, true, gi != nullptr);
+                if (rc) return rc;
+            }
             G.child_rays = q->lv[g + 1].rays.p;
             G.child_keys = q->lv[g + 1].keys.p;
             G.child_cap = (uint32_t)std::min<uint64_t>(q->lv[g + 1].rays.cap, SHOOT_LEVEL_RAYS);
             if (gi) G.child_cap = (uint32_t)std::min<uint64_t>(G.child_cap, q->lv[g + 1].keys.cap);
+            if (dev) G.child_cap = dev->cap[g + 1];   // (at most what the arrays hold: shoot_enqueue; a child beyond it is the background)
         }
-        G.child_count = q->swords.p + SW_COUNT + g + 1;
+        G.child_count = d_count + g + 1;
         G.spawn = spawn ? 1u : 0u;
-        if (gi) hipLaunchKernelGGL(radiance_scatter<true>, dim3(blocks), dim3(BLOCK), 0, stream, A, G);
+        if (devn) {
+            if (gi) hipLaunchKernelGGL((radiance_scatter<true, true>), dim3(blocks), dim3(BLOCK), 0, stream, A, G);
+            else hipLaunchKernelGGL((radiance_scatter<false, true>), dim3(blocks), dim3(BLOCK), 0, stream, A, G);
+        } else if (gi) hipLaunchKernelGGL(radiance_scatter<true>, dim3(blocks), dim3(BLOCK), 0, stream, A, G);
         else hipLaunchKernelGGL(radiance_scatter<false>, dim3(blocks), dim3(BLOCK), 0, stream, A, G);
         CRT_HIP_CHECK(ctx, hipGetLastError());
         if (!spawn) break;
-        // the one wait of a level: four bytes through pinned memory, to size the next one
-        CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_shoot + SH_COUNT, G.child_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));
-        count[g + 1] = (uint32_t)std::min<uint64_t>(*reinterpret_cast<const uint32_t *>(q->h_shoot + SH_COUNT), fan * n);
+        if (dev) count[g + 1] = dev->cap[g + 1];   // no wait: the next level is launched for what it may hold, and counts for itself
+        else {
+            // the one wait of a level: four bytes through pinned memory, to size the next one
+            CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_shoot + SH_COUNT, G.child_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));
+            count[g + 1] = (uint32_t)std::min<uint64_t>(*reinterpret_cast<const uint32_t *>(q->h_shoot + SH_COUNT), fan * n);
+        }
         if (count[g + 1] == 0) break;
     }
-    for (uint32_t g = 0; g <= last; g++) q->shoot.level_rays[g] += count[g];
-    q->shoot.levels = std::max(q->shoot.levels, last + 1);
+    if (!dev) {
+        for (uint32_t g = 0; g <= last; g++) q->shoot.level_rays[g] += count[g];
+        q->shoot.levels = std::max(q->shoot.levels, last + 1);
+    }
     // the up-sweep: level g's recursing records from level g + 1's colours, which are final by then
     for (uint32_t g = last + 1; g-- > 0;) {
         const ShootLevel &L = q->lv[g];
@@ -578,9 +662,29 @@ static int shoot_pass(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t m, con
         G.child_n = g < last ? count[g + 1] : 0u;
         G.gi_samples = gi ? o->gi_sample_size : 0u;
         const dim3 grid((uint32_t)(((uint64_t)count[g] + BLOCK - 1) / BLOCK));
-        if (gi) hipLaunchKernelGGL(radiance_combine<true>, grid, dim3(BLOCK), 0, stream, A, G);
+        if (dev) {
+            G.n_dev = g > 0 ? d_count + g : nullptr;
+            G.child_n_dev = g < last ? d_count + g + 1 : nullptr;
+            if (gi) hipLaunchKernelGGL((radiance_combine<true, true>), grid, dim3(BLOCK), 0, stream, A, G);
+            else hipLaunchKernelGGL((radiance_combine<false, true>), grid, dim3(BLOCK), 0, stream, A, G);
+        } else if (gi) hipLaunchKernelGGL(radiance_combine<true>, grid, dim3(BLOCK), 0, stream, A, G);
         else hipLaunchKernelGGL(radiance_combine<false>, grid, dim3(BLOCK), 0, stream, A, G);
         CRT_HIP_CHECK(ctx, hipGetLastError());
+    }
+    if (dev) {   // the call's numbers, summed where they are
+        ReportArgs P{};
+        P.count = d_count;
+        P.hits0 = q->d_hits0.p;
+        P.diffuse = reinterpret_cast<const unsigned long long *>(q->swords.p + SW_DIFFUSE);
+        P.rerouted = reinterpret_cast<const unsigned long long *>(q->words.p + QW_REROUTED);
+        P.out = dev->d_report;
+        P.out2 = dev->capturing ? nullptr : q->d_report.p;
+        P.n = m;
+        for (uint32_t g = 0; g <= last; g++) P.cap[g] = count[g];   // (0 behind the last level launched)
+        hipLaunchKernelGGL(radiance_report, dim3(1), dim3(64), 0, stream, P);
+        CRT_HIP_CHECK(ctx, hipGetLastError());
+        if (!dev->capturing) CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_report, q->d_report.p, sizeof(crt_shoot_report), hipMemcpyDeviceToHost, stream));
+        return CRT_OK;
     }
     CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_shoot + SH_DIFFUSE, q->swords.p + SW_DIFFUSE, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_shoot + SH_REROUTED, q->words.p + QW_REROUTED, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
@@ -601,7 +705,7 @@ static int shoot_check(crt_ctx *ctx, const void *rays, const crt_options *option
     return CRT_OK;
 }
 
-// crt_shoot_rays_gi*: the arguments, and *pass = the rays of one pass
+// crt_shoot_rays_gi*: the arguments, and *pass = the rays of one pass (null: no pass size is asked for, and none can be refused)
 static int shoot_gi_check(crt_ctx *ctx, const void *rays, const crt_options *options, const void *out, uint32_t ray_type, const char *what, uint64_t *pass) {
     if (!rays || !options || !out) { ctx->error = std::string(what) + ": NULL array or options with n > 0"; return CRT_ERR_INVALID; }
     if (ray_type > (uint32_t)CRT_RAY_REFRACTION) { ctx->error = std::string(what) + ": unknown ray_type " + std::to_string(ray_type); return CRT_ERR_INVALID; }
@@ -617,6 +721,7 @@ static int shoot_gi_check(crt_ctx *ctx, const void *rays, const crt_options *opt
         ctx->error = std::string(what) + ": max_depth too large: " + std::to_string(options->max_depth) + " + 1 levels, at most " + std::to_string(MAX_GENERATIONS);
         return CRT_ERR_INVALID;
     }
+    if (!pass) return CRT_OK;   // (crt_shoot_rays_gi_enqueue: one pass, whose levels the capacities bound)
     uint64_t product = 0;
     *pass = shoot_gi_pass_rays(ctx, options, &product);
     if (*pass == 0) {
@@ -628,17 +733,29 @@ static int shoot_gi_check(crt_ctx *ctx, const void *rays, const crt_options *opt
     return CRT_OK;
 }
 
+// the radiance queries' own words and pinned slots, the enqueue calls' among them: made by the first radiance call of a context, so that
+// an enqueue call inside a capture finds them
+static int shoot_words_reserve(crt_ctx *ctx) {
+    crt_query_state *q = ctx->query;
+    if (q->h_shoot) return CRT_OK;
+    int rc;
+    if ((rc = q->swords.reserve(ctx, SW_WORDS)) || (rc = q->d_report.reserve(ctx, 1)) || (rc = q->d_hits0.reserve(ctx, 1))) return rc;
+    if (!q->h_report) {
+        CRT_HIP_CHECK(ctx, hipHostMalloc((void **)&q->h_report, sizeof(crt_shoot_report)));
+        memset(q->h_report, 0, sizeof(crt_shoot_report));
+    }
+    CRT_HIP_CHECK(ctx, hipHostMalloc((void **)&q->h_shoot, SH_SLOTS * sizeof(uint64_t)));
+    memset(q->h_shoot, 0, SH_SLOTS * sizeof(uint64_t));
+    return CRT_OK;
+}
+
 // one device call: n rays, `pass` at a time
 static int shoot_run(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *d_rgb, hipStream_t stream,
                      const uint64_t pass, const ShootGi *gi) {
     int rc = query_begin(ctx, stream, true);
     if (rc) return rc;
     crt_query_state *q = ctx->query;
-    if (!q->h_shoot) {
-        if ((rc = q->swords.reserve(ctx, SW_WORDS))) return rc;
-        CRT_HIP_CHECK(ctx, hipHostMalloc((void **)&q->h_shoot, SH_SLOTS * sizeof(uint64_t)));
-        memset(q->h_shoot, 0, SH_SLOTS * sizeof(uint64_t));
-    }
+    if ((rc = shoot_words_reserve(ctx))) return rc;
     q->stats = crt_query_stats{};
     q->stats.rays = n;
     q->shoot = crt_shoot_stats{};
@@ -657,6 +774,80 @@ static int shoot_run(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t r
     CRT_HIP_CHECK(ctx, hipEventRecord(q->call.ev1, stream));
     q->call.stream = stream;
     q->call.radiance = true;
+    q->call.enqueue = false;
+    q->call.open = true;
+    return CRT_OK;
+}
+
+// rays level g's arrays hold now (`own_rgb`, `keys`: as shoot_level_reserve takes them)
+static uint64_t shoot_level_room(const crt_query_state *q, const uint32_t g, const bool own_rgb, const bool keys) {
+    const ShootLevel &L = q->lv[g];
+    uint64_t room = std::min(std::min(L.rays.cap, L.hits.cap), std::min(L.status.cap, L.nodes.cap / 2));
+    if (own_rgb) room = std::min(room, L.rgb.cap / 3);
+    if (keys) room = std::min(room, L.keys.cap);
+    return room;
+}
+
+// crt_shoot_rays*_enqueue: one pass whose levels' sizes stay on the device (shoot_pass with a ShootDev).  Everything that waits,
+// allocates or records an event happens HERE, before the first launch, and none of it inside a capture: what a capture would need of
+// it is refused while nothing is enqueued yet, so that the capture stays valid.
+static int shoot_enqueue(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *o, float *d_rgb,
+                         const uint32_t *level_cap, crt_shoot_report *d_report, hipStream_t stream, const ShootGi *gi, const char *what) {
+    if (n > SHOOT_ENQUEUE_RAYS) {
+        ctx->error = std::string(what) + ": a call is one pass: n = " + std::to_string(n) + " > 2^22 rays; split the rays over several calls";
+        return CRT_ERR_INVALID;
+    }
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    CRT_HIP_CHECK(ctx, hipStreamIsCapturing(stream, &capture));
+    const bool capturing = capture != hipStreamCaptureStatusNone;
+    const auto refuse = [&](const char *why) {
+        ctx->error = std::string(what) + ": the stream is being captured and " + why;
+        return CRT_ERR_INVALID;
+    };
+    int rc;
+    if (capturing) {
+        if (capture != hipStreamCaptureStatusActive) return refuse("the capture is invalidated");
+        if (ctx->pending) return refuse("a crt_render_async frame is pending: the call would have to wait for it (crt_wait before the capture)");
+        if (!ctx->query || !ctx->query->h_words || !ctx->query->h_shoot)
+            return refuse("the query scratch would have to grow (the context has none yet): size it with a radiance call before the capture");
+        if (ctx->query->call.open)
+            return refuse("an open call would have to be harvested, which waits (crt_get_shoot_stats or crt_get_query_stats before the capture)");
+    } else if ((rc = query_begin(ctx, stream, true, true)) || (rc = shoot_words_reserve(ctx))) return rc;
+    crt_query_state *q = ctx->query;
+    // the capacities, and room for them
+    const bool keys = gi != nullptr;
+    uint64_t have[MAX_GENERATIONS];
+    for (uint32_t g = 0; g < (uint32_t)MAX_GENERATIONS; g++) have[g] = shoot_level_room(q, g, true, keys);
+    ShootDev dev{};
+    shoot_level_caps(n, shoot_fan(o, keys), o->max_depth, level_cap, have, dev.cap);
+    uint64_t widest = n;
+    bool fits = shoot_level_room(q, 0, false, keys) >= n;
+    for (uint32_t g = 1; g <= o->max_depth; g++) {
+        widest = std::max<uint64_t>(widest, dev.cap[g]);
+        fits = fits && have[g] >= dev.cap[g];
+    }
+    if (capturing) {
+        // (the reroute list need not follow the widest level here: a level's launches are cut to what the list holds, query_launches)
+        if (!fits || (uses_filter(ctx) && q->list.cap < std::min(n, ctx->query_launch_rays)))
+            return refuse("the query scratch would have to grow for these rays and capacities: make the same call once before the capture");
+    } else {
+        if ((rc = query_list_reserve(ctx, widest)) || (rc = shoot_level_reserve(ctx, 0, n, false, keys))) return rc;
+        for (uint32_t g = 1; g <= o->max_depth && dev.cap[g]; g++)
+            if ((rc = shoot_level_reserve(ctx, g, dev.cap[g], true, keys))) return rc;
+        q->stats = crt_query_stats{};
+        q->stats.rays = n;
+        q->shoot = crt_shoot_stats{};
+        q->shoot.rays = n;
+        CRT_HIP_CHECK(ctx, hipEventRecord(q->call.ev0, stream));
+    }
+    dev.d_report = d_report;
+    dev.capturing = capturing;
+    rc = shoot_pass(ctx, d_rays, (uint32_t)n, ray_type, o, d_rgb, stream, gi, &dev);
+    if (rc || capturing) return rc;   // (a captured call leaves no open call behind: the replays' numbers are d_report's)
+    CRT_HIP_CHECK(ctx, hipEventRecord(q->call.ev1, stream));
+    q->call.stream = stream;
+    q->call.radiance = q->call.enqueue = true;
     q->call.open = true;
     return CRT_OK;
 }
@@ -741,3 +932,35 @@ extern "C" int crt_get_shoot_stats(crt_ctx *ctx, crt_shoot_stats *out) {
     *out = ctx->query->shoot;
     return CRT_OK;
 }
+
+extern "C" int crt_shoot_rays_enqueue(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *d_rgb,
+                                      const uint32_t *level_cap, crt_shoot_report *d_report, void *stream) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    int rc = shoot_check(ctx, d_rays, options, d_rgb, ray_type, "crt_shoot_rays_enqueue");
+    if (rc) return rc;
+    return shoot_enqueue(ctx, d_rays, n, ray_type, options, d_rgb, level_cap, d_report, (hipStream_t)stream, nullptr, "crt_shoot_rays_enqueue");
+}
+
+extern "C" int crt_shoot_rays_gi_enqueue(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t *d_keys, uint64_t n, uint32_t ray_type,
+                                         const crt_options *options, float *d_rgb, const uint32_t *level_cap, crt_shoot_report *d_report,
+                                         void *stream) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    int rc = shoot_gi_check(ctx, d_rays, options, d_rgb, ray_type, "crt_shoot_rays_gi_enqueue", nullptr);
+    if (rc) return rc;
+    const ShootGi gi{d_keys, 0u};
+    return shoot_enqueue(ctx, d_rays, n, ray_type, options, d_rgb, level_cap, d_report, (hipStream_t)stream, &gi, "crt_shoot_rays_gi_enqueue");
+}
+
+extern "C" int crt_get_shoot_report(crt_ctx *ctx, crt_shoot_report *out) {
+    if (!ctx || !out) return CRT_ERR_INVALID;
+    if (!ctx->query) { *out = crt_shoot_report{}; return CRT_OK; }
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    int rc = query_harvest(ctx);
+    if (rc) return rc;
+    *out = ctx->query->report;
+    return CRT_OK;
+}
+
+extern "C" uint64_t crt_query_scratch_generation(const crt_ctx *ctx) { return ctx && ctx->query ? ctx->query->generation : 0; }

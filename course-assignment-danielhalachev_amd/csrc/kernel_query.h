@@ -17,6 +17,7 @@
 
 #include "kernel_bvh.h"
 #include "kernel_lane.h"
+#include "shoot_caps.h"
 
 // The filter's error analysis (kernel_bvh.h, top of the file and bvh_ray_setup) takes t for the distance travelled: |d| = 1 up to
 // rounding.  It has a factor of twelve in hand (a slack of 256 unit roundoffs where about 20 are needed), the shadow walk's
@@ -43,7 +44,18 @@ struct QueryArgs {
     uint32_t *spill;              // the walks' stacks beyond their LDS part: one column per thread of this grid
     uint32_t direct;              // query_reroute: no list -- every ray of the launch (a scene without a filter, crt_tuning::bvh == 0)
     uint32_t chunk;               // indices a wave claims per atomic (kernel_stream.h: wave_fetch_chunked)
+    // the DEVN builds alone (crt_shoot_rays*_enqueue: a level's size stays on the device)
+    const uint32_t *count;        // rays of the whole LEVEL, of which this launch has [first, first + n): n is the launch's capacity
+    uint32_t first;
 };
+
+// rays of this launch.  DEVN: clamp(*count - first, 0, n) (shoot_caps.h) -- one load for the wave, from a word that
+// the launches before this one have finished with.  The other builds read n and are what they were.
+template <bool DEVN>
+__device__ __forceinline__ uint32_t query_count(const QueryArgs &Q) {
+    if constexpr (DEVN) return shoot_part_count((uint32_t)__builtin_amdgcn_readfirstlane(*Q.count), Q.first, Q.n);
+    else return Q.n;
+}
 
 __device__ __forceinline__ void query_load_ray(const QueryArgs &Q, const uint32_t r, Ray &R) {
     const crt_ray q = Q.rays[r];
@@ -118,10 +130,11 @@ __device__ __forceinline__ BvhStack query_stack_of(const QueryArgs &Q, uint32_t 
 //     <= inf), and such a hit is no candidate of the filter: those rays (and only those) go through the miss check when the walk found
 //     no occluder, like a closest-hit ray without a hit -- nothing found (all but certain): not occluded; something found: the
 //     reference-order walk decides.
-template <int MODE, bool OCCLUDED>
+template <int MODE, bool OCCLUDED, bool DEVN = false>
 __global__ __launch_bounds__(BLOCK) void query_walk(const KernelArgs A, const QueryArgs Q) {
     __shared__ uint32_t stack_lds[BVH_LDS_STACK * BLOCK];
     const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t n = query_count<DEVN>(Q);
     const BvhStack stack = query_stack_of(Q, stack_lds);
     const bool primary = !OCCLUDED && Q.ray_type == (uint32_t)RAY_PRIMARY;
     uint32_t nbox = 0, ntri = 0, n_hits = 0;
@@ -146,10 +159,10 @@ __global__ __launch_bounds__(BLOCK) void query_walk(const KernelArgs A, const Qu
                 state = BVH_FETCH;
             }
             // one fetch per free lane and round: no inner loop, no `continue` (compiler notes)
-            const uint32_t claimed = wave_fetch_chunked(Q.words + QW_CURSOR, lane, state == BVH_FETCH, chunk, Q.chunk, Q.n);
+            const uint32_t claimed = wave_fetch_chunked(Q.words + QW_CURSOR, lane, state == BVH_FETCH, chunk, Q.chunk, n);
             if (state == BVH_FETCH) {
                 r = claimed;
-                if (r >= Q.n) state = BVH_OUT;
+                if (r >= n) state = BVH_OUT;
                 else {
                     query_load_ray(Q, r, R);
                     if constexpr (OCCLUDED) {
@@ -181,9 +194,9 @@ __global__ __launch_bounds__(BLOCK) void query_walk(const KernelArgs A, const Qu
 // The rays the filter kernel listed (or, `direct`, every ray of the launch), walked in the reference's order, a lane per ray:
 // render_lanes' walk (kernel_lane.h) without the recursion.  Launched behind the filter kernel with a grid for the worst case --
 // every ray listed --; the list is all but always empty or short, and a workgroup that sees no ray for one of its lanes leaves.
-template <bool OCCLUDED>
+template <bool OCCLUDED, bool DEVN = false>
 __global__ __launch_bounds__(BLOCK) void query_reroute(const KernelArgs A, const QueryArgs Q) {
-    const uint32_t count = Q.direct ? Q.n : Q.words[QW_LIST];
+    const uint32_t count = Q.direct ? query_count<DEVN>(Q) : Q.words[QW_LIST];
     if (blockIdx.x == 0 && threadIdx.x == 0 && count) atomicAdd(reinterpret_cast<unsigned long long *>(Q.words + QW_REROUTED), (unsigned long long)count);
     if ((uint64_t)blockIdx.x * BLOCK >= count) return;
     const uint32_t lane = threadIdx.x & 63u;
@@ -219,6 +232,21 @@ __global__ __launch_bounds__(BLOCK) void query_reroute(const KernelArgs A, const
             }
     }
     wave_add_u64(Q.words + QW_HITS, n_hits, lane);
+}
+
+// crt_shoot_rays*_enqueue: what the other calls do with hipMemsetAsync and a small copy, as ONE kernel -- a captured call is then a
+// chain of kernel nodes and nothing else.  Copies src to dst (64 bits; null: nothing) and then zeroes a[0 .. na) and b[0 .. nb): the
+// counter words before a launch that starts counting again.  One workgroup; plain stores.
+struct ResetArgs {
+    uint32_t *a, *b;
+    uint32_t na, nb;
+    const unsigned long long *src;
+    unsigned long long *dst;
+};
+__global__ __launch_bounds__(BLOCK) void query_reset(const ResetArgs P) {
+    if (threadIdx.x == 0 && P.src) *P.dst = *P.src;
+    for (uint32_t i = threadIdx.x; i < P.na; i += BLOCK) P.a[i] = 0u;
+    for (uint32_t i = threadIdx.x; i < P.nb; i += BLOCK) P.b[i] = 0u;
 }
 
 // RayTracer::getRay (RayTracer.cpp:61-80) at the pixel centre, one thread per pixel, row-major: the direction normalised ONCE, as

@@ -9,6 +9,10 @@
 //                      albedo or Fresnel coefficient, two child indices) and its child rays in level g + 1's ray array;
 //   radiance_combine   from the deepest level up: a lane per recursing record mixes its children's colours into its own.
 //
+// DEVN = true: the builds of crt_shoot_rays*_enqueue, whose host loop never learns a level's size.  The launch is sized for the level's
+// CAPACITY (n, child_n) and the kernel reads how many rays the level holds from the word radiance_scatter counted them in, clamped to
+// that capacity; radiance_report turns the words into the call's crt_shoot_report.  The other builds are what they were.
+//
 // Every level has arrays of its own (rays, records, colours, status, nodes): a parent holds its children's indices in the next level's
 // arrays, so the ORDER in which a level's children are appended may differ between two runs and no colour does.  Nothing of a frame is
 // used: no FrameArgs queue, no level queue, no ray tree of a pixel.
@@ -46,7 +50,22 @@ struct RadianceArgs {
     uint32_t gi_samples;                // GI_SAMPLE_SIZE
     uint32_t gi_seed, key_first;        // in_keys == null: the seed, and the index in the CALL of this pass's first ray
     float monte_carlo_bias;
+    // the DEVN builds alone (crt_shoot_rays*_enqueue); null: n / child_n are the counts themselves (level 0's n is the caller's)
+    const uint32_t *n_dev;              // rays appended to this level: it holds min(*n_dev, n)
+    const uint32_t *child_n_dev;        // ... to level g + 1 (radiance_combine): it holds min(*child_n_dev, child_n)
 };
+
+// rays of a level whose capacity is `cap`: one load for the wave
+template <bool DEVN>
+__device__ __forceinline__ uint32_t radiance_count(const uint32_t *dev, const uint32_t cap) {
+    if constexpr (DEVN) {
+        if (dev) {
+            const uint32_t have = (uint32_t)__builtin_amdgcn_readfirstlane(*dev);
+            return have < cap ? have : cap;
+        }
+    }
+    return cap;
+}
 
 // shootRay's entry (RayTracer.cpp:420) for the caller's rays: normalize3 leaves a zero direction as it is.  GI: and the rays' keys --
 // the caller's, or those of a frame's pixels key_first + r, sample 0 (kernel_stream.h: level0_key).
@@ -69,15 +88,16 @@ __global__ __launch_bounds__(BLOCK) void radiance_prepare(const RadianceArgs G) 
 // leaves point + normal * monte_carlo_bias in gi_sample_direction(incoming direction, normal, u(key, 2 + 2i), u(key, 3 + 2i)) with key
 // child_key(key, 2 + i); the mirror and glass children get child_key(key, 0) and (key, 1).  The record's node holds the first sample's
 // index (CHILD_BG: nothing is traced -- no samples, or they would enter shootRay beyond max_depth).
-template <bool GI>
+template <bool GI, bool DEVN = false>
 __global__ __launch_bounds__(BLOCK) void radiance_scatter(const KernelArgs A, const RadianceArgs G) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;   // (every lane stays to the end: the ballots are the wave's)
-    const uint32_t status = r < G.n ? (uint32_t)G.status[r] : (uint32_t)CRT_SHADE_BACKGROUND;
-    const unsigned long long diffuse = __ballot(r < G.n && status == (uint32_t)CRT_SHADE_DIFFUSE);
+    const uint32_t level_n = radiance_count<DEVN>(G.n_dev, G.n);
+    const uint32_t status = r < level_n ? (uint32_t)G.status[r] : (uint32_t)CRT_SHADE_BACKGROUND;
+    const unsigned long long diffuse = __ballot(r < level_n && status == (uint32_t)CRT_SHADE_DIFFUSE);
     if (lane == 0 && diffuse) atomicAdd(G.diffuse_total, (unsigned long long)__popcll(diffuse));
-    const bool recurses = r < G.n && status == (uint32_t)CRT_SHADE_RECURSES;
-    const bool gi_record = GI && r < G.n && status == (uint32_t)CRT_SHADE_DIFFUSE;
+    const bool recurses = r < level_n && status == (uint32_t)CRT_SHADE_RECURSES;
+    const bool gi_record = GI && r < level_n && status == (uint32_t)CRT_SHADE_DIFFUSE;
     const bool samples = gi_record && G.spawn != 0u && G.gi_samples > 0u;
     uint32_t key = 0;
     if constexpr (GI) if (recurses || samples) key = G.keys[r];
@@ -168,9 +188,10 @@ __global__ __launch_bounds__(BLOCK) void radiance_scatter(const KernelArgs A, co
 }
 
 // the colour shootRay returned for child `index` of the next level (CHILD_BG: the depth rule, RayTracer.cpp:427-429)
-__device__ __forceinline__ void radiance_child(const KernelArgs &A, const RadianceArgs &G, const uint32_t index, float &x, float &y, float &z) {
+__device__ __forceinline__ void radiance_child(const KernelArgs &A, const RadianceArgs &G, const uint32_t child_n, const uint32_t index, float &x,
+                                               float &y, float &z) {
     x = A.s->bgx; y = A.s->bgy; z = A.s->bgz;
-    if (index < G.child_n) { x = G.child_rgb[3 * (size_t)index]; y = G.child_rgb[3 * (size_t)index + 1]; z = G.child_rgb[3 * (size_t)index + 2]; }
+    if (index < child_n) { x = G.child_rgb[3 * (size_t)index]; y = G.child_rgb[3 * (size_t)index + 1]; z = G.child_rgb[3 * (size_t)index + 2]; }
 }
 
 // What calculateReflection / calculateRefraction return once their recursive calls have (RayTracer.cpp:368-372, 414-416): the
@@ -178,10 +199,11 @@ __device__ __forceinline__ void radiance_child(const KernelArgs &A, const Radian
 // this runs for level g.  GI: and what calculateDiffusion returns once its sample rays have (RayTracer.cpp:349-353): the record's
 // colour is its direct light until then; the samples' colours are added in sample order to an indirect sum that starts at 0, a sample
 // that was not traced is the background, and no samples at all is (direct + 0) * (1 / 1).
-template <bool GI>
+template <bool GI, bool DEVN = false>
 __global__ __launch_bounds__(BLOCK) void radiance_combine(const KernelArgs A, const RadianceArgs G) {
     const uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (r >= G.n) return;
+    const uint32_t child_n = radiance_count<DEVN>(G.child_n_dev, G.child_n);
+    if (r >= radiance_count<DEVN>(G.n_dev, G.n)) return;
     if constexpr (GI) {
         if (G.status[r] == (uint8_t)CRT_SHADE_DIFFUSE) {
             const uint32_t first = __float_as_uint(G.nodes[2 * r + 1].x);
@@ -189,7 +211,7 @@ __global__ __launch_bounds__(BLOCK) void radiance_combine(const KernelArgs A, co
             float ix = 0.0f, iy = 0.0f, iz = 0.0f;
             for (uint32_t i = 0; i < G.gi_samples; i++) {
                 float cx, cy, cz;
-                radiance_child(A, G, first == CHILD_BG ? CHILD_BG : first + i, cx, cy, cz);
+                radiance_child(A, G, child_n, first == CHILD_BG ? CHILD_BG : first + i, cx, cy, cz);
                 ix = ix + cx; iy = iy + cy; iz = iz + cz;
             }
             G.rgb[3 * r] = (G.rgb[3 * r] + ix) * gi_inv; G.rgb[3 * r + 1] = (G.rgb[3 * r + 1] + iy) * gi_inv; G.rgb[3 * r + 2] = (G.rgb[3 * r + 2] + iz) * gi_inv;
@@ -200,17 +222,53 @@ __global__ __launch_bounds__(BLOCK) void radiance_combine(const KernelArgs A, co
     const float4 n0 = G.nodes[2 * r], n1 = G.nodes[2 * r + 1];
     const uint32_t kind = __float_as_uint(n0.w) & TN_KIND_MASK;
     float cx, cy, cz;
-    radiance_child(A, G, __float_as_uint(n1.x), cx, cy, cz);   // the reflection ray is shot first (RayTracer.cpp:366, 398-400)
+    radiance_child(A, G, child_n, __float_as_uint(n1.x), cx, cy, cz);   // the reflection ray is shot first (RayTracer.cpp:366, 398-400)
     if (kind == TN_REFLECT) {
         cx = 0.0f + n0.x * cx; cy = 0.0f + n0.y * cy; cz = 0.0f + n0.z * cz;   // RayTracer.cpp:368-372
     } else {
         const uint32_t refr = __float_as_uint(n1.y);
         if (refr != CHILD_NONE) {   // (CHILD_NONE: `return reflectionColor`, RayTracer.cpp:416)
             float tx, ty, tz;
-            radiance_child(A, G, refr, tx, ty, tz);
+            radiance_child(A, G, child_n, refr, tx, ty, tz);
             const float f = n1.z;
             cx = f * cx + (1 - f) * tx; cy = f * cy + (1 - f) * ty; cz = f * cz + (1 - f) * tz;   // RayTracer.cpp:414
         }
     }
     G.rgb[3 * r] = cx; G.rgb[3 * r + 1] = cy; G.rgb[3 * r + 2] = cz;
+}
+
+// The call's crt_shoot_report from the device words, behind the last radiance_combine: one wave, lane g for level g.  Level 0 holds the
+// caller's rays; level g >= 1 holds min(count[g], cap[g]) of the count[g] children radiance_scatter appended to it, and the rest did not
+// fit (cap[g] = 0 behind the last level the host launched).  Written to `out` and `out2`, whichever is not null, with plain stores.
+struct ReportArgs {
+    const uint32_t *count;               // [g]: rays appended to level g (g >= 1)
+    const unsigned long long *hits0;     // the caller's rays with a hit
+    const unsigned long long *diffuse;   // DIFFUSE records over all levels
+    const unsigned long long *rerouted;  // the constituent launches' rerouted rays and records
+    crt_shoot_report *out, *out2;
+    uint32_t n;                          // the caller's rays
+    uint32_t cap[MAX_GENERATIONS];
+};
+__global__ __launch_bounds__(64) void radiance_report(const ReportArgs P) {
+    const uint32_t g = threadIdx.x;
+    const uint32_t appended = g == 0 ? P.n : P.count[g];
+    const uint32_t held = g == 0 ? P.n : (appended < P.cap[g] ? appended : P.cap[g]);
+    const unsigned long long lost = __ballot(appended > held);
+    unsigned long long dropped = appended - held;
+    for (int off = 32; off > 0; off >>= 1) dropped += __shfl_down(dropped, off);
+    const uint32_t levels = (uint32_t)__popcll(__ballot(held > 0u));   // (level g + 1 holds children of level g: the levels with rays are the first ones)
+    crt_shoot_report *const outs[2] = {P.out, P.out2};
+    for (int k = 0; k < 2; k++) {
+        crt_shoot_report *o = outs[k];
+        if (!o) continue;
+        o->level_rays[g] = held;
+        if (g == 0) {
+            o->levels = levels;
+            o->overflow = lost ? (uint32_t)__ffsll((long long)lost) - 1u : 0u;   // level g + 1 is lane g + 1: 1 + g
+            o->dropped = dropped;
+            o->hits = *P.hits0;
+            o->shadow_records = *P.diffuse;
+            o->rerouted = *P.rerouted;
+        }
+    }
 }

@@ -68,11 +68,12 @@ __device__ __forceinline__ void shade_store(const KernelArgs &A, const ShadeArgs
 // sets up the next shadow ray, or is through), BVH_WALK, BVH_FINISHED (its record is to be stored or listed), BVH_OUT.
 // EVERY: the GI build's occlusion rule -- no mesh is skipped (AccelerationStructure.cpp:67-71) -- as a build of its own, for the levels
 // of crt_shoot_rays_gi*: the plain build is what it was, instruction for instruction.
-template <int MODE, bool POINTS, bool EVERY = false>
+template <int MODE, bool POINTS, bool EVERY = false, bool DEVN = false>
 __global__ __launch_bounds__(BLOCK) void query_direct(const KernelArgs A, const ShadeArgs S) {
     __shared__ uint32_t stack_lds[BVH_LDS_STACK * BLOCK];
     const uint32_t lane = threadIdx.x & 63u;
     const QueryArgs &Q = S.q;
+    const uint32_t n = query_count<DEVN>(Q);
     const BvhStack stack = query_stack_of(Q, stack_lds);
     const uint32_t n_lights = A.s->n_lights;
     uint32_t nbox = 0, ntri = 0, n_diffuse = 0;
@@ -99,10 +100,10 @@ __global__ __launch_bounds__(BLOCK) void query_direct(const KernelArgs A, const 
                 state = BVH_FETCH;
             }
             // one fetch per free lane and round: no inner loop, no `continue` (compiler notes)
-            const uint32_t claimed = wave_fetch_chunked(Q.words + QW_CURSOR, lane, state == BVH_FETCH, chunk, Q.chunk, Q.n);
+            const uint32_t claimed = wave_fetch_chunked(Q.words + QW_CURSOR, lane, state == BVH_FETCH, chunk, Q.chunk, n);
             if (state == BVH_FETCH) {
                 r = claimed;
-                if (r >= Q.n) state = BVH_OUT;
+                if (r >= n) state = BVH_OUT;
                 else {
                     const uint32_t status = shade_load<POINTS>(A, S, r, H);
                     if (status != CRT_SHADE_DIFFUSE) shade_store<POINTS>(A, S, r, status, 0.0f, 0.0f, 0.0f);   // (the lane fetches again next round)
@@ -151,10 +152,10 @@ __global__ __launch_bounds__(BLOCK) void query_direct(const KernelArgs A, const 
 // record, every light of it walked in the reference's order as render_lanes walks a diffuse hit's shadow rays (kernel_lane.h:
 // traversal_begin / traversal_step<false>, rtype SHADOW; that walk reads the occlusion rule from the frame block, A.f->use_gi: the
 // queries have an all-zero block and one with use_gi = 1).  The grid is sized for the worst case; a workgroup without a record leaves.
-template <bool POINTS>
+template <bool POINTS, bool DEVN = false>
 __global__ __launch_bounds__(BLOCK) void query_direct_reroute(const KernelArgs A, const ShadeArgs S) {
     const QueryArgs &Q = S.q;
-    const uint32_t count = Q.direct ? Q.n : Q.words[QW_LIST];
+    const uint32_t count = Q.direct ? query_count<DEVN>(Q) : Q.words[QW_LIST];
     if ((uint64_t)blockIdx.x * BLOCK >= count) return;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t n_lights = A.s->n_lights;

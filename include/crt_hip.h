@@ -448,6 +448,61 @@ int crt_shoot_rays_gi(crt_ctx *ctx, const crt_ray *rays, const uint32_t *keys, u
 int crt_shoot_rays_gi_device(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t *d_keys, uint64_t n, uint32_t ray_type,
                              const crt_options *options, float *d_rgb, void *stream);
 
+/* ---- Radiance queries with no host wait: crt_shoot_rays_device's and crt_shoot_rays_gi_device's colours from a call that only ENQUEUES
+ * and can be captured into a hipGraph -- light probes re-shot every frame, other cameras, depth of field, re-shooting changed pixels
+ * inside an animation loop.  Kernels: the DEVN builds of csrc/kernel_query.h, kernel_shade.h and kernel_radiance.h.  Single-device
+ * contexts only.
+ *
+ * The colours are crt_shoot_rays_device's (crt_shoot_rays_gi_device's), bit for bit, for every ray whose ray tree lost no child (below).
+ *   The walks, the lighting, the scatter and combine arithmetic, the keys and ray_type are those calls'; the same `options` fields are
+ *   read and the same CRT_ERR_INVALID rules hold for use_gi, gi_sample_size, max_depth, ray_type and NULL arguments.  n == 0 is CRT_OK and
+ *   touches nothing.  A call is ONE pass: n > 2^22 is CRT_ERR_INVALID, the caller splits.  The GI calls' worst-case product rule (64 x
+ *   fan^max_depth <= 2^26) does not apply: the capacities bound the memory.
+ * Level capacities.  With fan = 2 (the GI call: max(2, gi_sample_size)), level g, 1 <= g <= max_depth, holds at most
+ *   min(level_cap[g], fan^g n, 2^30) rays (the GI call: and (2^32 - 1) / fan while g < max_depth, so that no 32-bit count wraps);
+ *   level_cap has max_depth + 1 entries and level_cap[0] is ignored.  level_cap == NULL means "what this context's level arrays hold now":
+ *   the width earlier radiance calls left (the scratch grows and is kept, and those calls reserve fan x a level's rays for the level
+ *   below it).  The intended use is the frames' pattern: one ordinary crt_shoot_rays_device call to size the context, then enqueue calls.
+ *   With explicit capacities, and outside a capture, the call first grows the scratch to them, like any other query.
+ * No waits.  The call enqueues its launches on `stream` and returns: no hipStreamSynchronize, no readback that the host waits for.  Every
+ *   level's kernels are launched for the level's CAPACITY and read the level's actual size from a device word (the count of the rays
+ *   appended to it, clamped to the capacity).  A level that ran dry costs empty launches, nothing else.
+ * Overflow.  A child that does not fit its level becomes the background, as a child beyond max_depth is; nothing is written out of
+ *   bounds, the return code stays CRT_OK, and the report says so (overflow, dropped).  Colours of rays whose ray tree lost no child are
+ *   still exact; the caller repeats the call with larger capacities, or uses the synchronous call.  (GI: a DIFFUSE record's samples fit
+ *   as a block or not at all; slots of the level that a refused block leaves unwritten are traced with what they held, and count in
+ *   level_rays, not in dropped.  No other ray reads their colours.)
+ * d_report (device memory, 8-byte aligned; may be NULL) is filled by one small kernel behind the last launch.
+ * Outside a capture the call is an open call like the other device calls: events are recorded around it, crt_get_shoot_stats and
+ *   crt_get_query_stats are filled from the report (copied to pinned memory behind the last launch) and crt_get_shoot_report returns
+ *   it.  The waiting rules of the other queries apply (a pending crt_render_async frame, an open call on another stream, an open call
+ *   of another kind are waited for first), with one exception: an enqueue call behind an enqueue call on the SAME stream waits for
+ *   nothing and supersedes its statistics.
+ * While `stream` is being captured (hipStreamIsCapturing) the call makes NO HIP call that synchronises, allocates or records one of the
+ *   library's events.  If it would need one -- a pending crt_render_async frame, an open call to harvest, scratch that would have to
+ *   grow (a context without a radiance call so far has none) -- it returns CRT_ERR_INVALID with a message that names the reason BEFORE
+ *   it enqueues anything, so the capture stays valid.  It leaves no open call behind and touches no statistics: those of the replays
+ *   come through d_report alone.
+ * The captured graph is a single chain on the caller's stream -- no second stream, no parallel branch.  It holds pointers into the
+ *   context's scratch: it is valid while crt_query_scratch_generation(ctx) is unchanged and the context lives.  While it may be running,
+ *   ordering other queries of this context behind it is the caller's job (they share the scratch). */
+typedef struct crt_shoot_report {   /* written by the DEVICE, 8-byte aligned */
+    uint32_t levels;           /* recursion levels that held at least one ray */
+    uint32_t overflow;         /* 0, or 1 + the first level g whose children did not all fit level g + 1 */
+    uint64_t dropped;          /* children that did not fit, all levels */
+    uint64_t level_rays[64];   /* rays traced at level g */
+    uint64_t hits;             /* the caller's rays with a hit (level 0) */
+    uint64_t shadow_records, rerouted;   /* as in crt_shoot_stats */
+} crt_shoot_report;
+int crt_shoot_rays_enqueue(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *d_rgb,
+                           const uint32_t *level_cap, crt_shoot_report *d_report, void *stream);
+int crt_shoot_rays_gi_enqueue(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t *d_keys, uint64_t n, uint32_t ray_type,
+                              const crt_options *options, float *d_rgb, const uint32_t *level_cap, crt_shoot_report *d_report, void *stream);
+/* host copy of the last non-captured enqueue call's report; waits for it */
+int crt_get_shoot_report(crt_ctx *ctx, crt_shoot_report *out);
+/* changes whenever any query scratch array is reallocated */
+uint64_t crt_query_scratch_generation(const crt_ctx *ctx);
+
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
  * stream per listed device (a device may be listed more than once); the covered 8x8 tiles are dealt round-robin, every
