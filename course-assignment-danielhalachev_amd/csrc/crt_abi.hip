@@ -277,8 +277,15 @@ extern "C" int crt_kernel_times_ms(crt_ctx *ctx, double *out_phase_ms, uint32_t 
         CRT_HIP_CHECK(ctx, hipEventElapsedTime(&t, ctx->ev0[slot], ctx->ev4[slot]));
         CRT_HIP_CHECK(ctx, hipEventElapsedTime(&a, ctx->ev0[slot], ctx->ev1[slot]));
         CRT_HIP_CHECK(ctx, hipEventElapsedTime(&b, ctx->ev_s0[slot], ctx->ev_s1[slot]));
-        CRT_HIP_CHECK(ctx, hipEventElapsedTime(&c, ctx->ev1[slot], ctx->ev2[slot]));
-        CRT_HIP_CHECK(ctx, hipEventElapsedTime(&e, ctx->ev2[slot], ctx->ev3[slot]));
+        // ev2 marks the point where the levels AND pass 0 have ended.  A frame whose pass ran on the frame's stream recorded nothing there: it is
+        // the later of ev1 (the queue's last launch, on its own stream) and ev_s1 (the pass), which the resolve waits for
+        hipEvent_t e2 = ctx->ev2[slot];
+        if (ctx->slot_ev2_is_s1[slot]) {
+            CRT_HIP_CHECK(ctx, hipEventElapsedTime(&c, ctx->ev1[slot], ctx->ev_s1[slot]));
+            e2 = c < 0.0f ? ctx->ev1[slot] : ctx->ev_s1[slot];
+        }
+        CRT_HIP_CHECK(ctx, hipEventElapsedTime(&c, ctx->ev1[slot], e2));
+        CRT_HIP_CHECK(ctx, hipEventElapsedTime(&e, e2, ctx->ev3[slot]));
         if (out_phase_ms) {
             out_phase_ms[5 * i] = t; out_phase_ms[5 * i + 1] = a; out_phase_ms[5 * i + 2] = b;
             out_phase_ms[5 * i + 3] = c; out_phase_ms[5 * i + 4] = e;

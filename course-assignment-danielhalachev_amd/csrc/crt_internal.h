@@ -48,6 +48,7 @@ struct crt_ctx {
     static constexpr int EV_RING = 64;       // event sets of the most recent render launches
     hipEvent_t ev0[EV_RING] = {}, ev1[EV_RING] = {}, ev2[EV_RING] = {}, ev3[EV_RING] = {}, ev4[EV_RING] = {};  // phase boundaries of a render
     hipEvent_t ev_fork[EV_RING] = {}, ev_s0[EV_RING] = {}, ev_s1[EV_RING] = {}, ev_s2[EV_RING] = {};        // ... of its side stream
+    bool slot_ev2_is_s1[EV_RING] = {};       // the slot's frame ran its pass on the frame's stream and did not record ev2: the later of ev1 and ev_s1 marks that point (crt_launch.hip, crt_kernel_times_ms)
     uint64_t launches = 0;
     uint32_t width = 0, height = 0, tiles_x = 0, tiles_y = 0;
     SceneArgs scene{};                // host copy of what crt_create uploads to d_scene
@@ -86,7 +87,7 @@ struct crt_ctx {
     uint32_t bvh_stack_built = 0;     // SceneArgs::bvh_stack as crt_create sized it (a test hook may lower the scene's value, never this one)
     // words of one spill region: a column of (built stack - LDS part) entries for every thread of the largest grid
     size_t bvh_spill_words() const { return bvh_stack_built > BVH_LDS_STACK ? (size_t)grid_blocks * BLOCK * (bvh_stack_built - BVH_LDS_STACK) : 0u; }
-    hipStream_t side = nullptr;       // shadow pass 0 overlaps the deeper recursion levels on this stream
+    hipStream_t side = nullptr;       // shadow pass 0 overlaps the deeper recursion levels on this stream (where a frame's levels are launches of their own)
     hipStream_t early = nullptr;      // the level queue's launch starts WITH level 0 on this one (crt_launch.hip)
     hipEvent_t ev_reset[EV_RING] = {}, ev_queue[EV_RING] = {};   // the frame's counters are zeroed / the level queue's launch has ended
     // What a finished frame tells the next ones (queue sizing, launch sizes, fallback count): every frame copies its counter

@@ -255,6 +255,7 @@ struct FramePlan {
     uint32_t level_budget;        // steps after which a deeper level's per-lane walk is evicted
     const uint32_t *prev;         // counters of a completed frame of this size and kind, or null
     bool last_resort;             // render_lanes behind the stream pass
+    bool one_stream;              // level 0, the bulk shadow pass and the resolve follow one another on the frame's stream (launch_stream_levels)
 };
 
 // The one launch ahead of a frame's kernels (kernel_stream.h: stream_frame_reset): this frame's argument block from its pinned slot into its
@@ -266,7 +267,8 @@ static void launch_frame_reset(crt_ctx *ctx, const FramePlan &P, hipStream_t str
                        shadow_preset, split_preset, ctx->d_sync, (uint32_t *)(ctx->d_frame_ring + P.slot), (const uint32_t *)(ctx->h_frame_ring_dev + P.slot));
 }
 
-// Levels 0 .. MAX_DEPTH on `stream`; after level 0 the bulk shadow pass (and the walks it gives up) on the side stream.
+// Levels 0 .. MAX_DEPTH on `stream`; after level 0 the bulk shadow pass (and the walks it gives up) on the side stream -- or, where the level
+// queue runs beside level 0 and `stream` has nothing else to do (FramePlan::one_stream), on `stream` itself.
 static int launch_stream_levels(crt_ctx *ctx, const crt_options *o, FramePlan &P, KernelArgs &A, hipStream_t stream) {
     // Level 0's fixed shadow slots: the shadow queue's fill starts there.  Where the level queue runs the frame (P.queue) they are also ALL
     // the bulk shadow pass walks -- the queue's lanes walk the deeper levels' shadow rays themselves, bvh_trace_shadow<1> is not launched --
@@ -315,6 +317,10 @@ static int launch_stream_levels(crt_ctx *ctx, const crt_options *o, FramePlan &P
     // every level below level 0: one launch that feeds itself (kernel_bvh.h); one workgroup per CU holds more lanes than the widest
     // level of a frame of this size has rays
     const bool early_queue = P.queue && side_per_cu && !(ctx->tuning.level_queue & 512u) && !g_debug_sync;   // (level_queue bit 9: the launch behind level 0, as it used to be)
+    // The production frame -- the level queue beside level 0, the pass's slots known to the host -- has nothing on `stream` between level 0 and
+    // the resolve but the pass: it follows level 0 there as a plain kernel-after-kernel dependency, and the resolve follows it the same way.
+    // (Everywhere else the pass runs BESIDE the levels' own launches on `stream`, and the side stream is what lets it.)
+    P.one_stream = early_queue && P.bvh && split_known && !(ctx->tuning.level_queue & 4096u);
     auto launch_queue = [&](hipStream_t where) {
         KernelArgs Q = A;
         const uint32_t qblocks = std::min(P.lane_blocks, (uint32_t)ctx->num_cus * std::max(1u, ctx->tuning.level_queue & 15u));
@@ -381,11 +387,14 @@ static int launch_stream_levels(crt_ctx *ctx, const crt_options *o, FramePlan &P
         if (g == 0) {
             // where level 0's shadow rays end (unless the reset launch has said so already); they start now, on the side stream, beside the deeper levels
             if (!split_known) hipLaunchKernelGGL(stream_mark_split, dim3(1), dim3(64), 0, stream, A, (uint32_t)SC_SHADOW_SPLIT, (uint32_t)SC_SHADOW);
-            hipStream_t where = side_per_cu ? ctx->side : stream;
-            if (side_per_cu) {
+            hipStream_t where = side_per_cu && !P.one_stream ? ctx->side : stream;
+            // (one stream: ev_s0 below marks level 0's end too -- the queue's second launch waits for that one; each record between two
+            //  launches of a stream holds the second back by ~5 us, timed or not)
+            if (side_per_cu && !P.one_stream) {
                 CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork[P.slot], stream));
                 CRT_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork[P.slot], 0));
             }
+            if (P.one_stream && o->max_depth == 0) CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1[P.slot], stream));   // (no queue launch: the levels end here)
             CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev_s0[P.slot], where));
             // (beside the levels its persistent waves must leave wave slots on every CU for the level kernels)
             const uint32_t blocks0 = side_per_cu ? std::min(ctx->grid_blocks, (uint32_t)ctx->num_cus * side_per_cu) : ctx->grid_blocks;   // (a spill region holds grid_blocks workgroups' columns)
@@ -403,14 +412,16 @@ static int launch_stream_levels(crt_ctx *ctx, const crt_options *o, FramePlan &P
             if (P.heavy && !P.bvh) hipLaunchKernelGGL(stream_mark_split, dim3(1), dim3(64), 0, where, S, (uint32_t)SC_SHEAVY_SPLIT, (uint32_t)SC_SHEAVY);
             CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev_s1[P.slot], where));
             if (P.heavy && !P.bvh) launch(P.exec_count ? heavy_trace_shadow_tally : heavy_trace_shadow, HEAVY_BLOCKS, where, S, 0u);
-            CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev_s2[P.slot], where));
+            if (!P.one_stream) CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev_s2[P.slot], where));   // (one stream: nothing waits for it, nobody reads it)
         }
         if (P.queue) {
             if (early_queue && o->max_depth >= 1) {
                 // ... and once more behind level 0 AND the first launch: nothing promises that two streams' kernels run side by side, so the
                 // first launch's patience with an empty queue is bounded, and what it left is walked here (normally nothing: ~15 us)
-                CRT_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->early, ctx->ev_fork[P.slot], 0));
+                CRT_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->early, P.one_stream ? ctx->ev_s0[P.slot] : ctx->ev_fork[P.slot], 0));
                 launch_queue(ctx->early);
+                // (the pass holds `stream` until it ends: "recursion levels" still ends where this launch does)
+                if (P.one_stream) CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1[P.slot], ctx->early));
                 CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev_queue[P.slot], ctx->early));
                 CRT_HIP_CHECK(ctx, hipStreamWaitEvent(stream, ctx->ev_queue[P.slot], 0));
             }
@@ -427,9 +438,9 @@ static int launch_stream_tail(crt_ctx *ctx, FramePlan &P, KernelArgs &A, hipStre
     const uint32_t *prev = P.prev;
     const uint32_t level_budget = P.level_budget;
     CRT_HIP_CHECK(ctx, hipGetLastError());
-    CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1[P.slot], stream));
+    if (!P.one_stream) CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1[P.slot], stream));   // (one stream: recorded where the levels ended, launch_stream_levels)
     // the shadow rays of the deeper levels (queued behind level 0's), then the wave-per-ray walks of both passes
-    if (side_per_cu) CRT_HIP_CHECK(ctx, hipStreamWaitEvent(stream, ctx->ev_s1[P.slot], 0));
+    if (side_per_cu && !P.one_stream) CRT_HIP_CHECK(ctx, hipStreamWaitEvent(stream, ctx->ev_s1[P.slot], 0));
     KernelArgs S1 = A;
     S1.wave_prio = 0u;
     S1.counters = ctx->d_counters + 2 * C_N;
@@ -452,10 +463,11 @@ static int launch_stream_tail(crt_ctx *ctx, FramePlan &P, KernelArgs &A, hipStre
     else if (P.wide) launch(stream_trace_shadow_plan_wide<1>, P.lane_blocks, stream, S1);
     else if (P.lean) launch(stream_trace_shadow_plan<1>, P.lane_blocks, stream, S1);
     else launch(stream_trace_shadow<false>, P.lane_blocks, stream, S1, 1u);
-    if (side_per_cu) CRT_HIP_CHECK(ctx, hipStreamWaitEvent(stream, ctx->ev_s2[P.slot], 0));
+    if (side_per_cu && !P.one_stream) CRT_HIP_CHECK(ctx, hipStreamWaitEvent(stream, ctx->ev_s2[P.slot], 0));
     if (P.heavy && !P.bvh) launch(P.exec_count ? heavy_trace_shadow_tally : heavy_trace_shadow, HEAVY_BLOCKS, stream, S1, 1u);
     CRT_HIP_CHECK(ctx, hipGetLastError());
-    CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev2[P.slot], stream));
+    // (one stream: the later of ev_s1, recorded behind the pass on this stream, and ev1 marks this point: crt_kernel_times_ms reads them, slot_ev2_is_s1)
+    if (!P.one_stream) CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev2[P.slot], stream));
     A.counters = ctx->d_counters + 2 * C_N;
     // post-order combination per pixel, then the queue-less fallback, which only runs after an overflow
     if (P.count) launch(stream_resolve<true>, P.lane_blocks, stream, A);
@@ -488,7 +500,7 @@ static int launch_lanes_pass(crt_ctx *ctx, FramePlan &P, KernelArgs &A, hipStrea
 // One frame's launches.  Ray-stream path (kernel_stream.h), per recursion level g = 0 .. MAX_DEPTH on `stream`:
 //   the per-lane kernel (plan kernels; the faithful kernel for the counting build and for scenes without a plan),
 //   heavy_trace_closest for the walks it handed over (or the whole level), stream_shade_evicted for their hits;
-// the bulk shadow pass (level 0's shadow rays) on the side stream as soon as level 0 is done, then the deeper levels'
+// the bulk shadow pass (level 0's shadow rays) on the side stream (or `stream`: launch_stream_levels) as soon as level 0 is done, then the deeper levels'
 // shadow rays, the wave-per-ray shadow walks, stream_resolve, and render_lanes, which only runs after a queue overflow.
 static int launch_frame(crt_ctx *ctx, const crt_options *o, uint32_t n_items, float *d_out, uint32_t packed, hipStream_t stream, bool last_resort) {
     const bool gi = o->use_gi != 0;  // the GI / multi-sample mode: rendered pixel by pixel by render_lanes<.., true> (kernel_lane.h)
@@ -526,7 +538,8 @@ static int launch_frame(crt_ctx *ctx, const crt_options *o, uint32_t n_items, fl
     // The walks' spill regions (kernel_bvh.h: bvh_stack_of), one per stream of a frame, because these launches may run side by side:
     //   bvh_spill        `stream`: bvh_trace_level0 / bvh_trace_shade* (lane_blocks or level_blocks <= grid_blocks workgroups), and behind
     //                    them bvh_trace_shadow<1> (lane_blocks), which uses the side region: pass 0 has ended by then (ev_s1)
-    //   bvh_spill_side   ctx->side: bvh_trace_shadow<0> (num_cus x side_blocks, at most grid_blocks) beside the levels and the queue
+    //   bvh_spill_side   ctx->side (`stream` behind level 0 on the one-stream path): bvh_trace_shadow<0> (num_cus x side_blocks, at most
+    //                    grid_blocks) beside the levels and the queue
     //   bvh_spill_queue  ctx->early (or `stream` behind level 0): bvh_trace_queue (at most lane_blocks), beside level 0 and pass 0; its
     //                    second launch runs behind the first on the same stream
     // Frames of one context follow one another on `stream`; a query has scratch of its own (crt_query.hip).
@@ -552,6 +565,7 @@ static int launch_frame(crt_ctx *ctx, const crt_options *o, uint32_t n_items, fl
         // nothing to render: the events still bracket an (empty) frame, so that every reader of a slot finds recorded events
         for (hipEvent_t e : {ctx->ev1[slot], ctx->ev_s0[slot], ctx->ev_s1[slot], ctx->ev_s2[slot], ctx->ev2[slot], ctx->ev3[slot], ctx->ev4[slot]})
             CRT_HIP_CHECK(ctx, hipEventRecord(e, stream));
+        ctx->slot_ev2_is_s1[slot] = false;
         ctx->launches++;
         return CRT_OK;
     }
@@ -592,7 +606,7 @@ static int launch_frame(crt_ctx *ctx, const crt_options *o, uint32_t n_items, fl
     A.s = (scene_args_p)ctx->d_scene;
     A.f = (frame_args_p)(ctx->d_frame_ring + slot);
     A.counters = ctx->d_counters;
-    FramePlan P{slot, n_items, vitems, lane_blocks, gi, count, exec_count, heavy, lean, wide, bvh, queue, widest, 0u, nullptr, last_resort};
+    FramePlan P{slot, n_items, vitems, lane_blocks, gi, count, exec_count, heavy, lean, wide, bvh, queue, widest, 0u, nullptr, last_resort, false};
     rc = stream_mode ? launch_stream_levels(ctx, o, P, A, stream) : launch_lanes_pass(ctx, P, A, stream);
     if (rc == CRT_OK && stream_mode) rc = launch_stream_tail(ctx, P, A, stream);
     if (rc) return rc;
@@ -603,6 +617,7 @@ static int launch_frame(crt_ctx *ctx, const crt_options *o, uint32_t n_items, fl
     else CRT_HIP_CHECK(ctx, hipMemcpyAsync(h + SC_FALLBACK_TOTAL, ctx->d_fallback_total, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     ctx->slot_items[slot] = stream_mode ? vitems : 0u;
     ctx->slot_cfg[slot] = frame_config_of(o);
+    ctx->slot_ev2_is_s1[slot] = P.one_stream;
     CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev3[slot], stream));
     CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev4[slot], stream));
     ctx->launches++;
