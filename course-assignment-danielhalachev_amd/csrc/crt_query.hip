@@ -9,11 +9,18 @@
 //                      the end of this file; crt_shoot_rays_gi*: the same loop for the GI build (a key per ray, sample rays at DIFFUSE
 //                      records, no mesh skipped by a shadow ray)
 // and their statistics (crt_get_query_stats, crt_get_shoot_stats).  A query reads the context's scene and nothing of its frames: the
-// scratch below is the queries' own.
+// scratch below is the queries' own.  The shape of the file:
+//   an entry point    query_entry: the preamble and the one argument check (query_check, told what the call needs by a CallCheck)
+//   a call            query_begin (the waiting rule: call_wait.h), then its launches between call_open and call_close
+//   its launches      query_launches: the filter / reroute pair of the call's kind from one table (PAIRS); clear_words clears every word
+//   a radiance pass   shoot_pass: shoot_down (level behind level), shoot_up, shoot_numbers.  The synchronous and the enqueue form part in
+//                     shoot_children (a level's room and size), clear_words and shoot_numbers -- and in shoot_up's choice of build --,
+//                     and nowhere in the level loop
 #include "crt_internal.h"
 #include "glibc_powf.h"
 #include "gi_random.h"
 #include "shoot_caps.h"
+#include "call_wait.h"
 
 static void query_scratch_changed(crt_ctx *ctx);   // (below crt_query_state)
 
@@ -64,6 +71,13 @@ struct DeviceArray {
         cap = 0;
     }
 };
+// reserve_all(ctx, a, n, b, m, ...): room for n elements in a, m in b, ...; the first failure ends it
+int reserve_all(crt_ctx *) { return CRT_OK; }
+template <typename T, typename... More>
+int reserve_all(crt_ctx *ctx, DeviceArray<T> &a, const uint64_t n, More &&...more) {
+    if (int rc = a.reserve(ctx, n)) return rc;
+    return reserve_all(ctx, more...);
+}
 
 // one recursion level of a radiance query: rays, their records, colours (level 0 writes the caller's array), status and nodes
 struct ShootLevel {
@@ -140,12 +154,22 @@ QueryCall call_part(QueryCall c, const uint64_t first, const uint64_t m) {
 //   * a call on ANOTHER stream waits for the open call's last launch (one on the same stream is ordered behind it, and supersedes its
 //     statistics);
 //   * any call after a radiance call waits for it: that one's statistics are read through the words this one is about to clear;
-//   * a radiance call after any call harvests that one first, for the same reason.
+//   * a radiance call after any call harvests that one first, for the same reason;
+//   * but an enqueue call behind an enqueue call on the same stream does not wait: that one's statistics come through a report of
+//     their own, not through the words.
+// call_waits (call_wait.h) is this rule, and query_begin asks nothing else.
 struct OpenCall {
-    bool open = false, radiance = false;
-    bool enqueue = false;   // a radiance call of the enqueue kind: its numbers are the report's (h_report), not h_shoot's
+    bool open = false;
+    CallKind kind = CALL_QUERY;   // CALL_ENQUEUE: its numbers are the report's (QueryPinned::report), not the SH_* slots'
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around its launches
+};
+
+// what comes back through pinned memory, in one block that query_begin makes with the rest of the scratch
+struct QueryPinned {
+    uint32_t words[QW_WORDS];   // the words of the last call, copied behind its last launch
+    uint64_t shoot[SH_SLOTS];   // SH_*
+    crt_shoot_report report;    // crt_query_state::d_report, copied behind the last launch of an enqueue call
 };
 
 }  // namespace
@@ -154,7 +178,7 @@ struct crt_query_state {
     DeviceArray<FrameArgs> frame;     // two frame blocks, all zero but for use_gi = 1 in the second: the reference-order walk reads use_gi
                                       // (0: shadow rays skip refractive meshes; 1, the levels of crt_shoot_rays_gi*: they skip none)
     DeviceArray<uint32_t> words;      // QW_*
-    uint32_t *h_words = nullptr;      // pinned: the words of the last call, copied behind its last launch
+    QueryPinned *pin = nullptr;
     DeviceArray<uint32_t> list;       // reroute list: follows the largest launch asked for
     DeviceArray<uint32_t> spill;      // walk-stack spill columns of the query grid (never FrameArgs::bvh_spill: a frame's kernels may run beside)
     OpenCall call;
@@ -173,18 +197,16 @@ struct crt_query_state {
     DeviceArray<crt_ray> shoot_in;    // the host variant's device copy of the caller's rays
     DeviceArray<uint32_t> shoot_keys; // ... and of the caller's keys (crt_shoot_rays_gi)
     DeviceArray<uint32_t> swords;     // SW_*
-    uint64_t *h_shoot = nullptr;      // pinned, SH_*
     crt_shoot_stats shoot{};          // of the last radiance call
     // crt_shoot_rays*_enqueue
     DeviceArray<crt_shoot_report> d_report;   // what radiance_report writes for the library's own statistics (outside a capture)
     DeviceArray<unsigned long long> d_hits0;  // level 0's hits: QW_HITS as the level's trace left it (the lighting launches add to that word)
-    crt_shoot_report *h_report = nullptr;     // pinned: d_report, copied behind the last launch
     crt_shoot_report report{};                // of the last enqueue call outside a capture
     uint64_t generation = 0;                  // crt_query_scratch_generation
+    // the radiance queries' own device words: made by the first radiance call of a context (shoot_words_reserve)
+    bool shoot_words_made() const { return swords.p && d_report.p && d_hits0.p; }
     ~crt_query_state() {
-        if (h_words) (void)hipHostFree(h_words);
-        if (h_shoot) (void)hipHostFree(h_shoot);
-        if (h_report) (void)hipHostFree(h_report);
+        if (pin) (void)hipHostFree(pin);
         if (call.ev0) (void)hipEventDestroy(call.ev0);
         if (call.ev1) (void)hipEventDestroy(call.ev1);
     }
@@ -201,9 +223,9 @@ void query_destroy(crt_ctx *ctx) {
 
 // a radiance pass's numbers, once its last copy has arrived
 static void shoot_fold(crt_query_state *q) {
-    q->stats.hits += q->h_shoot[SH_HITS0];
-    q->shoot.shadow_records += q->h_shoot[SH_DIFFUSE];
-    q->shoot.rerouted += q->h_shoot[SH_REROUTED];
+    q->stats.hits += q->pin->shoot[SH_HITS0];
+    q->shoot.shadow_records += q->pin->shoot[SH_DIFFUSE];
+    q->shoot.rerouted += q->pin->shoot[SH_REROUTED];
 }
 
 // the words and events of the open call, once: waits for it
@@ -214,10 +236,10 @@ static int query_harvest(crt_ctx *ctx) {
     q->call.open = false;
     float ms = 0;
     CRT_HIP_CHECK(ctx, hipEventElapsedTime(&ms, q->call.ev0, q->call.ev1));
-    if (q->call.radiance) {   // its last pass's numbers, and what crt_get_query_stats says of it
+    if (q->call.kind != CALL_QUERY) {   // its last pass's numbers, and what crt_get_query_stats says of it
         q->shoot.kernel_ms = ms;
-        if (q->call.enqueue) {   // (one pass, and the device has done the sums)
-            q->report = *q->h_report;
+        if (q->call.kind == CALL_ENQUEUE) {   // (one pass, and the device has done the sums)
+            q->report = q->pin->report;
             q->shoot.levels = q->report.levels;
             memcpy(q->shoot.level_rays, q->report.level_rays, sizeof(q->shoot.level_rays));
             q->shoot.shadow_records = q->report.shadow_records;
@@ -228,8 +250,8 @@ static int query_harvest(crt_ctx *ctx) {
         q->stats.kernel_ms = q->shoot.kernel_ms;
     } else {
         q->stats.kernel_ms += ms;
-        memcpy(&q->stats.hits, q->h_words + QW_HITS, sizeof(uint64_t));          // (totals of the call: its launches add to the same words)
-        memcpy(&q->stats.rerouted, q->h_words + QW_REROUTED, sizeof(uint64_t));
+        memcpy(&q->stats.hits, q->pin->words + QW_HITS, sizeof(uint64_t));          // (totals of the call: its launches add to the same words)
+        memcpy(&q->stats.rerouted, q->pin->words + QW_REROUTED, sizeof(uint64_t));
     }
     return CRT_OK;
 }
@@ -237,7 +259,7 @@ static int query_harvest(crt_ctx *ctx) {
 static bool uses_filter(const crt_ctx *ctx) { return ctx->scene.bvh_ok && ctx->tuning.bvh; }
 
 // before a call on `stream`: the waiting rules (OpenCall), and what every query needs, allocated by the first one
-static int query_begin(crt_ctx *ctx, hipStream_t stream, bool radiance, bool enqueue = false) {
+static int query_begin(crt_ctx *ctx, hipStream_t stream, const CallKind kind) {
     if (ctx->pending) {
         int rc = crt_wait(ctx);
         if (rc) return rc;
@@ -246,25 +268,42 @@ static int query_begin(crt_ctx *ctx, hipStream_t stream, bool radiance, bool enq
     if (!ctx->query) ctx->query = new (std::nothrow) crt_query_state;
     crt_query_state *q = ctx->query;
     if (!q) { ctx->error = "out of memory"; return CRT_ERR_NOMEM; }
-    if (!q->h_words) {
-        int rc;
-        if ((rc = q->frame.reserve(ctx, 2)) || (rc = q->words.reserve(ctx, QW_WORDS))) return rc;
+    if (!q->pin) {
+        if (int rc = reserve_all(ctx, q->frame, 2, q->words, QW_WORDS)) return rc;
         CRT_HIP_CHECK(ctx, hipMemset(q->frame.p, 0, 2 * sizeof(FrameArgs)));
         const uint32_t one = 1u;
         CRT_HIP_CHECK(ctx, hipMemcpy(&q->frame.p[1].use_gi, &one, sizeof(one), hipMemcpyHostToDevice));
         // one region: every filter launch of a query (query_walk / query_direct, the levels of crt_shoot_rays* among them) has at most
         // grid_blocks workgroups and follows the previous one on ONE stream (a call on another stream, and a pending frame, are waited
         // for first): no two of them run side by side
-        if ((rc = q->spill.reserve(ctx, ctx->bvh_spill_words()))) return rc;
+        if (int rc = q->spill.reserve(ctx, ctx->bvh_spill_words())) return rc;
         if (!q->call.ev0) CRT_HIP_CHECK(ctx, hipEventCreate(&q->call.ev0));
         if (!q->call.ev1) CRT_HIP_CHECK(ctx, hipEventCreate(&q->call.ev1));
-        CRT_HIP_CHECK(ctx, hipHostMalloc((void **)&q->h_words, QW_WORDS * sizeof(uint32_t)));
-        memset(q->h_words, 0, QW_WORDS * sizeof(uint32_t));
+        CRT_HIP_CHECK(ctx, hipHostMalloc((void **)&q->pin, sizeof(QueryPinned)));
+        memset(q->pin, 0, sizeof(QueryPinned));
     }
-    // (an enqueue call behind an enqueue call on the same stream is ordered behind it and supersedes its statistics, which come through
-    // a report of their own, not through the words: no wait)
-    if (q->call.open && enqueue && q->call.radiance && q->call.enqueue && q->call.stream == stream) return CRT_OK;
-    if (q->call.open && (q->call.stream != stream || q->call.radiance || radiance)) return query_harvest(ctx);
+    return call_waits(q->call.open, q->call.kind, kind, q->call.stream == stream) ? query_harvest(ctx) : CRT_OK;
+}
+
+// A call's bracket.  call_open: the statistics of a call of `kind` for n rays start again (`first` false: a later round trip of a host
+// variant adds to them) and ev0 is recorded; call_close: ev1 behind the last launch, and the call is the open one.
+static int call_open(crt_ctx *ctx, const CallKind kind, const uint64_t n, hipStream_t stream, const bool first = true) {
+    crt_query_state *q = ctx->query;
+    if (first) q->stats = crt_query_stats{};
+    q->stats.rays += n;
+    if (kind != CALL_QUERY) {
+        q->shoot = crt_shoot_stats{};
+        q->shoot.rays = n;
+    }
+    CRT_HIP_CHECK(ctx, hipEventRecord(q->call.ev0, stream));
+    return CRT_OK;
+}
+static int call_close(crt_ctx *ctx, const CallKind kind, hipStream_t stream) {
+    OpenCall &call = ctx->query->call;
+    CRT_HIP_CHECK(ctx, hipEventRecord(call.ev1, stream));
+    call.stream = stream;
+    call.kind = kind;
+    call.open = true;
     return CRT_OK;
 }
 
@@ -280,17 +319,50 @@ static void launch_reset(uint32_t *a, uint32_t na, uint32_t *b, uint32_t nb, con
     hipLaunchKernelGGL(query_reset, dim3(1), dim3(BLOCK), 0, stream, P);
 }
 
-template <typename Args>
-static hipError_t launch_pair(void (*filter)(KernelArgs, Args), void (*reroute)(KernelArgs, Args), bool use_filter, uint32_t blocks, hipStream_t stream,
-                              const KernelArgs &A, const Args &args) {
+// The one way to clear counter words: a[0 .. na) and b[0 .. nb) (nb 0: none) become zero, by hipMemsetAsync -- or, `kernels_only` (an
+// enqueue call, which a graph must be able to capture as a single chain of kernels), by query_reset.
+static int clear_words(crt_ctx *ctx, uint32_t *a, uint32_t na, uint32_t *b, uint32_t nb, const bool kernels_only, hipStream_t stream) {
+    if (kernels_only) {
+        launch_reset(a, na, b, nb, nullptr, nullptr, stream);
+        CRT_HIP_CHECK(ctx, hipGetLastError());
+        return CRT_OK;
+    }
+    CRT_HIP_CHECK(ctx, hipMemsetAsync(a, 0, na * sizeof(uint32_t), stream));
+    if (nb) CRT_HIP_CHECK(ctx, hipMemsetAsync(b, 0, nb * sizeof(uint32_t), stream));
+    return CRT_OK;
+}
+
+// a filter / reroute kernel pair, launched: the ray queries' arguments are the first member of the lighting queries'
+static const QueryArgs &pair_args(const ShadeArgs &S, void (*)(KernelArgs, QueryArgs)) { return S.q; }
+static const ShadeArgs &pair_args(const ShadeArgs &S, void (*)(KernelArgs, ShadeArgs)) { return S; }
+template <auto FILTER, auto REROUTE>
+static hipError_t launch_pair(bool use_filter, uint32_t blocks, hipStream_t stream, const KernelArgs &A, const ShadeArgs &S) {
     if (use_filter) {
-        hipLaunchKernelGGL(filter, dim3(blocks), dim3(BLOCK), 0, stream, A, args);
+        hipLaunchKernelGGL(FILTER, dim3(blocks), dim3(BLOCK), 0, stream, A, pair_args(S, FILTER));
         if (hipError_t e = hipGetLastError()) return e;
     }
     // behind it, for what it listed (all but always nothing: the workgroups leave at once) -- or for everything
-    hipLaunchKernelGGL(reroute, dim3(blocks), dim3(BLOCK), 0, stream, A, args);
+    hipLaunchKernelGGL(REROUTE, dim3(blocks), dim3(BLOCK), 0, stream, A, pair_args(S, REROUTE));
     return hipGetLastError();
 }
+using PairLaunch = hipError_t (*)(bool, uint32_t, hipStream_t, const KernelArgs &, const ShadeArgs &);
+template <bool OCCLUDED, bool DEVN>
+constexpr PairLaunch WALK = launch_pair<query_walk<BVH_PLAIN, OCCLUDED, DEVN>, query_reroute<OCCLUDED, DEVN>>;
+template <bool POINTS, bool EVERY, bool DEVN>
+constexpr PairLaunch DIRECT = launch_pair<query_direct<BVH_PLAIN, POINTS, EVERY, DEVN>, query_direct_reroute<POINTS, DEVN>>;
+// Kernel choice: [QueryKind; 4: Q_SHADE_HITS by the GI build's occlusion rule (every_mesh)][the DEVN build: the level's size is a device
+// word, crt_shoot_rays*_enqueue].  Null: no such build.
+static const PairLaunch PAIRS[5][2] = {{WALK<false, false>, WALK<false, true>},
+                                       {WALK<true, false>, nullptr},
+                                       {DIRECT<false, false, false>, DIRECT<false, false, true>},
+                                       {DIRECT<true, false, false>, nullptr},
+                                       {DIRECT<false, true, false>, DIRECT<false, true, true>}};
+// ... and the radiance queries' own kernels: [GI], [GI][DEVN]
+static void (*const PREPARE[2])(RadianceArgs) = {radiance_prepare<false>, radiance_prepare<true>};
+static void (*const SCATTER[2][2])(KernelArgs, RadianceArgs) = {{radiance_scatter<false>, radiance_scatter<false, true>},
+                                                                {radiance_scatter<true>, radiance_scatter<true, true>}};
+static void (*const COMBINE[2][2])(KernelArgs, RadianceArgs) = {{radiance_combine<false>, radiance_combine<false, true>},
+                                                                {radiance_combine<true>, radiance_combine<true, true>}};
 
 // the launches of a call's rays or records, at most query_launch_rays at a time, on the scratch query_begin and query_list_reserve have made; `clean`: the cursors
 // and the list's length are zero already
@@ -300,15 +372,15 @@ static int query_launches(crt_ctx *ctx, const QueryCall &C, hipStream_t stream, 
     A.s = (scene_args_p)ctx->d_scene;
     A.f = (frame_args_p)(q->frame.p + (C.every_mesh ? 1 : 0));   // all zero but for use_gi (0: shadow rays skip refractive meshes); the bias travels in ShadeArgs
     const bool filter = uses_filter(ctx);
+    const PairLaunch launch = PAIRS[C.kind == Q_SHADE_HITS && C.every_mesh ? 4 : C.kind][C.d_count ? 1 : 0];
+    if (!launch) CRT_HIP_CHECK(ctx, hipErrorInvalidValue);
     // (an enqueue call grows nothing inside a capture: its parts are what the reroute list holds)
     const uint64_t part = C.d_count && filter ? std::min<uint64_t>(ctx->query_launch_rays, q->list.cap) : ctx->query_launch_rays;
     if (part == 0) { ctx->error = "query_launches: no reroute list"; return CRT_ERR_INVALID; }
     for (uint64_t done = 0; done < C.n; done += part) {
         const QueryCall c = call_part(C, done, std::min(C.n - done, part));
-        if ((done || !clean) && C.kernels_only) {
-            launch_reset(q->words.p, QW_HITS, nullptr, 0, nullptr, nullptr, stream);
-            CRT_HIP_CHECK(ctx, hipGetLastError());
-        } else if (done || !clean) CRT_HIP_CHECK(ctx, hipMemsetAsync(q->words.p, 0, QW_HITS * sizeof(uint32_t), stream));   // cursors and list length; the totals stay
+        if (done || !clean)   // cursors and list length; the totals stay
+            if (int rc = clear_words(ctx, q->words.p, QW_HITS, nullptr, 0, C.kernels_only, stream)) return rc;
         ShadeArgs S{};   // (the ray queries' arguments are its first member)
         QueryArgs &Q = S.q;
         Q.n = (uint32_t)c.n;
@@ -321,71 +393,46 @@ static int query_launches(crt_ctx *ctx, const QueryCall &C, hipStream_t stream, 
         Q.count = c.d_count; Q.first = c.count_first;
         S.hits = c.records; S.points = c.points; S.normals = c.normals; S.out = c.out; S.status = c.status; S.shadow_bias = c.shadow_bias;
         const uint32_t blocks = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(ctx->grid_blocks, (c.n + BLOCK - 1) / BLOCK));
-        hipError_t e = hipSuccess;
-        if (c.d_count) {   // the DEVN builds: the levels of crt_shoot_rays*_enqueue
-            if (c.kind == Q_CLOSEST) e = launch_pair(query_walk<BVH_PLAIN, false, true>, query_reroute<false, true>, filter, blocks, stream, A, Q);
-            else if (c.kind != Q_SHADE_HITS) e = hipErrorInvalidValue;
-            else if (c.every_mesh) e = launch_pair(query_direct<BVH_PLAIN, false, true, true>, query_direct_reroute<false, true>, filter, blocks, stream, A, S);
-            else e = launch_pair(query_direct<BVH_PLAIN, false, false, true>, query_direct_reroute<false, true>, filter, blocks, stream, A, S);
-        } else switch (c.kind) {
-            case Q_CLOSEST: e = launch_pair(query_walk<BVH_PLAIN, false>, query_reroute<false>, filter, blocks, stream, A, Q); break;
-            case Q_OCCLUDED: e = launch_pair(query_walk<BVH_PLAIN, true>, query_reroute<true>, filter, blocks, stream, A, Q); break;
-            case Q_SHADE_HITS:
-                e = c.every_mesh ? launch_pair(query_direct<BVH_PLAIN, false, true>, query_direct_reroute<false>, filter, blocks, stream, A, S)
-                                 : launch_pair(query_direct<BVH_PLAIN, false>, query_direct_reroute<false>, filter, blocks, stream, A, S);
-                break;
-            case Q_LIGHT_POINTS: e = launch_pair(query_direct<BVH_PLAIN, true>, query_direct_reroute<true>, filter, blocks, stream, A, S); break;
-        }
-        CRT_HIP_CHECK(ctx, e);
+        CRT_HIP_CHECK(ctx, launch(filter, blocks, stream, A, S));
     }
     return CRT_OK;
 }
 
 // one device call; `first`: the call's counters start at zero (the host variants make one call of every round trip)
 static int query_run(crt_ctx *ctx, const QueryCall &C, hipStream_t stream, bool first) {
-    int rc = query_begin(ctx, stream, false);
+    int rc = query_begin(ctx, stream, CALL_QUERY);
     if (rc) return rc;
     crt_query_state *q = ctx->query;
     if ((rc = query_list_reserve(ctx, C.n))) return rc;
-    if (first) {
-        q->stats = crt_query_stats{};
-        CRT_HIP_CHECK(ctx, hipMemsetAsync(q->words.p, 0, QW_WORDS * sizeof(uint32_t), stream));
-    }
-    q->stats.rays += C.n;
-    CRT_HIP_CHECK(ctx, hipEventRecord(q->call.ev0, stream));
-    rc = query_launches(ctx, C, stream, first);
-    if (rc) return rc;
-    CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_words, q->words.p, QW_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    CRT_HIP_CHECK(ctx, hipEventRecord(q->call.ev1, stream));
-    q->call.stream = stream;
-    q->call.radiance = q->call.enqueue = false;
-    q->call.open = true;
-    return CRT_OK;
+    if (first && (rc = clear_words(ctx, q->words.p, QW_WORDS, nullptr, 0, false, stream))) return rc;
+    if ((rc = call_open(ctx, CALL_QUERY, C.n, stream, first)) || (rc = query_launches(ctx, C, stream, first))) return rc;
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->pin->words, q->words.p, QW_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    return call_close(ctx, CALL_QUERY, stream);
 }
 
 // The host variants: H holds the caller's host arrays.  Copy in, run, copy out, query_host_rays at a time, through the family's device
 // copies, which are kept for the next call.
 static int query_host(crt_ctx *ctx, const QueryCall &H) {
-    int rc = query_begin(ctx, ctx->stream, false);
+    int rc = query_begin(ctx, ctx->stream, CALL_QUERY);
     if (rc) return rc;
     crt_query_state *q = ctx->query;
     const uint64_t cap = std::min(H.n, ctx->query_host_rays);
     QueryCall D = H;   // the same call on the device copies
     switch (H.kind) {
         case Q_CLOSEST:
-            if ((rc = q->s_rays.reserve(ctx, cap)) || (rc = q->s_hits.reserve(ctx, cap))) return rc;
+            if ((rc = reserve_all(ctx, q->s_rays, cap, q->s_hits, cap))) return rc;
             D.rays = q->s_rays.p; D.hits = q->s_hits.p;
             break;
         case Q_OCCLUDED:
-            if ((rc = q->s_rays.reserve(ctx, cap)) || (rc = q->s_dist.reserve(ctx, cap)) || (rc = q->s_occ.reserve(ctx, cap))) return rc;
+            if ((rc = reserve_all(ctx, q->s_rays, cap, q->s_dist, cap, q->s_occ, cap))) return rc;
             D.rays = q->s_rays.p; D.max_distance = q->s_dist.p; D.occluded = q->s_occ.p;
             break;
         case Q_SHADE_HITS:
-            if ((rc = q->s_records.reserve(ctx, cap)) || (rc = q->s_rgb.reserve(ctx, 3 * cap)) || (rc = q->s_status.reserve(ctx, cap))) return rc;
+            if ((rc = reserve_all(ctx, q->s_records, cap, q->s_rgb, 3 * cap, q->s_status, cap))) return rc;
             D.records = q->s_records.p; D.out = q->s_rgb.p; D.status = q->s_status.p;
             break;
         case Q_LIGHT_POINTS:
-            if ((rc = q->s_points.reserve(ctx, 3 * cap)) || (rc = q->s_normals.reserve(ctx, 3 * cap)) || (rc = q->s_sums.reserve(ctx, cap))) return rc;
+            if ((rc = reserve_all(ctx, q->s_points, 3 * cap, q->s_normals, 3 * cap, q->s_sums, cap))) return rc;
             D.points = q->s_points.p; D.normals = q->s_normals.p; D.out = q->s_sums.p;
             break;
     }
@@ -411,85 +458,104 @@ static int query_host(crt_ctx *ctx, const QueryCall &H) {
     return CRT_OK;
 }
 
-static int query_check(crt_ctx *ctx, const void *rays, const void *extra, const void *out, uint32_t ray_type, const char *what) {
-    if (!rays || !extra || !out) { ctx->error = std::string(what) + ": NULL array with n > 0"; return CRT_ERR_INVALID; }
-    if (ray_type > (uint32_t)CRT_RAY_REFRACTION) { ctx->error = std::string(what) + ": unknown ray_type " + std::to_string(ray_type); return CRT_ERR_INVALID; }
+// rays of level g + 1 for each ray of level g of a radiance query, at most
+static uint64_t shoot_fan(const crt_options *o, const bool gi) { return gi ? std::max(2u, o->gi_sample_size) : 2u; }
+
+// GI: the rays of one pass -- as many as keep the worst-case deepest level (every hit of every level DIFFUSE) at SHOOT_GI_DEEPEST_RAYS,
+// between 64 and shoot_pass_rays; 0 when 64 rays do not fit.  *product: max(2, gi_sample_size)^max_depth (saturated above the bound).
+static uint64_t shoot_gi_pass_rays(const crt_ctx *ctx, const crt_options *o, uint64_t *product) {
+    const uint64_t fan = shoot_fan(o, true);   // (<= 64: the product below stays under 2^33)
+    uint64_t p = 1;
+    for (uint32_t d = 0; d < o->max_depth && p <= SHOOT_GI_DEEPEST_RAYS; d++) p *= fan;
+    *product = p;
+    if (64u * p > SHOOT_GI_DEEPEST_RAYS) return 0;
+    return std::min(std::max<uint64_t>(SHOOT_GI_DEEPEST_RAYS / p, 64u), ctx->shoot_pass_rays);
+}
+
+// What a call needs of its arguments: the one check of every entry point that takes n > 0 rays or records.
+struct CallCheck {
+    const char *what;             // the entry point
+    const void *p[3];             // its arrays, and its options where it cannot do without them: none may be NULL
+    uint32_t ray_type;            // one of crt_ray_type (CRT_RAY_SHADOW where the call takes none)
+    const crt_options *options;   // or null: nothing of them is looked at.  use_gi must be 0 ...
+    bool radiance;                // crt_shoot_rays*: max_depth + 1 levels must exist
+    bool gi;                      // crt_shoot_rays_gi*: ... no: use_gi must be 1, and gi_sample_size a frame's
+    uint64_t *pass;               // crt_shoot_rays_gi*, or null: the rays of one pass are wanted, and 64 of them must fit
+};
+static int query_check(crt_ctx *ctx, const CallCheck &k) {
+    const auto refuse = [&](const std::string &why) {
+        ctx->error = std::string(k.what) + ": " + why;
+        return (int)CRT_ERR_INVALID;
+    };
+    const crt_options *o = k.options;
+    if (!k.p[0] || !k.p[1] || !k.p[2]) return refuse(k.radiance ? "NULL array or options with n > 0" : "NULL array with n > 0");
+    if (k.ray_type > (uint32_t)CRT_RAY_REFRACTION) return refuse("unknown ray_type " + std::to_string(k.ray_type));
+    if (o && o->use_gi && !k.gi)
+        return refuse(std::string("use_gi is not offered (the GI build's ") + (k.radiance ? "random sample rays, its " : "") +
+                      "occlusion rule and its division by GI_SAMPLE_SIZE + 1)");
+    if (k.gi && !o->use_gi) return refuse("use_gi is 0: the deterministic build's colours are crt_shoot_rays' (crt_shoot_rays_device's)");
+    if (k.gi && o->gi_sample_size > 64u)   // (a frame's rule: crt_launch.hip)
+        return refuse("gi_sample_size too large: " + std::to_string(o->gi_sample_size) + ", at most 64");
+    if (k.radiance && (uint64_t)o->max_depth + 1 > (uint64_t)MAX_GENERATIONS)   // (a frame's rule as well)
+        return refuse("max_depth too large: " + std::to_string(o->max_depth) + " + 1 levels, at most " + std::to_string(MAX_GENERATIONS));
+    if (!k.pass) return CRT_OK;   // (crt_shoot_rays_gi_enqueue asks for none: one pass, whose levels the capacities bound)
+    uint64_t product = 0;
+    *k.pass = shoot_gi_pass_rays(ctx, o, &product);
+    if (*k.pass == 0)
+        return refuse("the deepest level of a pass of 64 rays may hold 64 x max(2, gi_sample_size)^max_depth = 64 x " + std::to_string(shoot_fan(o, true)) +
+                      "^" + std::to_string(o->max_depth) + (product > SHOOT_GI_DEEPEST_RAYS ? " > 64 x 2^26" : " = " + std::to_string(64u * product)) +
+                      " rays, more than 2^26");
     return CRT_OK;
 }
 
-static int shade_check(crt_ctx *ctx, const void *a, const void *b, const void *out, const crt_options *options, const char *what) {
-    if (!a || !b || !out) { ctx->error = std::string(what) + ": NULL array with n > 0"; return CRT_ERR_INVALID; }
-    if (options && options->use_gi) {
-        ctx->error = std::string(what) + ": use_gi is not offered (the GI build's occlusion rule and its division by GI_SAMPLE_SIZE + 1)";
-        return CRT_ERR_INVALID;
-    }
-    return CRT_OK;
+// the preamble of those entry points: no context is an error, no rays are no work; then the check, then the call
+template <typename Run>
+static int query_entry(crt_ctx *ctx, const uint64_t n, const CallCheck &k, Run &&run) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    if (int rc = query_check(ctx, k)) return rc;
+    return run();
 }
 
 extern "C" int crt_trace_rays_device(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, crt_hit *d_out, void *stream) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
-    int rc = query_check(ctx, d_rays, d_rays, d_out, ray_type, "crt_trace_rays_device");
-    if (rc) return rc;
-    return query_run(ctx, closest_call(d_rays, n, ray_type, d_out), (hipStream_t)stream, true);
+    return query_entry(ctx, n, {"crt_trace_rays_device", {d_rays, d_rays, d_out}, ray_type},
+                       [&] { return query_run(ctx, closest_call(d_rays, n, ray_type, d_out), (hipStream_t)stream, true); });
 }
 
 extern "C" int crt_occluded_rays_device(crt_ctx *ctx, const crt_ray *d_rays, const float *d_max_distance, uint64_t n, uint8_t *d_out, void *stream) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
-    int rc = query_check(ctx, d_rays, d_max_distance, d_out, CRT_RAY_SHADOW, "crt_occluded_rays_device");
-    if (rc) return rc;
-    return query_run(ctx, occluded_call(d_rays, d_max_distance, n, d_out), (hipStream_t)stream, true);
+    return query_entry(ctx, n, {"crt_occluded_rays_device", {d_rays, d_max_distance, d_out}, CRT_RAY_SHADOW},
+                       [&] { return query_run(ctx, occluded_call(d_rays, d_max_distance, n, d_out), (hipStream_t)stream, true); });
 }
 
 extern "C" int crt_trace_rays(crt_ctx *ctx, const crt_ray *rays, uint64_t n, uint32_t ray_type, crt_hit *out) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
-    int rc = query_check(ctx, rays, rays, out, ray_type, "crt_trace_rays");
-    if (rc) return rc;
-    return query_host(ctx, closest_call(rays, n, ray_type, out));
+    return query_entry(ctx, n, {"crt_trace_rays", {rays, rays, out}, ray_type}, [&] { return query_host(ctx, closest_call(rays, n, ray_type, out)); });
 }
 
 extern "C" int crt_occluded_rays(crt_ctx *ctx, const crt_ray *rays, const float *max_distance, uint64_t n, uint8_t *out) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
-    int rc = query_check(ctx, rays, max_distance, out, CRT_RAY_SHADOW, "crt_occluded_rays");
-    if (rc) return rc;
-    return query_host(ctx, occluded_call(rays, max_distance, n, out));
+    return query_entry(ctx, n, {"crt_occluded_rays", {rays, max_distance, out}, CRT_RAY_SHADOW},
+                       [&] { return query_host(ctx, occluded_call(rays, max_distance, n, out)); });
 }
 
 extern "C" int crt_shade_hits_device(crt_ctx *ctx, const crt_hit *d_hits, uint64_t n, const crt_options *options, float *d_rgb, uint8_t *d_status,
                                      void *stream) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
-    int rc = shade_check(ctx, d_hits, options, d_rgb, options, "crt_shade_hits_device");
-    if (rc) return rc;
-    return query_run(ctx, shade_call(d_hits, n, options->shadow_bias, d_rgb, d_status), (hipStream_t)stream, true);
+    return query_entry(ctx, n, {"crt_shade_hits_device", {d_hits, options, d_rgb}, CRT_RAY_SHADOW, options},
+                       [&] { return query_run(ctx, shade_call(d_hits, n, options->shadow_bias, d_rgb, d_status), (hipStream_t)stream, true); });
 }
 
 extern "C" int crt_light_points_device(crt_ctx *ctx, const float *d_points, const float *d_normals, uint64_t n, float shadow_bias, float *d_out,
                                        void *stream) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
-    int rc = shade_check(ctx, d_points, d_normals, d_out, nullptr, "crt_light_points_device");
-    if (rc) return rc;
-    return query_run(ctx, points_call(d_points, d_normals, n, shadow_bias, d_out), (hipStream_t)stream, true);
+    return query_entry(ctx, n, {"crt_light_points_device", {d_points, d_normals, d_out}, CRT_RAY_SHADOW},
+                       [&] { return query_run(ctx, points_call(d_points, d_normals, n, shadow_bias, d_out), (hipStream_t)stream, true); });
 }
 
 extern "C" int crt_shade_hits(crt_ctx *ctx, const crt_hit *hits, uint64_t n, const crt_options *options, float *out_rgb, uint8_t *out_status) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
-    int rc = shade_check(ctx, hits, options, out_rgb, options, "crt_shade_hits");
-    if (rc) return rc;
-    return query_host(ctx, shade_call(hits, n, options->shadow_bias, out_rgb, out_status));
+    return query_entry(ctx, n, {"crt_shade_hits", {hits, options, out_rgb}, CRT_RAY_SHADOW, options},
+                       [&] { return query_host(ctx, shade_call(hits, n, options->shadow_bias, out_rgb, out_status)); });
 }
 
 extern "C" int crt_light_points(crt_ctx *ctx, const float *points, const float *normals, uint64_t n, float shadow_bias, float *out) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
-    int rc = shade_check(ctx, points, normals, out, nullptr, "crt_light_points");
-    if (rc) return rc;
-    return query_host(ctx, points_call(points, normals, n, shadow_bias, out));
+    return query_entry(ctx, n, {"crt_light_points", {points, normals, out}, CRT_RAY_SHADOW},
+                       [&] { return query_host(ctx, points_call(points, normals, n, shadow_bias, out)); });
 }
 
 extern "C" int crt_camera_rays_device(crt_ctx *ctx, crt_ray *d_rays, void *stream) {
@@ -507,15 +573,19 @@ extern "C" int crt_camera_rays_device(crt_ctx *ctx, crt_ray *d_rays, void *strea
     return CRT_OK;
 }
 
-extern "C" int crt_get_query_stats(crt_ctx *ctx, crt_query_stats *out) {
+// the statistics of the last call, harvested first
+template <typename T>
+static int stats_of(crt_ctx *ctx, T *out, T crt_query_state::*member) {
     if (!ctx || !out) return CRT_ERR_INVALID;
-    if (!ctx->query) { *out = crt_query_stats{}; return CRT_OK; }
+    if (!ctx->query) { *out = T{}; return CRT_OK; }
     CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    int rc = query_harvest(ctx);
-    if (rc) return rc;
-    *out = ctx->query->stats;
+    if (int rc = query_harvest(ctx)) return rc;
+    *out = ctx->query->*member;
     return CRT_OK;
 }
+extern "C" int crt_get_query_stats(crt_ctx *ctx, crt_query_stats *out) { return stats_of(ctx, out, &crt_query_state::stats); }
+extern "C" int crt_get_shoot_stats(crt_ctx *ctx, crt_shoot_stats *out) { return stats_of(ctx, out, &crt_query_state::shoot); }
+extern "C" int crt_get_shoot_report(crt_ctx *ctx, crt_shoot_report *out) { return stats_of(ctx, out, &crt_query_state::report); }
 
 // ---- radiance queries (csrc/kernel_radiance.h): RayTracer::shootRay for the caller's rays, level-synchronous.  For level g = 0 ..
 // max_depth: trace the level's rays and light their records (query_launches, twice: background, constant and diffuse records are
@@ -531,27 +601,10 @@ struct ShootGi {
     uint32_t key_first;       // the index in the call of the pass's first ray
 };
 
-// rays of level g + 1 for each ray of level g, at most
-static uint64_t shoot_fan(const crt_options *o, const bool gi) { return gi ? std::max(2u, o->gi_sample_size) : 2u; }
-
-// GI: the rays of one pass -- as many as keep the worst-case deepest level (every hit of every level DIFFUSE) at SHOOT_GI_DEEPEST_RAYS,
-// between 64 and shoot_pass_rays; 0 when 64 rays do not fit.  *product: max(2, gi_sample_size)^max_depth (saturated above the bound).
-static uint64_t shoot_gi_pass_rays(const crt_ctx *ctx, const crt_options *o, uint64_t *product) {
-    const uint64_t fan = shoot_fan(o, true);   // (<= 64: the product below stays under 2^33)
-    uint64_t p = 1;
-    for (uint32_t d = 0; d < o->max_depth && p <= SHOOT_GI_DEEPEST_RAYS; d++) p *= fan;
-    *product = p;
-    if (64u * p > SHOOT_GI_DEEPEST_RAYS) return 0;
-    return std::min(std::max<uint64_t>(SHOOT_GI_DEEPEST_RAYS / p, 64u), ctx->shoot_pass_rays);
-}
-
 // room for `cap` rays at level g (`own_rgb`: with colours of its own; level 0 writes the caller's array; `keys`: a GI call)
 static int shoot_level_reserve(crt_ctx *ctx, const uint32_t g, const uint64_t cap, const bool own_rgb, const bool keys) {
     ShootLevel &L = ctx->query->lv[g];
-    int rc;
-    if ((rc = L.rays.reserve(ctx, cap)) || (rc = L.hits.reserve(ctx, cap)) || (rc = L.status.reserve(ctx, cap)) || (rc = L.nodes.reserve(ctx, 2 * cap))) return rc;
-    if (keys && (rc = L.keys.reserve(ctx, cap))) return rc;
-    return own_rgb ? L.rgb.reserve(ctx, 3 * cap) : CRT_OK;
+    return reserve_all(ctx, L.rays, cap, L.hits, cap, L.status, cap, L.nodes, 2 * cap, L.keys, keys ? cap : 0, L.rgb, own_rgb ? 3 * cap : 0);
 }
 
 // what crt_shoot_rays*_enqueue adds to a pass's arguments (null: the host reads every level's size back): the levels' capacities, in
@@ -562,221 +615,184 @@ struct ShootDev {
     bool capturing;                  // the stream is being captured: the library's own copy of the report is not made
 };
 
-// one pass: m rays of the caller's (at most shoot_pass_rays, or what shoot_gi_pass_rays allows), every level of them; leaves the pass's
-// numbers on their way to h_shoot (dev: to h_report)
-static int shoot_pass(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t m, const uint32_t ray_type, const crt_options *o, float *d_rgb,
-                      hipStream_t stream, const ShootGi *gi, const ShootDev *dev = nullptr) {
+// A level as its launches see it: n rays -- exactly; or, `count` not null, at most, and that device word says how many (the launches
+// are the DEVN builds, sized for what the level may hold).  Level 0's size is the caller's: its launches are those of the other calls.
+struct LevelSize { uint32_t n; const uint32_t *count; };
+
+// One pass: m rays of the caller's (at most shoot_pass_rays, or what shoot_gi_pass_rays allows) and every level of them; level 0's
+// room is the caller's business.  Leaves the pass's numbers on their way to the pinned SH_* slots (dev: to the pinned report).
+struct ShootPass {
+    const crt_ray *d_rays; uint32_t m, ray_type; const crt_options *o; float *d_rgb; hipStream_t stream;
+    const ShootGi *gi;                       // or null
+    const ShootDev *dev;                     // or null
+    KernelArgs A;                            // (shoot_pass fills in what follows)
+    bool kernels_only;                       // how words are cleared (clear_words), by the levels' launches as well
+    LevelSize level[MAX_GENERATIONS + 1];    // the down-sweep's: levels 0 .. last, and {0, null} behind them
+    uint32_t last;
+};
+
+// Where a pass's numbers go -- the ONE place that tells: through the pinned SH_* slots, which shoot_fold adds up, or (dev) into
+// radiance_report's sums and their copy.  `level0`: level 0's hits, QW_HITS as its trace left it (the lighting launches add to that
+// word); else the rest, behind the up-sweep.
+static int shoot_numbers(crt_ctx *ctx, const ShootPass &P, const bool level0) {
     crt_query_state *q = ctx->query;
-    KernelArgs A{};
-    A.s = (scene_args_p)ctx->d_scene;
-    A.f = (frame_args_p)q->frame.p;
-    const uint64_t fan = shoot_fan(o, gi != nullptr);
-    if (dev) {   // (kernel launches alone: shoot_enqueue)
-        launch_reset(q->words.p, QW_WORDS, q->swords.p, SW_WORDS, nullptr, nullptr, stream);
+    const auto hits = reinterpret_cast<const unsigned long long *>(q->words.p + QW_HITS), diffuse = reinterpret_cast<const unsigned long long *>(q->swords.p + SW_DIFFUSE);
+    if (!P.dev) {
+        if (level0) {
+            CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->pin->shoot + SH_HITS0, hits, sizeof(uint64_t), hipMemcpyDeviceToHost, P.stream));
+            return CRT_OK;
+        }
+        for (uint32_t g = 0; g <= P.last; g++) q->shoot.level_rays[g] += P.level[g].n;
+        q->shoot.levels = std::max(q->shoot.levels, P.last + 1);
+        CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->pin->shoot + SH_DIFFUSE, diffuse, sizeof(uint64_t), hipMemcpyDeviceToHost, P.stream));
+        CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->pin->shoot + SH_REROUTED, q->words.p + QW_REROUTED, sizeof(uint64_t), hipMemcpyDeviceToHost, P.stream));
+    } else if (level0) {
+        launch_reset(nullptr, 0, nullptr, 0, hits, q->d_hits0.p, P.stream);
         CRT_HIP_CHECK(ctx, hipGetLastError());
-    } else {
-        CRT_HIP_CHECK(ctx, hipMemsetAsync(q->words.p, 0, QW_WORDS * sizeof(uint32_t), stream));
-        CRT_HIP_CHECK(ctx, hipMemsetAsync(q->swords.p, 0, SW_WORDS * sizeof(uint32_t), stream));
+    } else {   // the call's numbers, summed where they are
+        ReportArgs R{};
+        R.count = q->swords.p + SW_COUNT;
+        R.hits0 = q->d_hits0.p;
+        R.diffuse = diffuse;
+        R.rerouted = reinterpret_cast<const unsigned long long *>(q->words.p + QW_REROUTED);
+        R.out = P.dev->d_report;
+        R.out2 = P.dev->capturing ? nullptr : q->d_report.p;
+        R.n = P.m;
+        for (uint32_t g = 0; g <= P.last; g++) R.cap[g] = P.level[g].n;   // (0 behind the last level launched)
+        hipLaunchKernelGGL(radiance_report, dim3(1), dim3(64), 0, P.stream, R);
+        CRT_HIP_CHECK(ctx, hipGetLastError());
+        if (!P.dev->capturing) CRT_HIP_CHECK(ctx, hipMemcpyAsync(&q->pin->report, q->d_report.p, sizeof(crt_shoot_report), hipMemcpyDeviceToHost, P.stream));
     }
-    uint32_t count[MAX_GENERATIONS + 1] = {m};   // dev: the capacities -- what the launches are sized for
+    return CRT_OK;
+}
+
+// radiance_scatter of level g (G: its arguments), and how level g + 1 gets its room -- BEFORE the launch that fills it -- and its size,
+// behind it: the ONE place that tells.  Read back through pinned memory and reserve; or (dev) take the capacity, and wait for nothing.
+static int shoot_children(crt_ctx *ctx, ShootPass &P, const uint32_t g, RadianceArgs &G) {
+    crt_query_state *q = ctx->query;
+    const bool gi = P.gi != nullptr;
+    const LevelSize S = P.level[g];
+    const auto scatter = [&] {
+        if (G.spawn) { G.child_rays = q->lv[g + 1].rays.p; G.child_keys = q->lv[g + 1].keys.p; }
+        hipLaunchKernelGGL(SCATTER[gi][S.count ? 1 : 0], dim3((uint32_t)(((uint64_t)S.n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, P.stream, P.A, G);
+        return hipGetLastError();
+    };
+    if (!G.spawn) {   // the deepest level a ray may reach: no children, and the level behind it stays {0, null}
+        CRT_HIP_CHECK(ctx, scatter());
+        return CRT_OK;
+    }
+    if (P.dev) {   // no wait: the next level is launched for what it may hold, and counts for itself
+        G.child_cap = P.dev->cap[g + 1];   // (at most what the arrays hold: shoot_enqueue; a child beyond it is the background)
+        P.level[g + 1] = {G.child_cap, G.child_count};
+        CRT_HIP_CHECK(ctx, scatter());
+        return CRT_OK;
+    }
+    // the next level holds at most `fan` rays for each of this one
+    const uint64_t most = shoot_fan(P.o, gi) * S.n;
+    if (most > SHOOT_LEVEL_RAYS) { ctx->error = "crt_shoot_rays: a recursion level wider than 2^30 rays"; return CRT_ERR_NOMEM; }
+    if (int rc = shoot_level_reserve(ctx, g + 1, most, true, gi)) return rc;
+    G.child_cap = (uint32_t)std::min<uint64_t>(q->lv[g + 1].rays.cap, SHOOT_LEVEL_RAYS);
+    if (gi) G.child_cap = (uint32_t)std::min<uint64_t>(G.child_cap, q->lv[g + 1].keys.cap);
+    CRT_HIP_CHECK(ctx, scatter());
+    // the one wait of a level: four bytes through pinned memory, to size the next one
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->pin->shoot + SH_COUNT, G.child_count, sizeof(uint32_t), hipMemcpyDeviceToHost, P.stream));
+    CRT_HIP_CHECK(ctx, hipStreamSynchronize(P.stream));
+    P.level[g + 1] = {(uint32_t)std::min<uint64_t>(*reinterpret_cast<const uint32_t *>(q->pin->shoot + SH_COUNT), most), nullptr};
+    return query_list_reserve(ctx, P.level[g + 1].n);   // (the list follows the widest level)
+}
+
+// the down-sweep: level after level, until one has no children
+static int shoot_down(crt_ctx *ctx, ShootPass &P) {
+    crt_query_state *q = ctx->query;
+    const crt_options *o = P.o;
+    const bool gi = P.gi != nullptr;
     uint32_t *const d_count = q->swords.p + SW_COUNT;   // [g]: rays appended to level g
-    uint32_t last = 0;
+    P.level[0] = {P.m, nullptr};
     for (uint32_t g = 0; g <= o->max_depth; g++) {
-        const uint32_t n = count[g];
-        last = g;
-        int rc;
-        if (!dev && ((rc = query_list_reserve(ctx, n)) || (rc = shoot_level_reserve(ctx, g, n, g > 0, gi != nullptr)))) return rc;   // (the list follows the widest level)
-        const bool devn = dev && g > 0;   // (level 0's size is the caller's n: its launches are those of the other calls)
+        const LevelSize S = P.level[g];
+        P.last = g;
         const ShootLevel &L = q->lv[g];
-        float *rgb = g == 0 ? d_rgb : L.rgb.p;
-        const uint32_t blocks = (uint32_t)(((uint64_t)n + BLOCK - 1) / BLOCK);
+        float *rgb = g == 0 ? P.d_rgb : L.rgb.p;
         RadianceArgs G{};
-        G.in_rays = d_rays; G.rays = L.rays.p; G.hits = L.hits.p; G.status = L.status.p; G.rgb = rgb; G.nodes = L.nodes.p; G.n = n;
+        G.in_rays = P.d_rays; G.rays = L.rays.p; G.hits = L.hits.p; G.status = L.status.p; G.rgb = rgb; G.nodes = L.nodes.p; G.n = S.n; G.n_dev = S.count;
         G.diffuse_total = reinterpret_cast<unsigned long long *>(q->swords.p + SW_DIFFUSE);
         G.reflection_bias = o->reflection_bias; G.refraction_bias = o->refraction_bias;
         if (gi) {
-            G.in_keys = gi->d_keys; G.keys = L.keys.p; G.gi_samples = o->gi_sample_size; G.gi_seed = o->gi_seed; G.key_first = gi->key_first;
+            G.in_keys = P.gi->d_keys; G.keys = L.keys.p; G.gi_samples = o->gi_sample_size; G.gi_seed = o->gi_seed; G.key_first = P.gi->key_first;
             G.monte_carlo_bias = o->monte_carlo_bias;
         }
-        if (devn) G.n_dev = d_count + g;
         if (g == 0) {
-            if (gi) hipLaunchKernelGGL(radiance_prepare<true>, dim3(blocks), dim3(BLOCK), 0, stream, G);
-            else hipLaunchKernelGGL(radiance_prepare<false>, dim3(blocks), dim3(BLOCK), 0, stream, G);
+            hipLaunchKernelGGL(PREPARE[gi], dim3((uint32_t)(((uint64_t)S.n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, P.stream, G);
             CRT_HIP_CHECK(ctx, hipGetLastError());
         }
         // children are REFLECTION or REFRACTION rays, which walk alike: only the caller's own ray can be PRIMARY (Ray.cpp:13)
-        QueryCall trace = closest_call(L.rays.p, n, g == 0 ? ray_type : (uint32_t)CRT_RAY_REFLECTION, L.hits.p);
-        QueryCall light = shade_call(L.hits.p, n, o->shadow_bias, rgb, L.status.p, gi != nullptr);
-        if (devn) trace.d_count = light.d_count = d_count + g;
-        trace.kernels_only = light.kernels_only = dev != nullptr;
-        rc = query_launches(ctx, trace, stream, g == 0);
-        if (rc) return rc;
-        if (g == 0 && dev) {
-            launch_reset(nullptr, 0, nullptr, 0, reinterpret_cast<const unsigned long long *>(q->words.p + QW_HITS), q->d_hits0.p, stream);
-            CRT_HIP_CHECK(ctx, hipGetLastError());
-        } else if (g == 0) CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_shoot + SH_HITS0, q->words.p + QW_HITS, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        rc = query_launches(ctx, light, stream, false);
-        if (rc) return rc;
-        // the next level holds at most `fan` rays for each of this one: room for that BEFORE the launch that fills it
-        const bool spawn = g + 1 <= o->max_depth;   // a child enters shootRay with depth g + 1 (RayTracer.cpp:427)
-        if (spawn) {
-            if (!dev) {
-                if (fan * n > SHOOT_LEVEL_RAYS) { ctx->error = "crt_shoot_rays: a recursion level wider than 2^30 rays"; return CRT_ERR_NOMEM; }
-                rc = shoot_level_reserve(ctx, g + 1, fan * n, true, gi != nullptr);
-                if (rc) return rc;
-            }
-            G.child_rays = q->lv[g + 1].rays.p;
-            G.child_keys = q->lv[g + 1].keys.p;
-            G.child_cap = (uint32_t)std::min<uint64_t>(q->lv[g + 1].rays.cap, SHOOT_LEVEL_RAYS);
-            if (gi) G.child_cap = (uint32_t)std::min<uint64_t>(G.child_cap, q->lv[g + 1].keys.cap);
-            if (dev) G.child_cap = dev->cap[g + 1];   // (at most what the arrays hold: shoot_enqueue; a child beyond it is the background)
-        }
+        QueryCall trace = closest_call(L.rays.p, S.n, g == 0 ? P.ray_type : (uint32_t)CRT_RAY_REFLECTION, L.hits.p);
+        QueryCall light = shade_call(L.hits.p, S.n, o->shadow_bias, rgb, L.status.p, gi);
+        trace.d_count = light.d_count = S.count;
+        trace.kernels_only = light.kernels_only = P.kernels_only;
+        int rc = query_launches(ctx, trace, P.stream, g == 0);
+        if (rc || (g == 0 && (rc = shoot_numbers(ctx, P, true))) || (rc = query_launches(ctx, light, P.stream, false))) return rc;
         G.child_count = d_count + g + 1;
-        G.spawn = spawn ? 1u : 0u;
-        if (devn) {
-            if (gi) hipLaunchKernelGGL((radiance_scatter<true, true>), dim3(blocks), dim3(BLOCK), 0, stream, A, G);
-            else hipLaunchKernelGGL((radiance_scatter<false, true>), dim3(blocks), dim3(BLOCK), 0, stream, A, G);
-        } else if (gi) hipLaunchKernelGGL(radiance_scatter<true>, dim3(blocks), dim3(BLOCK), 0, stream, A, G);
-        else hipLaunchKernelGGL(radiance_scatter<false>, dim3(blocks), dim3(BLOCK), 0, stream, A, G);
-        CRT_HIP_CHECK(ctx, hipGetLastError());
-        if (!spawn) break;
-        if (dev) count[g + 1] = dev->cap[g + 1];   // no wait: the next level is launched for what it may hold, and counts for itself
-        else {
-            // the one wait of a level: four bytes through pinned memory, to size the next one
-            CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_shoot + SH_COUNT, G.child_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));
-            count[g + 1] = (uint32_t)std::min<uint64_t>(*reinterpret_cast<const uint32_t *>(q->h_shoot + SH_COUNT), fan * n);
-        }
-        if (count[g + 1] == 0) break;
+        G.spawn = g + 1 <= o->max_depth ? 1u : 0u;   // a child enters shootRay with depth g + 1 (RayTracer.cpp:427)
+        if ((rc = shoot_children(ctx, P, g, G))) return rc;
+        if (P.level[g + 1].n == 0) break;
     }
-    if (!dev) {
-        for (uint32_t g = 0; g <= last; g++) q->shoot.level_rays[g] += count[g];
-        q->shoot.levels = std::max(q->shoot.levels, last + 1);
-    }
-    // the up-sweep: level g's recursing records from level g + 1's colours, which are final by then
-    for (uint32_t g = last + 1; g-- > 0;) {
+    return CRT_OK;
+}
+
+// the up-sweep: level g's recursing records from level g + 1's colours, which are final by then
+static int shoot_up(crt_ctx *ctx, const ShootPass &P) {
+    crt_query_state *q = ctx->query;
+    for (uint32_t g = P.last + 1; g-- > 0;) {
         const ShootLevel &L = q->lv[g];
+        const LevelSize S = P.level[g], C = g < P.last ? P.level[g + 1] : LevelSize{0u, nullptr};
         RadianceArgs G{};
-        G.status = L.status.p; G.nodes = L.nodes.p; G.rgb = g == 0 ? d_rgb : L.rgb.p; G.n = count[g];
-        G.child_rgb = g < last ? q->lv[g + 1].rgb.p : nullptr;
-        G.child_n = g < last ? count[g + 1] : 0u;
-        G.gi_samples = gi ? o->gi_sample_size : 0u;
-        const dim3 grid((uint32_t)(((uint64_t)count[g] + BLOCK - 1) / BLOCK));
-        if (dev) {
-            G.n_dev = g > 0 ? d_count + g : nullptr;
-            G.child_n_dev = g < last ? d_count + g + 1 : nullptr;
-            if (gi) hipLaunchKernelGGL((radiance_combine<true, true>), grid, dim3(BLOCK), 0, stream, A, G);
-            else hipLaunchKernelGGL((radiance_combine<false, true>), grid, dim3(BLOCK), 0, stream, A, G);
-        } else if (gi) hipLaunchKernelGGL(radiance_combine<true>, grid, dim3(BLOCK), 0, stream, A, G);
-        else hipLaunchKernelGGL(radiance_combine<false>, grid, dim3(BLOCK), 0, stream, A, G);
+        G.status = L.status.p; G.nodes = L.nodes.p; G.rgb = g == 0 ? P.d_rgb : L.rgb.p; G.n = S.n; G.n_dev = S.count;
+        G.child_rgb = g < P.last ? q->lv[g + 1].rgb.p : nullptr;
+        G.child_n = C.n; G.child_n_dev = C.count;
+        G.gi_samples = P.gi ? P.o->gi_sample_size : 0u;
+        // (an enqueue call's up-sweep is the DEVN build at every level, level 0 among them: the sizes it reads are its children's too)
+        hipLaunchKernelGGL(COMBINE[P.gi ? 1 : 0][P.dev ? 1 : 0], dim3((uint32_t)(((uint64_t)S.n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, P.stream, P.A, G);
         CRT_HIP_CHECK(ctx, hipGetLastError());
     }
-    if (dev) {   // the call's numbers, summed where they are
-        ReportArgs P{};
-        P.count = d_count;
-        P.hits0 = q->d_hits0.p;
-        P.diffuse = reinterpret_cast<const unsigned long long *>(q->swords.p + SW_DIFFUSE);
-        P.rerouted = reinterpret_cast<const unsigned long long *>(q->words.p + QW_REROUTED);
-        P.out = dev->d_report;
-        P.out2 = dev->capturing ? nullptr : q->d_report.p;
-        P.n = m;
-        for (uint32_t g = 0; g <= last; g++) P.cap[g] = count[g];   // (0 behind the last level launched)
-        hipLaunchKernelGGL(radiance_report, dim3(1), dim3(64), 0, stream, P);
-        CRT_HIP_CHECK(ctx, hipGetLastError());
-        if (!dev->capturing) CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_report, q->d_report.p, sizeof(crt_shoot_report), hipMemcpyDeviceToHost, stream));
-        return CRT_OK;
-    }
-    CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_shoot + SH_DIFFUSE, q->swords.p + SW_DIFFUSE, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->h_shoot + SH_REROUTED, q->words.p + QW_REROUTED, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     return CRT_OK;
 }
 
-static int shoot_check(crt_ctx *ctx, const void *rays, const crt_options *options, const void *out, uint32_t ray_type, const char *what) {
-    if (!rays || !options || !out) { ctx->error = std::string(what) + ": NULL array or options with n > 0"; return CRT_ERR_INVALID; }
-    if (ray_type > (uint32_t)CRT_RAY_REFRACTION) { ctx->error = std::string(what) + ": unknown ray_type " + std::to_string(ray_type); return CRT_ERR_INVALID; }
-    if (options->use_gi) {
-        ctx->error = std::string(what) + ": use_gi is not offered (the GI build's random sample rays, its occlusion rule and its division by GI_SAMPLE_SIZE + 1)";
-        return CRT_ERR_INVALID;
-    }
-    if ((uint64_t)options->max_depth + 1 > (uint64_t)MAX_GENERATIONS) {   // (a frame's rule: crt_launch.hip)
-        ctx->error = std::string(what) + ": max_depth too large: " + std::to_string(options->max_depth) + " + 1 levels, at most " + std::to_string(MAX_GENERATIONS);
-        return CRT_ERR_INVALID;
-    }
-    return CRT_OK;
+static int shoot_pass(crt_ctx *ctx, ShootPass &P) {
+    crt_query_state *q = ctx->query;
+    P.A.s = (scene_args_p)ctx->d_scene;
+    P.A.f = (frame_args_p)q->frame.p;
+    P.kernels_only = P.dev != nullptr;   // (kernel launches alone: shoot_enqueue)
+    int rc;
+    if ((rc = clear_words(ctx, q->words.p, QW_WORDS, q->swords.p, SW_WORDS, P.kernels_only, P.stream)) || (rc = shoot_down(ctx, P)) || (rc = shoot_up(ctx, P))) return rc;
+    return shoot_numbers(ctx, P, false);
 }
 
-// crt_shoot_rays_gi*: the arguments, and *pass = the rays of one pass (null: no pass size is asked for, and none can be refused)
-static int shoot_gi_check(crt_ctx *ctx, const void *rays, const crt_options *options, const void *out, uint32_t ray_type, const char *what, uint64_t *pass) {
-    if (!rays || !options || !out) { ctx->error = std::string(what) + ": NULL array or options with n > 0"; return CRT_ERR_INVALID; }
-    if (ray_type > (uint32_t)CRT_RAY_REFRACTION) { ctx->error = std::string(what) + ": unknown ray_type " + std::to_string(ray_type); return CRT_ERR_INVALID; }
-    if (!options->use_gi) {
-        ctx->error = std::string(what) + ": use_gi is 0: the deterministic build's colours are crt_shoot_rays' (crt_shoot_rays_device's)";
-        return CRT_ERR_INVALID;
-    }
-    if (options->gi_sample_size > 64u) {   // (a frame's rule: crt_launch.hip)
-        ctx->error = std::string(what) + ": gi_sample_size too large: " + std::to_string(options->gi_sample_size) + ", at most 64";
-        return CRT_ERR_INVALID;
-    }
-    if ((uint64_t)options->max_depth + 1 > (uint64_t)MAX_GENERATIONS) {
-        ctx->error = std::string(what) + ": max_depth too large: " + std::to_string(options->max_depth) + " + 1 levels, at most " + std::to_string(MAX_GENERATIONS);
-        return CRT_ERR_INVALID;
-    }
-    if (!pass) return CRT_OK;   // (crt_shoot_rays_gi_enqueue: one pass, whose levels the capacities bound)
-    uint64_t product = 0;
-    *pass = shoot_gi_pass_rays(ctx, options, &product);
-    if (*pass == 0) {
-        ctx->error = std::string(what) + ": the deepest level of a pass of 64 rays may hold 64 x max(2, gi_sample_size)^max_depth = 64 x " +
-                     std::to_string(shoot_fan(options, true)) + "^" + std::to_string(options->max_depth) +
-                     (product > SHOOT_GI_DEEPEST_RAYS ? " > 64 x 2^26" : " = " + std::to_string(64u * product)) + " rays, more than 2^26";
-        return CRT_ERR_INVALID;
-    }
-    return CRT_OK;
-}
-
-// the radiance queries' own words and pinned slots, the enqueue calls' among them: made by the first radiance call of a context, so that
-// an enqueue call inside a capture finds them
+// the radiance queries' own words, the enqueue calls' among them: made by the first radiance call of a context, so that an enqueue
+// call inside a capture finds them
 static int shoot_words_reserve(crt_ctx *ctx) {
     crt_query_state *q = ctx->query;
-    if (q->h_shoot) return CRT_OK;
-    int rc;
-    if ((rc = q->swords.reserve(ctx, SW_WORDS)) || (rc = q->d_report.reserve(ctx, 1)) || (rc = q->d_hits0.reserve(ctx, 1))) return rc;
-    if (!q->h_report) {
-        CRT_HIP_CHECK(ctx, hipHostMalloc((void **)&q->h_report, sizeof(crt_shoot_report)));
-        memset(q->h_report, 0, sizeof(crt_shoot_report));
-    }
-    CRT_HIP_CHECK(ctx, hipHostMalloc((void **)&q->h_shoot, SH_SLOTS * sizeof(uint64_t)));
-    memset(q->h_shoot, 0, SH_SLOTS * sizeof(uint64_t));
-    return CRT_OK;
+    return q->shoot_words_made() ? CRT_OK : reserve_all(ctx, q->swords, SW_WORDS, q->d_report, 1, q->d_hits0, 1);
 }
 
 // one device call: n rays, `pass` at a time
 static int shoot_run(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *d_rgb, hipStream_t stream,
                      const uint64_t pass, const ShootGi *gi) {
-    int rc = query_begin(ctx, stream, true);
-    if (rc) return rc;
+    int rc;
+    if ((rc = query_begin(ctx, stream, CALL_RADIANCE)) || (rc = shoot_words_reserve(ctx)) || (rc = call_open(ctx, CALL_RADIANCE, n, stream))) return rc;
     crt_query_state *q = ctx->query;
-    if ((rc = shoot_words_reserve(ctx))) return rc;
-    q->stats = crt_query_stats{};
-    q->stats.rays = n;
-    q->shoot = crt_shoot_stats{};
-    q->shoot.rays = n;
-    CRT_HIP_CHECK(ctx, hipEventRecord(q->call.ev0, stream));
     for (uint64_t done = 0; done < n; done += pass) {
         if (done) {   // the previous pass's numbers leave the pinned slots before this pass writes them
             CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));
             shoot_fold(q);
         }
+        const uint32_t m = (uint32_t)std::min(n - done, pass);
         ShootGi part{};
         if (gi) { part.d_keys = gi->d_keys ? gi->d_keys + done : nullptr; part.key_first = gi->key_first + (uint32_t)done; }
-        rc = shoot_pass(ctx, d_rays + done, (uint32_t)std::min(n - done, pass), ray_type, options, d_rgb + 3 * done, stream, gi ? &part : nullptr);
-        if (rc) return rc;
+        ShootPass P{d_rays + done, m, ray_type, options, d_rgb + 3 * done, stream, gi ? &part : nullptr, nullptr};
+        if ((rc = query_list_reserve(ctx, m)) || (rc = shoot_level_reserve(ctx, 0, m, false, gi != nullptr)) || (rc = shoot_pass(ctx, P))) return rc;
     }
-    CRT_HIP_CHECK(ctx, hipEventRecord(q->call.ev1, stream));
-    q->call.stream = stream;
-    q->call.radiance = true;
-    q->call.enqueue = false;
-    q->call.open = true;
-    return CRT_OK;
+    return call_close(ctx, CALL_RADIANCE, stream);
 }
 
 // rays level g's arrays hold now (`own_rgb`, `keys`: as shoot_level_reserve takes them)
@@ -809,11 +825,11 @@ static int shoot_enqueue(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32
     if (capturing) {
         if (capture != hipStreamCaptureStatusActive) return refuse("the capture is invalidated");
         if (ctx->pending) return refuse("a crt_render_async frame is pending: the call would have to wait for it (crt_wait before the capture)");
-        if (!ctx->query || !ctx->query->h_words || !ctx->query->h_shoot)
+        if (!ctx->query || !ctx->query->shoot_words_made())
             return refuse("the query scratch would have to grow (the context has none yet): size it with a radiance call before the capture");
         if (ctx->query->call.open)
             return refuse("an open call would have to be harvested, which waits (crt_get_shoot_stats or crt_get_query_stats before the capture)");
-    } else if ((rc = query_begin(ctx, stream, true, true)) || (rc = shoot_words_reserve(ctx))) return rc;
+    } else if ((rc = query_begin(ctx, stream, CALL_ENQUEUE)) || (rc = shoot_words_reserve(ctx))) return rc;
     crt_query_state *q = ctx->query;
     // the capacities, and room for them
     const bool keys = gi != nullptr;
@@ -835,32 +851,24 @@ static int shoot_enqueue(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32
         if ((rc = query_list_reserve(ctx, widest)) || (rc = shoot_level_reserve(ctx, 0, n, false, keys))) return rc;
         for (uint32_t g = 1; g <= o->max_depth && dev.cap[g]; g++)
             if ((rc = shoot_level_reserve(ctx, g, dev.cap[g], true, keys))) return rc;
-        q->stats = crt_query_stats{};
-        q->stats.rays = n;
-        q->shoot = crt_shoot_stats{};
-        q->shoot.rays = n;
-        CRT_HIP_CHECK(ctx, hipEventRecord(q->call.ev0, stream));
+        if ((rc = call_open(ctx, CALL_ENQUEUE, n, stream))) return rc;
     }
     dev.d_report = d_report;
     dev.capturing = capturing;
-    rc = shoot_pass(ctx, d_rays, (uint32_t)n, ray_type, o, d_rgb, stream, gi, &dev);
-    if (rc || capturing) return rc;   // (a captured call leaves no open call behind: the replays' numbers are d_report's)
-    CRT_HIP_CHECK(ctx, hipEventRecord(q->call.ev1, stream));
-    q->call.stream = stream;
-    q->call.radiance = q->call.enqueue = true;
-    q->call.open = true;
-    return CRT_OK;
+    ShootPass P{d_rays, (uint32_t)n, ray_type, o, d_rgb, stream, gi, &dev};
+    rc = shoot_pass(ctx, P);
+    if (rc || capturing) return rc;   // (a captured call opens and closes nothing: the replays' numbers are d_report's)
+    return call_close(ctx, CALL_ENQUEUE, stream);
 }
 
 // the host variants: copy in, run, copy out, `pass` rays at a time; the colours' device copy is level 0's own colour array
 static int shoot_host(crt_ctx *ctx, const crt_ray *rays, const uint32_t *keys, uint64_t n, uint32_t ray_type, const crt_options *options, float *out_rgb,
                       const uint64_t pass, const bool gi) {
     const uint64_t m = std::min(n, pass);
-    int rc = query_begin(ctx, ctx->stream, true);
+    int rc = query_begin(ctx, ctx->stream, CALL_RADIANCE);
     if (rc) return rc;
     crt_query_state *q = ctx->query;
-    if ((rc = shoot_level_reserve(ctx, 0, m, true, gi)) || (rc = q->shoot_in.reserve(ctx, m))) return rc;
-    if (keys && (rc = q->shoot_keys.reserve(ctx, m))) return rc;
+    if ((rc = shoot_level_reserve(ctx, 0, m, true, gi)) || (rc = reserve_all(ctx, q->shoot_in, m, q->shoot_keys, keys ? m : 0))) return rc;
     crt_shoot_stats total{};
     crt_query_stats qtotal{};
     for (uint64_t done = 0; done < n; done += pass) {
@@ -885,82 +893,53 @@ static int shoot_host(crt_ctx *ctx, const crt_ray *rays, const uint32_t *keys, u
     return CRT_OK;
 }
 
+// the radiance entry points' check: the arrays and the options, ray_type, use_gi as the build has it, max_depth; `pass`: a GI pass's size
+static CallCheck shoot_needs(const char *what, const void *rays, const crt_options *options, const void *out, uint32_t ray_type, bool gi, uint64_t *pass) {
+    return {what, {rays, options, out}, ray_type, options, true, gi, pass};
+}
+
 extern "C" int crt_shoot_rays_device(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *d_rgb,
                                      void *stream) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
-    int rc = shoot_check(ctx, d_rays, options, d_rgb, ray_type, "crt_shoot_rays_device");
-    if (rc) return rc;
-    return shoot_run(ctx, d_rays, n, ray_type, options, d_rgb, (hipStream_t)stream, ctx->shoot_pass_rays, nullptr);
+    return query_entry(ctx, n, shoot_needs("crt_shoot_rays_device", d_rays, options, d_rgb, ray_type, false, nullptr),
+                       [&] { return shoot_run(ctx, d_rays, n, ray_type, options, d_rgb, (hipStream_t)stream, ctx->shoot_pass_rays, nullptr); });
 }
 
 extern "C" int crt_shoot_rays(crt_ctx *ctx, const crt_ray *rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *out_rgb) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
-    int rc = shoot_check(ctx, rays, options, out_rgb, ray_type, "crt_shoot_rays");
-    if (rc) return rc;
-    return shoot_host(ctx, rays, nullptr, n, ray_type, options, out_rgb, ctx->shoot_pass_rays, false);
+    return query_entry(ctx, n, shoot_needs("crt_shoot_rays", rays, options, out_rgb, ray_type, false, nullptr),
+                       [&] { return shoot_host(ctx, rays, nullptr, n, ray_type, options, out_rgb, ctx->shoot_pass_rays, false); });
 }
 
 extern "C" int crt_shoot_rays_gi_device(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t *d_keys, uint64_t n, uint32_t ray_type,
                                         const crt_options *options, float *d_rgb, void *stream) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
     uint64_t pass = 0;
-    int rc = shoot_gi_check(ctx, d_rays, options, d_rgb, ray_type, "crt_shoot_rays_gi_device", &pass);
-    if (rc) return rc;
     const ShootGi gi{d_keys, 0u};
-    return shoot_run(ctx, d_rays, n, ray_type, options, d_rgb, (hipStream_t)stream, pass, &gi);
+    return query_entry(ctx, n, shoot_needs("crt_shoot_rays_gi_device", d_rays, options, d_rgb, ray_type, true, &pass),
+                       [&] { return shoot_run(ctx, d_rays, n, ray_type, options, d_rgb, (hipStream_t)stream, pass, &gi); });
 }
 
 extern "C" int crt_shoot_rays_gi(crt_ctx *ctx, const crt_ray *rays, const uint32_t *keys, uint64_t n, uint32_t ray_type, const crt_options *options,
                                  float *out_rgb) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
     uint64_t pass = 0;
-    int rc = shoot_gi_check(ctx, rays, options, out_rgb, ray_type, "crt_shoot_rays_gi", &pass);
-    if (rc) return rc;
-    return shoot_host(ctx, rays, keys, n, ray_type, options, out_rgb, pass, true);
-}
-
-extern "C" int crt_get_shoot_stats(crt_ctx *ctx, crt_shoot_stats *out) {
-    if (!ctx || !out) return CRT_ERR_INVALID;
-    if (!ctx->query) { *out = crt_shoot_stats{}; return CRT_OK; }
-    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    int rc = query_harvest(ctx);
-    if (rc) return rc;
-    *out = ctx->query->shoot;
-    return CRT_OK;
+    return query_entry(ctx, n, shoot_needs("crt_shoot_rays_gi", rays, options, out_rgb, ray_type, true, &pass),
+                       [&] { return shoot_host(ctx, rays, keys, n, ray_type, options, out_rgb, pass, true); });
 }
 
 extern "C" int crt_shoot_rays_enqueue(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *d_rgb,
                                       const uint32_t *level_cap, crt_shoot_report *d_report, void *stream) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
-    int rc = shoot_check(ctx, d_rays, options, d_rgb, ray_type, "crt_shoot_rays_enqueue");
-    if (rc) return rc;
-    return shoot_enqueue(ctx, d_rays, n, ray_type, options, d_rgb, level_cap, d_report, (hipStream_t)stream, nullptr, "crt_shoot_rays_enqueue");
+    const char *what = "crt_shoot_rays_enqueue";
+    return query_entry(ctx, n, shoot_needs(what, d_rays, options, d_rgb, ray_type, false, nullptr), [&] {
+        return shoot_enqueue(ctx, d_rays, n, ray_type, options, d_rgb, level_cap, d_report, (hipStream_t)stream, nullptr, what);
+    });
 }
 
 extern "C" int crt_shoot_rays_gi_enqueue(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t *d_keys, uint64_t n, uint32_t ray_type,
                                          const crt_options *options, float *d_rgb, const uint32_t *level_cap, crt_shoot_report *d_report,
                                          void *stream) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n == 0) return CRT_OK;
-    int rc = shoot_gi_check(ctx, d_rays, options, d_rgb, ray_type, "crt_shoot_rays_gi_enqueue", nullptr);
-    if (rc) return rc;
+    const char *what = "crt_shoot_rays_gi_enqueue";
     const ShootGi gi{d_keys, 0u};
-    return shoot_enqueue(ctx, d_rays, n, ray_type, options, d_rgb, level_cap, d_report, (hipStream_t)stream, &gi, "crt_shoot_rays_gi_enqueue");
-}
-
-extern "C" int crt_get_shoot_report(crt_ctx *ctx, crt_shoot_report *out) {
-    if (!ctx || !out) return CRT_ERR_INVALID;
-    if (!ctx->query) { *out = crt_shoot_report{}; return CRT_OK; }
-    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    int rc = query_harvest(ctx);
-    if (rc) return rc;
-    *out = ctx->query->report;
-    return CRT_OK;
+    return query_entry(ctx, n, shoot_needs(what, d_rays, options, d_rgb, ray_type, true, nullptr), [&] {
+        return shoot_enqueue(ctx, d_rays, n, ray_type, options, d_rgb, level_cap, d_report, (hipStream_t)stream, &gi, what);
+    });
 }
 
 extern "C" uint64_t crt_query_scratch_generation(const crt_ctx *ctx) { return ctx && ctx->query ? ctx->query->generation : 0; }

@@ -59,6 +59,19 @@ def assert_shaded(pkg, rgb, status, want_status, want, what):
     assert np.all(rgb[zero].view(np.uint32) == 0), what + ": a record that recurses (or is invalid) is +0, 0, 0"
 
 
+def same_bits(a, b, what):
+    assert np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32)), what
+
+
+def level_rays(st):
+    return [int(x) for x in st.level_rays]
+
+
+def make(pkg, scenes, oracle, scene, folder="", tuning=None):
+    tracer = pkg.Tracer(pkg.Scene(json_text=scenes.to_json(scene), folder=folder), tuning=pkg.make_tuning(**tuning) if tuning else None)
+    return tracer, oracle.OracleScene(scenes.to_blob(scene))
+
+
 def distances(n):
     """per-ray occlusion limits of the ray-query tests"""
     return np.random.default_rng(12).uniform(0.1, 12.0, n).astype(np.float32)

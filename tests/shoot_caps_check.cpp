@@ -1,12 +1,14 @@
 // A stand-alone host program around csrc/shoot_caps.h, the arithmetic of crt_shoot_rays*_enqueue: the levels' capacities and the rays
-// of one launch of a level's chunk loop.  tests/test_shoot_enqueue_host.py compiles it with the host sanitizers and runs it; it prints
-// "ok <cases>" and returns 0, or says which property failed.
+// of one launch of a level's chunk loop; and around csrc/call_wait.h, the rule by which a call first waits for the one still under
+// way.  tests/test_shoot_enqueue_host.py compiles it with the host sanitizers and runs it; it prints "ok <cases>" and returns 0, or
+// says which property failed.
 //   shoot_caps_check --layout   prints sizeof(crt_shoot_report) and its fields' offsets, from the header
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
+#include "call_wait.h"
 #include "crt_hip.h"
 #include "shoot_caps.h"
 
@@ -94,6 +96,18 @@ int main(int argc, char **argv) {
                             REQUIRE(cap[g] == (g < depth ? std::min<uint64_t>(want, 0xFFFFFFFFull / fan) : want));
                         }
                     }
+    // the waiting rule, all 36 cases written out: [a call is open][its kind][the new call's kind][0: another stream, 1: the same].
+    // No open call: no wait.  Otherwise a wait, but for a query behind a query and an enqueue call behind an enqueue call on ONE stream.
+    static const bool waits[2][3][3][2] = {
+        {{{false, false}, {false, false}, {false, false}}, {{false, false}, {false, false}, {false, false}}, {{false, false}, {false, false}, {false, false}}},
+        {/* open: a query     */ {/* query */ {true, false}, /* radiance */ {true, true}, /* enqueue */ {true, true}},
+         /* open: a radiance  */ {/* query */ {true, true}, /* radiance */ {true, true}, /* enqueue */ {true, true}},
+         /* open: an enqueue  */ {/* query */ {true, true}, /* radiance */ {true, true}, /* enqueue */ {true, false}}}};
+    const CallKind kinds[3] = {CALL_QUERY, CALL_RADIANCE, CALL_ENQUEUE};
+    for (int open = 0; open < 2; open++)
+        for (int was = 0; was < 3; was++)
+            for (int next = 0; next < 3; next++)
+                for (int same = 0; same < 2; same++) REQUIRE(call_waits(open != 0, kinds[was], kinds[next], same != 0) == waits[open][was][next][same]);
     printf("ok %llu\n", cases);
     return 0;
 }

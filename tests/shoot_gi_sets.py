@@ -96,3 +96,27 @@ def assert_same_values(got, want, what):
     assert got.shape == want.shape, (what, got.shape, want.shape)
     bad = np.flatnonzero(~((got == want) | (np.isnan(got) & np.isnan(want))))
     assert bad.size == 0, "%s: %d of %d floats differ, first at %d: got %r want %r" % (what, bad.size, got.size, bad[0], got[bad[0]], want[bad[0]])
+
+
+_CASES = {}
+
+
+def case(pkg, scenes, oracle, name, tmp_path_factory, camera=None, tuning=None):
+    """A scene's tracer (with the named camera and tuning), its oracle, the camera's rays and the keys of a frame's pixels: made once"""
+    key = (name, camera, tuple(sorted((tuning or {}).items())))
+    if key not in _CASES:
+        scene = scene_of(scenes, name)
+        folder = ""
+        if scene.get("textures"):
+            folder = str(tmp_path_factory.mktemp(name))
+            scenes.write_bitmaps(scene, folder)
+        tracer = pkg.Tracer(pkg.Scene(json_text=scenes.to_json(scene), folder=folder), tuning=pkg.make_tuning(**tuning) if tuning else None)
+        o = oracle_of(scenes, oracle, name, camera)
+        if camera:
+            tracer.set_camera(CAMERAS[camera][0], look_at(*CAMERAS[camera]))
+        _CASES[key] = dict(scene=scene, tracer=tracer, oracle=o, rays=camera_rays(o), keys=pixel_keys(oracle, SEED, W * H))
+    return _CASES[key]
+
+
+def gi_options(pkg, depth, samples, seed=SEED, **more):
+    return pkg.make_options(depth, use_gi=True, gi_sample_size=samples, rays_per_pixel=1, gi_seed=seed, **more)

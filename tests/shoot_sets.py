@@ -8,6 +8,7 @@ import numpy as np
 
 import query_sets as qs
 import shade_sets as ss
+from helpers import make, small_case
 
 F32 = np.float32
 RECURSING = ("reflective", "refractive")
@@ -79,3 +80,19 @@ def level_two_matters(oracle_scene, rays):
     a, b = oracle_colours(oracle_scene, rays, 1), oracle_colours(oracle_scene, rays, 2)
     with np.errstate(all="ignore"):
         return bool(np.any((a.view(np.uint32) != b.view(np.uint32)) & ~(np.isnan(a) & np.isnan(b))))
+
+
+_CASES = {}
+
+
+def case(pkg, scenes, oracle, name, tmp_path_factory):
+    """A scene's tracer, oracle, its ray set (shoot_sets.rays_for) and the oracle's colours at the scene's depth: made once."""
+    if name not in _CASES:
+        scene, depth, folder = small_case(scenes, name, tmp_path_factory.mktemp(name))
+        tracer, o = make(pkg, scenes, oracle, scene, folder)
+        rays = rays_for(name, scene)
+        rays.setflags(write=False)
+        want = oracle_colours(o, rays, depth)
+        want.setflags(write=False)
+        _CASES[name] = dict(scene=scene, depth=depth, folder=folder, tracer=tracer, oracle=o, rays=rays, want=want)
+    return _CASES[name]

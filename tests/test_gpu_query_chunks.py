@@ -9,7 +9,7 @@ import pytest
 import query_sets as qs
 import shade_sets as ss
 import shoot_sets as sh
-from helpers import assert_same_floats, assert_same_hits, assert_shaded, distances, small_case
+from helpers import assert_same_floats, assert_same_hits, assert_shaded, distances, level_rays, same_bits, small_case
 
 pytestmark = pytest.mark.gpu
 CHUNKS = dict(host_rays=1024, launch_rays=192, pass_rays=1024)
@@ -301,7 +301,61 @@ def test_interleaved_calls_on_two_streams(pkg, scenes, oracle, tmp_path_factory)
     assert_same_floats(tracer.render(max_depth=depth), frame0, "the frame after the queries")
 
 
-# ---- 8. zeros restore the defaults: the staging arrays grow back
+# ---- 8. the same with enqueue calls among them: six calls on two streams, one of them the enqueue call that does not wait
+def test_interleaved_enqueue_calls_on_two_streams(pkg, scenes, oracle, tmp_path_factory):
+    import ctypes as C
+    import torch
+    c, hits, diffuse = shade_wants(pkg, scenes, oracle, tmp_path_factory)
+    _, shoot_rays = shoot_case(pkg, scenes, oracle, "hw11", tmp_path_factory)
+    tracer, depth, k = c["tracer"], c["depth"], len(shoot_rays)
+    frame0 = tracer.render(max_depth=depth).copy()
+    d = device_arrays(pkg, c, hits, diffuse, shoot_rays)
+    tracer.shoot_rays_device(d["shoot"].data_ptr(), k, d["colours"].data_ptr(), max_depth=SHOOT_DEPTH)   # alone: the yardstick (and the scratch's size)
+    torch.cuda.synchronize()
+    alone, alone_hits = tracer.shoot_stats(), int(tracer.query_stats().hits)
+    sync = d["colours"].cpu().numpy()[:k].copy()
+    lr = level_rays(alone)
+    print("hw11 at depth %d: level_rays %s" % (SHOOT_DEPTH, lr[:alone.levels]))
+    assert lr[1] > 0 and any(n > 256 for n in lr[1:alone.levels]), "condition on the input: a level below level 0 in several launches"
+    d["colours"].fill_(float("nan"))
+    rgb = [torch.full((k + 1, 3), float("nan"), dtype=torch.float32, device="cuda") for _ in range(3)]
+    rep = [torch.full((C.sizeof(pkg.ShootReport),), 0xEE, dtype=torch.uint8, device="cuda") for _ in range(3)]
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+
+    def enqueue(i):
+        tracer.shoot_rays_enqueue(d["shoot"].data_ptr(), k, rgb[i].data_ptr(), max_depth=SHOOT_DEPTH, d_report_ptr=rep[i].data_ptr(), stream_ptr=a.cuda_stream)
+
+    try:
+        tracer.set_query_chunks(launch_rays=256)
+        enqueue(0)
+        tracer.trace_rays_device(d["rays"].data_ptr(), N, qs.RAY_REFLECTION, d["hits"].data_ptr(), b.cuda_stream)
+        enqueue(1)
+        enqueue(2)   # behind an enqueue call on its stream: the call that does not wait
+        tracer.shoot_rays_device(d["shoot"].data_ptr(), k, d["colours"].data_ptr(), max_depth=SHOOT_DEPTH, stream_ptr=b.cuda_stream)
+        tracer.occluded_rays_device(d["rays"].data_ptr(), d["dist"].data_ptr(), N, d["occ"].data_ptr(), a.cuda_stream)
+        a.synchronize()
+        b.synchronize()
+        assert shoot_tuple(tracer.shoot_stats()) == shoot_tuple(alone)
+        assert query_tuple(tracer.query_stats()) == (N, int(c["occ"].sum()), 0)
+    finally:
+        tracer.set_query_chunks()
+    for i in range(3):
+        got = rgb[i].cpu().numpy()
+        assert np.all(np.isnan(got[k:])), "written past the end"
+        same_bits(got[:k], sync, "enqueue call %d on stream A" % i)
+        r = pkg.ShootReport.from_buffer_copy(rep[i].cpu().numpy().tobytes())
+        assert (r.levels, level_rays(r), r.shadow_records, r.rerouted, r.hits) == (alone.levels, lr, alone.shadow_records, alone.rerouted, alone_hits), i
+        assert (r.overflow, r.dropped) == (0, 0), i
+    got = {name: d[name].cpu().numpy() for name in ("hits", "occ", "colours")}
+    assert_same_hits(got["hits"][:N].view(pkg.HIT_DTYPE).reshape(-1), hits, "trace_rays_device on stream B")
+    same_bits(got["colours"][:k], sync, "shoot_rays_device on stream B")
+    assert_same_floats(got["colours"][:k], c["shoot_colours"], "shoot_rays_device on stream B: the oracle's colours")
+    assert np.array_equal(got["occ"][:N].astype(bool), c["occ"]), "occluded_rays_device on stream A"
+    assert_same_floats(tracer.render(max_depth=depth), frame0, "the frame after the queries")
+
+
+# ---- 9. zeros restore the defaults: the staging arrays grow back
 def test_zeros_restore_the_defaults(pkg, scenes, oracle, tmp_path_factory):
     c = random_wants(pkg, scenes, oracle, tmp_path_factory)
     tracer = pkg.Tracer(pkg.Scene(json_text=scenes.to_json(c["scene"]), folder=c["folder"]))   # (a context whose first call is a small one)

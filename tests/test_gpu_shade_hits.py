@@ -9,15 +9,10 @@ import pytest
 
 import query_sets as qs
 import shade_sets as ss
-from helpers import assert_same_floats, assert_shaded, small_case
+from helpers import assert_same_floats, assert_shaded, make, small_case
 
 pytestmark = pytest.mark.gpu
 _CASES = {}
-
-
-def make(pkg, scenes, oracle, scene, folder="", tuning=None):
-    tracer = pkg.Tracer(pkg.Scene(json_text=scenes.to_json(scene), folder=folder), tuning=pkg.make_tuning(**tuning) if tuning else None)
-    return tracer, oracle.OracleScene(scenes.to_blob(scene))
 
 
 def case(pkg, scenes, oracle, name, tmp_path_factory):

@@ -1,6 +1,6 @@
 """Radiance queries with no host wait on the GPU (include/crt_hip.h: crt_shoot_rays_enqueue, crt_shoot_rays_gi_enqueue): the colours and
 numbers of the synchronous device calls, bit for bit, from a call that only enqueues -- called directly, and captured into a graph and
-replayed.  The scenes, ray sets and the oracle's colours are those of tests/test_gpu_shoot_rays.py (made once, shared with it)."""
+replayed.  The scenes, ray sets and the oracle's colours are those of tests/test_gpu_shoot_rays.py (tests/shoot_sets.py: made once, shared with it)."""
 import ctypes as C
 
 import numpy as np
@@ -8,16 +8,12 @@ import pytest
 
 import query_sets as qs
 import shoot_sets as sh
-from helpers import assert_same_floats
-from test_gpu_shoot_rays import case, level_rays, make
-from test_gpu_shoot_rays_gi import case as gi_case, gi_options
+from helpers import assert_same_floats, level_rays, make, same_bits
+from shoot_gi_sets import case as gi_case, gi_options
+from shoot_sets import case
 
 pytestmark = pytest.mark.gpu
 SCENES = ["hw08", "hw11", "hw12", "hw14"]
-
-
-def same_bits(a, b, what):
-    assert np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32)), what
 
 
 def numbers(st):

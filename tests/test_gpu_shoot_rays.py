@@ -9,33 +9,11 @@ import pytest
 import query_sets as qs
 import shade_sets as ss
 import shoot_sets as sh
-from helpers import assert_same_floats, small_case
+from helpers import assert_same_floats, level_rays, make, small_case
+from shoot_sets import case
 
 pytestmark = pytest.mark.gpu
-_CASES = {}
 SCENES = ["hw08", "hw11", "hw12", "hw14"]
-
-
-def make(pkg, scenes, oracle, scene, folder="", tuning=None):
-    tracer = pkg.Tracer(pkg.Scene(json_text=scenes.to_json(scene), folder=folder), tuning=pkg.make_tuning(**tuning) if tuning else None)
-    return tracer, oracle.OracleScene(scenes.to_blob(scene))
-
-
-def case(pkg, scenes, oracle, name, tmp_path_factory):
-    """A scene's tracer, oracle, its ray set (shoot_sets.rays_for) and the oracle's colours at the scene's depth: made once."""
-    if name not in _CASES:
-        scene, depth, folder = small_case(scenes, name, tmp_path_factory.mktemp(name))
-        tracer, o = make(pkg, scenes, oracle, scene, folder)
-        rays = sh.rays_for(name, scene)
-        rays.setflags(write=False)
-        want = sh.oracle_colours(o, rays, depth)
-        want.setflags(write=False)
-        _CASES[name] = dict(scene=scene, depth=depth, folder=folder, tracer=tracer, oracle=o, rays=rays, want=want)
-    return _CASES[name]
-
-
-def level_rays(st):
-    return [int(x) for x in st.level_rays]
 
 
 # ---- 1. random rays against the oracle

@@ -10,31 +10,11 @@ import pytest
 import query_sets as qs
 import shoot_gi_sets as gs
 import shoot_sets as sh
+from helpers import level_rays, same_bits
+from shoot_gi_sets import case, gi_options
 
 pytestmark = pytest.mark.gpu
-_CASES = {}
 N = gs.W * gs.H
-
-
-def case(pkg, scenes, oracle, name, tmp_path_factory, camera=None, tuning=None):
-    """A scene's tracer (with the named camera and tuning), its oracle, the camera's rays and the keys of a frame's pixels: made once"""
-    key = (name, camera, tuple(sorted((tuning or {}).items())))
-    if key not in _CASES:
-        scene = gs.scene_of(scenes, name)
-        folder = ""
-        if scene.get("textures"):
-            folder = str(tmp_path_factory.mktemp(name))
-            scenes.write_bitmaps(scene, folder)
-        tracer = pkg.Tracer(pkg.Scene(json_text=scenes.to_json(scene), folder=folder), tuning=pkg.make_tuning(**tuning) if tuning else None)
-        o = gs.oracle_of(scenes, oracle, name, camera)
-        if camera:
-            tracer.set_camera(gs.CAMERAS[camera][0], gs.look_at(*gs.CAMERAS[camera]))
-        _CASES[key] = dict(scene=scene, tracer=tracer, oracle=o, rays=gs.camera_rays(o), keys=gs.pixel_keys(oracle, gs.SEED, N))
-    return _CASES[key]
-
-
-def gi_options(pkg, depth, samples, seed=gs.SEED, **more):
-    return pkg.make_options(depth, use_gi=True, gi_sample_size=samples, rays_per_pixel=1, gi_seed=seed, **more)
 
 
 def shoot_device(tracer, rays, keys, options, ray_type=qs.RAY_PRIMARY):
@@ -49,14 +29,6 @@ def shoot_device(tracer, rays, keys, options, ray_type=qs.RAY_PRIMARY):
     rgb = d_rgb.cpu().numpy()
     assert np.all(np.isnan(rgb[n:])), "written past the end"
     return rgb[:n]
-
-
-def same_bits(a, b, what):
-    assert np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32)), what
-
-
-def level_rays(st):
-    return [int(x) for x in st.level_rays]
 
 
 def stats_tuple(st):
