@@ -774,7 +774,7 @@ class Tracer:
         return s
 
     def kernels(self):
-        """{'level0': ..., 'shadow0': ..., 'levels': ...}: the kernels a production frame runs (names as rocprofv3 prints them)."""
+        """{'level0': ..., 'shadow0': ..., 'levels': ...}: the kernels a production frame runs (names as rocprofv3 prints them; shadow0 is what the last frame ran)."""
         buf = C.create_string_buffer(512)
         L = lib()
         L.crt_describe_kernels.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]

@@ -49,6 +49,7 @@ struct crt_ctx {
     hipEvent_t ev0[EV_RING] = {}, ev1[EV_RING] = {}, ev2[EV_RING] = {}, ev3[EV_RING] = {}, ev4[EV_RING] = {};  // phase boundaries of a render
     hipEvent_t ev_fork[EV_RING] = {}, ev_s0[EV_RING] = {}, ev_s1[EV_RING] = {}, ev_s2[EV_RING] = {};        // ... of its side stream
     bool slot_ev2_is_s1[EV_RING] = {};       // the slot's frame ran its pass on the frame's stream and did not record ev2: the later of ev1 and ev_s1 marks that point (crt_launch.hip, crt_kernel_times_ms)
+    bool shadow0_by_slot = false;            // the last filter frame's bulk shadow pass walked slots, not pixels: the GI mode, a frame without fixed slots (crt_launch.hip; crt_describe_kernels)
     uint64_t launches = 0;
     uint32_t width = 0, height = 0, tiles_x = 0, tiles_y = 0;
     SceneArgs scene{};                // host copy of what crt_create uploads to d_scene

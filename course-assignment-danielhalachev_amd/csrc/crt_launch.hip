@@ -11,7 +11,9 @@
 //    lanes are refilled from a queue; it writes ray-tree nodes, child rays for level g+1 and shadow rays.  Walks that outlast a step budget, and whole small levels, go to a wave-per-ray kernel
 //    (kernel_heavy.h).  The shadow rays of level 0 -- the bulk of the frame -- run on a side stream beside the
 //    deeper levels.  stream_resolve evaluates every pixel's ray tree in the reference's post-order, so that
-//    every float is combined in the same order;
+//    every float is combined in the same order.  A fixed shadow slot (level 0's) is written by whoever walks it
+//    and read by stream_resolve -- except in a filter frame outside the GI mode, whose bulk pass walks level 0's
+//    records pixel by pixel and leaves each pixel's direct light in its root node (kernel_bvh.h: bvh_shadow_pixels);
 //  * the reference's stack DFS has a FIXED visit order and no distance pruning, so the trees are flattened into
 //    hit/miss links (crt_node) and walked without a stack; the plan and leaf-sequence forms rest on the boxes
 //    being nested, which crt_create verifies;
@@ -398,7 +400,19 @@ static int launch_stream_levels(crt_ctx *ctx, const crt_options *o, FramePlan &P
             CRT_HIP_CHECK(ctx, hipEventRecord(ctx->ev_s0[P.slot], where));
             // (beside the levels its persistent waves must leave wave slots on every CU for the level kernels)
             const uint32_t blocks0 = side_per_cu ? std::min(ctx->grid_blocks, (uint32_t)ctx->num_cus * side_per_cu) : ctx->grid_blocks;   // (a spill region holds grid_blocks workgroups' columns)
-            if (P.bvh) {
+            // A filter frame with fixed slots (not the GI mode, whose roots carry children) walks them BY PIXEL (kernel_bvh.h: bvh_shadow_pixels):
+            // the same stream, grid, spill region and events, a pixel's lights in one lane, its direct light stored into its root node
+            const bool by_pixel = P.bvh && ctx->frame.fixed0 && !P.gi;
+            if (P.bvh) ctx->shadow0_by_slot = !by_pixel;
+            if (by_pixel) {
+                // (a claimed pixel is n_lights walks: the chunk that suits the slot pass, in pixels, is n_lights times as much work for a
+                //  wave to sit on beside the queue's waves -- DESIGN.md section 7, the cursor word; whole tiles, never below a wave's refill of 64)
+                S.chunk = std::max(64u, (S.chunk / std::max(1u, ctx->n_lights)) & ~63u);
+                if (P.exec_count) launch(bvh_trace_shadow<0, BVH_TALLY, true>, blocks0, where, S);
+                else if (ctx->tuning.bvh == 2) launch(bvh_trace_shadow<0, BVH_CHECKED, true>, blocks0, where, S);
+                else launch(bvh_trace_shadow<0, BVH_PLAIN, true>, blocks0, where, S);
+            }
+            else if (P.bvh) {
                 if (P.exec_count) launch(bvh_trace_shadow<0, BVH_TALLY>, blocks0, where, S);
                 else if (ctx->tuning.bvh == 2) launch(bvh_trace_shadow<0, BVH_CHECKED>, blocks0, where, S);
                 else launch(bvh_trace_shadow<0, BVH_PLAIN>, blocks0, where, S);

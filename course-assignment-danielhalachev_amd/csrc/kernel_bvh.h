@@ -72,7 +72,8 @@ constexpr int BVH_STEPS_QUEUE = 8;   // ... in the level queue's launch, where a
 // SC_BVH_DIAG + 2 code, the index beside it -- and index 0 is read instead: a development build that cannot fault)
 enum : int { BVH_PLAIN = 0, BVH_TALLY = 1, BVH_CHECKED = 2 };
 constexpr int SC_BVH_DIAG = SC_HEAVY_DIAG + 16;
-// (SC_BVH_DIAG + 0 .. 31: the bounds-checked build's 16 (flag, index) pairs; + 40 .. 43 and + 48 .. 77: the tallying build's walk lengths)
+// (SC_BVH_DIAG + 0 .. 31: the bounds-checked build's 16 (flag, index) pairs; + 40 .. 46 and + 48 .. 77: the tallying build's walk lengths -- + 44 .. 46:
+//  the bulk shadow pass's steps, walks and the steps its waves issued)
 constexpr int SC_BVH_MARK = SC_BVH_DIAG + 80;   // tallying and bounds-checked builds: the largest number of entries any walk's stack held in the frame
 static_assert(SC_BVH_MARK < SC_FALLBACK_TOTAL, "the high-water mark is a word of the frame's counter block");
 // bounds-checked build, codes of its own checks: the spill element lies in its region; a walk's pops returned what its pushes stored
@@ -772,7 +773,7 @@ __device__ __forceinline__ void bvh_shadow_rays(const KernelArgs &A, const uint3
     bvh_walk_begin(W, INFINITY);
     float light_dist = 0;
     int state = BVH_FETCH;
-    uint32_t r = 0, spins = 0;
+    uint32_t r = 0, spins = 0, issued = 0;
     WaveChunk chunk{0u, 0u};
     for (;;) {
         if (MODE == BVH_CHECKED && ++spins > (1u << 22)) { bvh_at<MODE>(A, spins, 0u, 15); break; }   // (a loop that does not end: say so and leave)
@@ -784,6 +785,7 @@ __device__ __forceinline__ void bvh_shadow_rays(const KernelArgs &A, const uint3
                     if (atomicMax(dg + 0, W.steps) < W.steps) dg[1] = r;
                     atomicAdd(dg + 2, W.steps >> 4);
                     if (W.steps >= 1024u) atomicAdd(dg + 3, 1u);
+                    atomicAdd(dg + 4, W.steps); atomicAdd(dg + 5, 1u);   // every step of every walk, and the walks: the useful lane-steps
                 }
                 if (W.give_up) { A.f->s_counts[SC_GUARD] = 1; A.f->s_counts[SC_OVERFLOW] = 1; }   // a ray the filter cannot take: the frame goes to the last resort
                 A.f->s_occluded[r] = W.have ? 1 : 0;
@@ -821,18 +823,120 @@ __device__ __forceinline__ void bvh_shadow_rays(const KernelArgs &A, const uint3
             }
         }
         if (!__ballot(state != BVH_OUT)) break;
+        if (MODE == BVH_TALLY && __ballot(state == BVH_WALK)) issued += (uint32_t)BVH_STEPS;   // (wave-uniform: the turn below runs all its steps for the wave if one lane walks)
         if (state == BVH_WALK) {
             for (int it = 0; it < BVH_STEPS; ++it)
                 if (state == BVH_WALK && !bvh_step<1, MODE>(A, R, false, light_dist, every_mesh, W, stack, nbox, ntri)) state = BVH_FINISHED;
         }
     }
+    if (MODE == BVH_TALLY && lane == 0) atomicAdd(A.f->s_counts + SC_BVH_DIAG + 46, issued);   // steps the wave issued, each a slot for 64 lanes
     exec_counters_flush(A, nbox, ntri, lane);
 }
-template <uint32_t pass, int MODE>  // (the passes are kernels of their own in a profile)
+
+// The bulk shadow pass BY PIXEL (a frame with fixed slots, not the GI mode: crt_launch.hip): the work item is level-0 ray r, not a slot.
+// A lane takes r's record {P, marker} {N, 0}, walks the pixel's lights one after the other -- as the level queue's lanes do for the hits they
+// shade (BVH_SHADOWS) -- and adds up what resolve_leaf would: ax += k * albedo for every light that is not blocked, from 0, in the lights'
+// order, in those very expressions.  After the last light it stores the sum into the pixel's root node as a constant leaf: stream_resolve
+// takes its TN_CONST branch for the pixel and loads neither flags nor factors.  Nothing is written to s_kfac or s_occluded, nothing is
+// inverted (level0_slot_owner), and a pixel's record is read by one lane instead of by n_lights lanes of n_lights waves.
+//   * a marker of SHADOW_SLOT_UNUSED: no diffuse hit (or no pixel) -- the lane is free again; every other record's root is TN_DIFFUSE
+//     without TN_GI by construction (shade_hit), and nothing reads such a node between level 0 and the resolve: the deeper levels write
+//     nodes of their own, the queries have scratch of their own
+//   * a light with kfac == 0 is not walked and counts as not blocked; its add is still executed (+-0, or NaN for a non-finite albedo)
+//   * a walk is bvh_shadow_rays' walk: bvh_walk_begin resets everything a lane carries from one walk to the next (cache_mesh, cache_k2 among
+//     it), so a ray executes the tests it executes there and the tallies are the slot pass's
+//   * the next light starts every BVH_PIXEL_RESTART steps inside a turn, in the lane, without a cursor or a ballot; a new PIXEL is the
+//     wave's business and keeps the slot pass's rule (BVH_BATCH free lanes), 64 consecutive r -- one 8x8 tile -- to a fresh wave
+//   * no lights: level 0 wrote no records, and resolve_leaf's sum over no lights is what the TN_DIFFUSE nodes give: nothing to do
+//   * SC_OVERFLOW set: the pass returns at once, with some roots rewritten and others not -- harmless: render_lanes redoes the frame from
+//     scratch, and the next frame's level 0 writes every root again
+constexpr int BVH_PIXEL_RESTART = 8;   // steps between two looks at lanes whose light has ended (measured 2 / 4 / 8 / 16: HW14 835 / 836 / 853 / 846 Mpixels/s)
+static_assert(BVH_STEPS % BVH_PIXEL_RESTART == 0, "a turn is a whole number of restart intervals");
+template <int MODE>
+__device__ __forceinline__ void bvh_shadow_pixels(const KernelArgs &A, uint32_t *stack_lds) {
+    const uint32_t lane = threadIdx.x & 63u;
+    if (A.f->s_counts[SC_OVERFLOW]) return;
+    const uint32_t n_lights = A.s->n_lights;
+    if (!n_lights) return;
+    const uint32_t total = stream_level_count(A, 0);
+    uint32_t *cursor = A.f->s_counts + SC_SHADOW_FETCH;
+    const BvhStack stack = bvh_stack_of(A, stack_lds, BVH_SPILL_SIDE);   // (where the slot pass runs: beside the level kernels and the level queue's launch)
+    uint32_t nbox = 0, ntri = 0;
+    Ray R;
+    R.ox = R.oy = R.oz = R.dx = R.dy = R.dz = R.ix = R.iy = R.iz = 0; R.parmask = 0;
+    BvhWalk W;
+    bvh_walk_begin(W, INFINITY);
+    float light_dist = 0, kfac = 0, ax = 0, ay = 0, az = 0, albx = 0, alby = 0, albz = 0;
+    int state = BVH_FETCH;   // BVH_SHADOWS: holds a pixel, its light `li` is to start; BVH_WALK: walks towards it
+    uint32_t r = 0, li = 0, spins = 0, issued = 0;
+    WaveChunk chunk{0u, 0u};
+    // light li of the lane's pixel has ended: its term, then the next light or the pixel's colour
+    auto light_ended = [&](const bool blocked) {
+        if (!blocked) { ax += kfac * albx; ay += kfac * alby; az += kfac * albz; }   // resolve_leaf's expressions
+        if (++li == n_lights) {
+            A.f->s_nodes[2 * (size_t)r] = make_float4(ax, ay, az, __uint_as_float(TN_CONST));
+            state = BVH_FETCH;
+        } else state = BVH_SHADOWS;
+    };
+    for (;;) {
+        if (MODE == BVH_CHECKED && ++spins > (1u << 22)) { bvh_at<MODE>(A, spins, 0u, 15); break; }   // (a loop that does not end: say so and leave)
+        const uint32_t n_free = (uint32_t)__popcll(__ballot(state == BVH_FETCH));
+        if (n_free >= BVH_BATCH || (n_free && !__ballot(state == BVH_WALK || state == BVH_SHADOWS))) {
+            const uint32_t claimed = wave_fetch_chunked(cursor, lane, state == BVH_FETCH, chunk, A.chunk, total);
+            if (state == BVH_FETCH) {   // (one fetch per free lane and round, as in bvh_shade_level)
+                r = claimed;
+                if (r >= total) state = BVH_OUT;
+                else {
+                    const float4 p = A.f->s_shadowq[2 * (size_t)r], n0 = A.f->s_nodes[2 * (size_t)r];
+                    if (__float_as_uint(p.w) != SHADOW_SLOT_UNUSED) {
+                        const uint32_t kind = __float_as_uint(n0.w);
+                        if ((kind & (TN_KIND_MASK | TN_GI)) != TN_DIFFUSE) bvh_at<MODE>(A, kind, 0u, 13);   // (cannot happen; the bounds-checked build says so)
+                        else { albx = n0.x; alby = n0.y; albz = n0.z; ax = ay = az = 0; li = 0; state = BVH_SHADOWS; }
+                    }
+                }
+            }
+        }
+        if (!__ballot(state != BVH_OUT)) break;
+        for (int part = 0; part < BVH_STEPS / BVH_PIXEL_RESTART; ++part) {
+            if (state == BVH_SHADOWS) {
+                // (the record once more per light: an L1 / L2 hit, against six registers held through every walk)
+                const float4 p = A.f->s_shadowq[2 * (size_t)r], n = A.f->s_shadowq[2 * (size_t)r + 1];
+                light_setup(A, li, p.x, p.y, p.z, n.x, n.y, n.z, R, light_dist, kfac);
+                if (kfac == 0.0f) light_ended(false);   // a light behind the surface: no walk (kernel_plan.h has the argument)
+                else {
+                    // an occluding hit has length(o + d t - o) <= light_dist with |d| = 1 up to two unit roundoffs: t <= light_dist (1 + 2^-16) (NaN: no bound)
+                    bvh_walk_begin(W, light_dist * (1.0f + 0x1p-16f));
+                    if (bvh_ray_setup(A, R, W.B)) state = BVH_WALK;
+                    else { A.f->s_counts[SC_GUARD] = 1; A.f->s_counts[SC_OVERFLOW] = 1; light_ended(false); }   // a ray the filter cannot take: the frame goes to the last resort
+                }
+            }
+            if (MODE == BVH_TALLY && __ballot(state == BVH_WALK)) issued += (uint32_t)BVH_PIXEL_RESTART;   // (wave-uniform, as in the slot pass)
+            for (int it = 0; it < BVH_PIXEL_RESTART; ++it)
+                if (state == BVH_WALK && !bvh_step<1, MODE>(A, R, false, light_dist, false, W, stack, nbox, ntri)) {
+                    if (MODE == BVH_TALLY) {   // diagnostics, as the slot pass's: the longest walk, which pixel's, all steps, walks of 1024 steps and more
+                        uint32_t *dg = A.f->s_counts + SC_BVH_DIAG + 40;
+                        if (atomicMax(dg + 0, W.steps) < W.steps) dg[1] = r;
+                        atomicAdd(dg + 2, W.steps >> 4);
+                        if (W.steps >= 1024u) atomicAdd(dg + 3, 1u);
+                        atomicAdd(dg + 4, W.steps); atomicAdd(dg + 5, 1u);   // every step of every walk, and the walks: the useful lane-steps
+                    }
+                    if (W.give_up) { A.f->s_counts[SC_GUARD] = 1; A.f->s_counts[SC_OVERFLOW] = 1; }
+                    light_ended(W.have);
+                }
+        }
+    }
+    if (MODE == BVH_TALLY && lane == 0) atomicAdd(A.f->s_counts + SC_BVH_DIAG + 46, issued);
+    exec_counters_flush(A, nbox, ntri, lane);
+}
+template <uint32_t pass, int MODE, bool PIXELS = false>  // (the passes are kernels of their own in a profile; PIXELS: pass 0 by pixel, bvh_trace_shadow<0u, MODE, true>)
 __global__ __launch_bounds__(BLOCK) void bvh_trace_shadow(const KernelArgs A) {
     __shared__ uint32_t stack_lds[BVH_LDS_STACK * BLOCK];
-    const uint32_t split = A.f->s_counts[SC_SHADOW_SPLIT];
-    bvh_shadow_rays<MODE, pass == 0>(A, pass == 0 ? 0u : split, pass == 0 ? split : A.f->s_counts[SC_SHADOW] - split,
-                          A.f->s_counts + (pass == 0 ? SC_SHADOW_FETCH : SC_SHADOW_FETCH2), stack_lds);
+    static_assert(!PIXELS || pass == 0, "only level 0's slots are fixed ones");
+    if constexpr (PIXELS) bvh_shadow_pixels<MODE>(A, stack_lds);
+    else {
+        const uint32_t split = A.f->s_counts[SC_SHADOW_SPLIT];
+        bvh_shadow_rays<MODE, pass == 0>(A, pass == 0 ? 0u : split, pass == 0 ? split : A.f->s_counts[SC_SHADOW] - split,
+                              A.f->s_counts + (pass == 0 ? SC_SHADOW_FETCH : SC_SHADOW_FETCH2), stack_lds);
+    }
 }
 

@@ -163,8 +163,9 @@ struct FrameArgs {
                                   // front of that range (fixed0) one record per level-0 ray instead: {hit point, marker} {normal, 0} (kernel_stream.h: level0_shadow_ray)
     uint8_t *s_occluded;          // one flag per shadow ray
     float *s_kfac;                // ... and its light factor, by the same index (written by shade_hit beside a queued ray, by whoever walks a fixed slot): with the
-                                  // flag all that stream_resolve reads of a slot
-    float4 *s_nodes;              // ray-tree nodes (TNode), 2 x float4 each
+                                  // flag all that stream_resolve reads of a slot.  (The filter kernels' bulk pass by pixel -- kernel_bvh.h: bvh_shadow_pixels --
+                                  // touches neither for a fixed slot: it leaves the pixel's direct light in its root node)
+    float4 *s_nodes;              // ray-tree nodes (TNode), 2 x float4 each; a level-0 root that is a diffuse leaf becomes a TN_CONST leaf in that pass
     uint32_t *s_counts;           // SC_WORDS counters / cursors, zeroed before every frame (all of the block but SC_FALLBACK_TOTAL)
     uint32_t s_ray_cap, s_shadow_cap, s_node_cap;
     uint32_t *fallback_total;     // frames redone by the queue-less kernel since crt_create (never reset): s_counts + SC_FALLBACK_TOTAL

@@ -23,6 +23,11 @@
 // at s_shadowq[2 r], and whoever walks fixed slot s finds its ray and light (shadow_place.h: level0_slot_owner), rebuilds the ray with
 // light_setup -- the expressions shade_hit used to store the results of -- and stores the factor in s_kfac (level0_shadow_ray).  n_lights
 // rays of 32 bytes per pixel became one record: level 0 writes a quarter of what it did, the bulk pass reads 64 consecutive records per refill.
+// The filter kernels' bulk pass (kernel_bvh.h: bvh_shadow_pixels; not the GI mode) goes one step further and walks the RECORDS, not the slots:
+// a lane reads record r once, walks the pixel's lights in turn and stores sum over open lights of k * albedo -- resolve_leaf's sum -- into
+// root node r as a TN_CONST leaf.  For such a frame nobody writes or reads the flag or the factor of a fixed slot; stream_resolve finds a
+// constant where the diffuse hit was.  The slot layout stays for everyone else: the GI mode, the plan and reference-order kernels, the
+// wave-per-ray kernel (level0_shadow_ray), and the deeper levels' slots, which hold rays.
 //
 // All rays of a level are independent, so each launch has millions of rays of parallelism and no lane ever
 // waits for a recursion.  Queues, the ray tree and the flags live in HBM (a few hundred MB at 1080p).
