@@ -181,6 +181,7 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_st
                   "crt_get_query_stats", "crt_shade_hits", "crt_shade_hits_device", "crt_light_points", "crt_light_points_device",
                   "crt_shoot_rays", "crt_shoot_rays_device", "crt_get_shoot_stats", "crt_shoot_rays_gi", "crt_shoot_rays_gi_device",
                   "crt_shoot_rays_enqueue", "crt_shoot_rays_gi_enqueue", "crt_get_shoot_report", "crt_query_scratch_generation",
+                  "crt_camera_sample_rays_device", "crt_accumulate_samples_device", "crt_render_progressive", "crt_progressive_samples",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -246,6 +247,11 @@ def lib():
     L.crt_get_shoot_report.argtypes = [vp, C.POINTER(ShootReport)]
     L.crt_query_scratch_generation.argtypes = [vp]
     L.crt_query_scratch_generation.restype = C.c_uint64
+    L.crt_camera_sample_rays_device.argtypes = [vp, u32, u32, vp, C.c_uint64, vp, vp, vp]
+    L.crt_accumulate_samples_device.argtypes = [vp, vp, vp, C.c_uint64, u32, vp, vp, vp]
+    L.crt_render_progressive.argtypes = [vp, C.POINTER(Options), u32, u32, vp]
+    L.crt_progressive_samples.argtypes = [vp]
+    L.crt_progressive_samples.restype = u32
     L.crt_host_shoot_stats_layout.argtypes = [C.POINTER(u32), u32]
     L.crt_host_shoot_stats_layout.restype = u32
     L.crt_get_kernel_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -758,6 +764,47 @@ class Tracer:
         """Changes whenever a query scratch array is reallocated: a graph captured from an enqueue call is valid while it stays."""
         self._single("query_scratch_generation")
         return int(lib().crt_query_scratch_generation(self.ctx))
+
+    # ---- progressive GI frames (include/crt_hip.h: crt_camera_sample_rays_device, crt_accumulate_samples_device, crt_render_progressive)
+    def camera_sample_rays_device(self, gi_seed, sample, d_rays_ptr, n=None, d_keys_ptr=None, d_pixels_ptr=None, stream_ptr=None):
+        """The rays (float32 [n, 6]) and keys (uint32 [n], or None) of sample `sample` of the pixels listed in d_pixels_ptr (uint32 [n],
+        row-major indices) or, without a list, of every pixel of the frame (n = H * W): sample 0 through the pixel centre, the others
+        jittered by the key's numbers.  Enqueues on the stream and returns."""
+        self._single("camera_sample_rays_device")
+        n = self.width * self.height if n is None else n
+        self._check(lib().crt_camera_sample_rays_device(self.ctx, int(gi_seed), int(sample), C.c_void_p(d_pixels_ptr or 0), n,
+                                                        C.c_void_p(d_rays_ptr), C.c_void_p(d_keys_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def accumulate_samples_device(self, d_rgb_ptr, sample, d_sum_ptr, d_mean_ptr=None, n=None, d_pixels_ptr=None, stream_ptr=None):
+        """One step of the frame's fold: sum[p] = (0 if sample == 0 else sum[p]) + rgb[i], mean[p] = sum[p] * (1 / (sample + 1)) for the
+        listed pixels (distinct!) or all of them; sum and mean are float32 [H * W * 3] device arrays of the caller's.  Enqueues and returns."""
+        self._single("accumulate_samples_device")
+        n = self.width * self.height if n is None else n
+        self._check(lib().crt_accumulate_samples_device(self.ctx, C.c_void_p(d_rgb_ptr), C.c_void_p(d_pixels_ptr or 0), n, int(sample),
+                                                        C.c_void_p(d_sum_ptr), C.c_void_p(d_mean_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def progressive_samples(self) -> int:
+        """Samples folded into the context's progressive frame so far (0 after set_camera or a render)."""
+        self._single("progressive_samples")
+        return int(lib().crt_progressive_samples(self.ctx))
+
+    def render_progressive(self, options, samples, per_call=1, on_pass=None, first_sample=0):
+        """The GI frame of `options` (use_gi set; rays_per_pixel is not read) with `samples` rays per pixel, per_call samples a call: every
+        pixel of the frame, bit for bit the one-shot frame when the last call is in.  on_pass(samples_done, mean) is called after every
+        call with the frame so far (float32 [H, W, 3], the caller's to keep) and may return False to stop.  first_sample > 0 continues
+        the context's frame (it must equal progressive_samples()).  Returns the last mean."""
+        self._single("render_progressive")
+        if per_call < 1:
+            raise ValueError("per_call: at least one sample a call")
+        rgb = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        done = int(first_sample)
+        while done < samples:
+            k = min(int(per_call), samples - done)
+            self._check(lib().crt_render_progressive(self.ctx, C.byref(options), done, k, _p(rgb)))
+            done += k
+            if on_pass is not None and on_pass(done, rgb.copy()) is False:
+                break
+        return rgb
 
     def shoot_stats(self) -> ShootStats:
         """rays / levels / level_rays / shadow_records / rerouted / kernel_ms of the last radiance query (waits for it)."""

@@ -16,7 +16,8 @@ int main(int argc, char **argv) {
   if (argc < 3) {
     std::fprintf(stderr,
                  "usage: %s scene.crtscene out.ppm [--folder DIR] [--depth N] [--mode 0..9] [--device D | --devices 0-7 | --devices 0,2,5] [--repeat K]\n"
-                 "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL [--seed S]]   (RenderOptions::USE_GI, RayTracer.h:27-30)\n"
+                 "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL [--seed S] [--progressive K]]   (RenderOptions::USE_GI, RayTracer.h:27-30;\n"
+                 "        --progressive: the same frame K samples a call, in memory that does not depend on RAYS_PER_PIXEL)\n"
                  "       [--probe ROW COL]   (no render: the closest hit of that pixel's camera ray; out.ppm is not written)\n",
                  argv[0]);
     return 2;
@@ -26,7 +27,7 @@ int main(int argc, char **argv) {
   int mode = crt::BVHBucketsThreadPool, device = 0, repeat = 1;
   std::vector<int> devices;  // --devices: the frame's tiles over several GPUs (first one gathers)
   bool useGI = false;
-  unsigned giSamples = 2, raysPerPixel = 1, seed = 0;
+  unsigned giSamples = 2, raysPerPixel = 1, seed = 0, progressive = 0;
   bool probe = false;
   unsigned probeRow = 0, probeCol = 0;
   for (int i = 3; i < argc; i++) {
@@ -49,7 +50,12 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--repeat") && i + 1 < argc) repeat = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--gi") && i + 2 < argc) { useGI = true; giSamples = (unsigned)atoi(argv[++i]); raysPerPixel = (unsigned)atoi(argv[++i]); }
     else if (!strcmp(argv[i], "--seed") && i + 1 < argc) seed = (unsigned)strtoul(argv[++i], nullptr, 0);
+    else if (!strcmp(argv[i], "--progressive") && i + 1 < argc) progressive = (unsigned)atoi(argv[++i]);
     else if (!strcmp(argv[i], "--probe") && i + 2 < argc) { probe = true; probeRow = (unsigned)atoi(argv[++i]); probeCol = (unsigned)atoi(argv[++i]); }
+  }
+  if (progressive && (!useGI || devices.size() > 0)) {
+    std::fprintf(stderr, "error: --progressive needs --gi and one device\n");
+    return 2;
   }
   try {
     crt::SceneParser parser;
@@ -75,7 +81,8 @@ int main(int argc, char **argv) {
     double best = 1e30;
     for (int r = 0; r < repeat; r++) {
       auto a = std::chrono::high_resolution_clock::now();
-      tracer.render(r + 1 == repeat ? outPath : std::string(), options);
+      if (progressive) tracer.renderProgressive(r + 1 == repeat ? outPath : std::string(), options, progressive);
+      else tracer.render(r + 1 == repeat ? outPath : std::string(), options);
       auto b = std::chrono::high_resolution_clock::now();
       best = std::min(best, std::chrono::duration<double>(b - a).count());
     }

@@ -164,6 +164,7 @@ CRT_INTERNAL void note_overflow(crt_ctx *ctx);
 CRT_INTERNAL int fetch_counters(crt_ctx *ctx, const crt_options *o, uint64_t pixels);
 // ---- crt_query.hip
 CRT_INTERNAL void query_destroy(crt_ctx *ctx);
+CRT_INTERNAL void query_progressive_reset(crt_ctx *ctx);   // crt_set_camera, crt_render*: crt_progressive_samples is 0 again
 // ---- crt_abi.hip
 CRT_INTERNAL uint64_t coverage_items(uint32_t width, uint32_t height, const crt_rect *rects, uint32_t n_rects, std::vector<WorkItem> &items);
 CRT_INTERNAL void launch_unpack_items(const float *packed, const WorkItem *items, uint32_t n_items, float *frame, uint32_t width, uint32_t height,

@@ -16,6 +16,9 @@
 //   a radiance pass   shoot_pass: shoot_down (level behind level), shoot_up, shoot_numbers.  The synchronous and the enqueue form part in
 //                     shoot_children (a level's room and size), clear_words and shoot_numbers -- and in shoot_up's choice of build --,
 //                     and nowhere in the level loop
+//   a progressive frame  crt_render_progressive, at the end of this file: a GI frame sample pass by sample pass -- the rays and keys of one
+//                     sample (crt_camera_sample_rays_device), shoot_run, one step of the pixel's fold (crt_accumulate_samples_device);
+//                     kernels: csrc/kernel_progressive.h
 #include "crt_internal.h"
 #include "glibc_powf.h"
 #include "gi_random.h"
@@ -35,6 +38,7 @@ namespace {
 #include "kernel_query.h"
 #include "kernel_shade.h"
 #include "kernel_radiance.h"
+#include "kernel_progressive.h"
 #pragma clang diagnostic pop
 
 // radiance queries: what a level may hold at most is SHOOT_LEVEL_RAYS (shoot_caps.h: a level is at most twice as wide as the one above
@@ -203,6 +207,12 @@ struct crt_query_state {
     DeviceArray<unsigned long long> d_hits0;  // level 0's hits: QW_HITS as the level's trace left it (the lighting launches add to that word)
     crt_shoot_report report{};                // of the last enqueue call outside a capture
     uint64_t generation = 0;                  // crt_query_scratch_generation
+    // crt_render_progressive: the frame's H*W*3 sums, one sample's rays, keys and colours for every pixel, the samples folded in so far
+    DeviceArray<float> prog_sum, prog_rgb;
+    DeviceArray<crt_ray> prog_rays;
+    DeviceArray<uint32_t> prog_keys;
+    uint32_t prog_samples = 0;
+    uint64_t level_peak[MAX_GENERATIONS] = {};   // the widest level g of a pass since a progressive frame's sample 0 began (shoot_numbers)
     // the radiance queries' own device words: made by the first radiance call of a context (shoot_words_reserve)
     bool shoot_words_made() const { return swords.p && d_report.p && d_hits0.p; }
     ~crt_query_state() {
@@ -219,6 +229,11 @@ static void query_scratch_changed(crt_ctx *ctx) {
 void query_destroy(crt_ctx *ctx) {
     delete ctx->query;
     ctx->query = nullptr;
+}
+
+// crt_set_camera and crt_render*: the progressive frame under way, if any, is no longer the context's frame
+void query_progressive_reset(crt_ctx *ctx) {
+    if (ctx->query) ctx->query->prog_samples = 0;
 }
 
 // a radiance pass's numbers, once its last copy has arrived
@@ -642,7 +657,10 @@ static int shoot_numbers(crt_ctx *ctx, const ShootPass &P, const bool level0) {
             CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->pin->shoot + SH_HITS0, hits, sizeof(uint64_t), hipMemcpyDeviceToHost, P.stream));
             return CRT_OK;
         }
-        for (uint32_t g = 0; g <= P.last; g++) q->shoot.level_rays[g] += P.level[g].n;
+        for (uint32_t g = 0; g <= P.last; g++) {
+            q->shoot.level_rays[g] += P.level[g].n;
+            q->level_peak[g] = std::max<uint64_t>(q->level_peak[g], P.level[g].n);
+        }
         q->shoot.levels = std::max(q->shoot.levels, P.last + 1);
         CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->pin->shoot + SH_DIFFUSE, diffuse, sizeof(uint64_t), hipMemcpyDeviceToHost, P.stream));
         CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->pin->shoot + SH_REROUTED, q->words.p + QW_REROUTED, sizeof(uint64_t), hipMemcpyDeviceToHost, P.stream));
@@ -943,3 +961,122 @@ extern "C" int crt_shoot_rays_gi_enqueue(crt_ctx *ctx, const crt_ray *d_rays, co
 }
 
 extern "C" uint64_t crt_query_scratch_generation(const crt_ctx *ctx) { return ctx && ctx->query ? ctx->query->generation : 0; }
+
+// ---- progressive GI frames (csrc/kernel_progressive.h): the frame's left fold over a pixel's samples, cut into sample passes.
+
+static QueryCamera camera_of(const crt_ctx *ctx) {
+    QueryCamera cam;
+    memcpy(cam.pos, ctx->frame.cam_pos, sizeof(cam.pos));   // crt_set_camera's last word, as crt_camera_rays_device takes it
+    memcpy(cam.m, ctx->frame.cam, sizeof(cam.m));
+    cam.width = ctx->width; cam.height = ctx->height;
+    return cam;
+}
+
+// what the two primitives ask of (d_pixels, n): without a list the call is for the whole frame; one thread per entry must fit a grid
+static int progressive_check(crt_ctx *ctx, const char *what, const uint32_t *d_pixels, const uint64_t n) {
+    const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
+    if (!d_pixels && n != pixels) {
+        ctx->error = std::string(what) + ": d_pixels is NULL, so n must be width * height = " + std::to_string(pixels) + ", not " + std::to_string(n);
+        return CRT_ERR_INVALID;
+    }
+    if (pixels > 0xFFFFFFFFull || (n + BLOCK - 1) / BLOCK > 0x7FFFFFFFull) {
+        ctx->error = std::string(what) + ": more pixels or entries than 32-bit pixel indices and one launch hold";
+        return CRT_ERR_INVALID;
+    }
+    return CRT_OK;
+}
+
+static int launch_sample_rays(crt_ctx *ctx, uint32_t gi_seed, uint32_t sample, const uint32_t *d_pixels, uint64_t n, crt_ray *d_rays, uint32_t *d_keys,
+                              hipStream_t stream) {
+    SampleRaysArgs P{};
+    P.cam = camera_of(ctx);
+    P.seed = gi_seed; P.sample = sample; P.pixels = d_pixels; P.n = n; P.rays = d_rays; P.keys = d_keys;
+    hipLaunchKernelGGL(progressive_sample_rays, dim3((uint32_t)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, P);
+    CRT_HIP_CHECK(ctx, hipGetLastError());
+    return CRT_OK;
+}
+
+static int launch_accumulate(crt_ctx *ctx, const float *d_rgb, const uint32_t *d_pixels, uint64_t n, uint32_t sample, float *d_sum, float *d_mean,
+                             hipStream_t stream) {
+    AccumulateArgs P{};
+    P.rgb = d_rgb; P.pixels = d_pixels; P.n = n; P.frame_pixels = (uint64_t)ctx->width * ctx->height; P.sample = sample; P.sum = d_sum; P.mean = d_mean;
+    hipLaunchKernelGGL(progressive_accumulate, dim3((uint32_t)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, P);
+    CRT_HIP_CHECK(ctx, hipGetLastError());
+    return CRT_OK;
+}
+
+extern "C" int crt_camera_sample_rays_device(crt_ctx *ctx, uint32_t gi_seed, uint32_t sample, const uint32_t *d_pixels, uint64_t n, crt_ray *d_rays,
+                                             uint32_t *d_keys, void *stream) {
+    const char *what = "crt_camera_sample_rays_device";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = progressive_check(ctx, what, d_pixels, n)) return rc;
+    if (n == 0) return CRT_OK;
+    if (!d_rays) { ctx->error = std::string(what) + ": d_rays is NULL"; return CRT_ERR_INVALID; }
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    return launch_sample_rays(ctx, gi_seed, sample, d_pixels, n, d_rays, d_keys, (hipStream_t)stream);
+}
+
+extern "C" int crt_accumulate_samples_device(crt_ctx *ctx, const float *d_rgb, const uint32_t *d_pixels, uint64_t n, uint32_t sample, float *d_sum,
+                                             float *d_mean, void *stream) {
+    const char *what = "crt_accumulate_samples_device";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = progressive_check(ctx, what, d_pixels, n)) return rc;
+    if (n == 0) return CRT_OK;
+    if (!d_rgb || !d_sum) { ctx->error = std::string(what) + ": d_rgb or d_sum is NULL"; return CRT_ERR_INVALID; }
+    if (sample == 0xFFFFFFFFu) { ctx->error = std::string(what) + ": sample + 1 does not fit 32 bits"; return CRT_ERR_INVALID; }
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    return launch_accumulate(ctx, d_rgb, d_pixels, n, sample, d_sum, d_mean, (hipStream_t)stream);
+}
+
+extern "C" uint32_t crt_progressive_samples(const crt_ctx *ctx) { return ctx && ctx->query ? ctx->query->prog_samples : 0u; }
+
+// Behind a frame's sample 0: room in the level arrays for later samples, whose levels differ from sample 0's by the pixels whose jittered
+// ray meets another material.  shoot_children reserves fan x a level's rays for the level below it; this reserves fan x (the widest such
+// level of sample 0's passes and a quarter more), never more than the level can hold at all (fan^g x a pass's rays).  A later sample that
+// still outgrows it grows the arrays as any radiance call does: only crt_query_scratch_generation tells.
+static int progressive_headroom(crt_ctx *ctx, const crt_options *o, const uint64_t pass_rays) {
+    crt_query_state *q = ctx->query;
+    const uint64_t fan = shoot_fan(o, true);
+    uint64_t most = pass_rays, widest = 0;
+    for (uint32_t g = 0; g < o->max_depth && q->level_peak[g]; g++) {
+        most = std::min<uint64_t>(most * fan, SHOOT_LEVEL_RAYS);
+        const uint64_t want = std::min(fan * (q->level_peak[g] + q->level_peak[g] / 4 + 64), most);
+        if (int rc = shoot_level_reserve(ctx, g + 1, want, true, true)) return rc;
+        widest = std::max(widest, want);
+    }
+    return query_list_reserve(ctx, widest);
+}
+
+extern "C" int crt_render_progressive(crt_ctx *ctx, const crt_options *options, uint32_t first_sample, uint32_t n_samples, float *out_rgb) {
+    const char *what = "crt_render_progressive";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n_samples == 0) return CRT_OK;
+    // the GI radiance calls' own check: the camera's rays are PRIMARY rays, the arrays are the context's
+    uint64_t pass = 0;
+    if (int rc = query_check(ctx, shoot_needs(what, ctx, options, ctx, CRT_RAY_PRIMARY, true, &pass))) return rc;
+    if (first_sample != 0 && first_sample != crt_progressive_samples(ctx)) {   // (0 starts a new frame, whatever the context holds)
+        ctx->error = std::string(what) + ": first_sample is " + std::to_string(first_sample) + ", but the context's frame holds " +
+                     std::to_string(crt_progressive_samples(ctx)) + " samples (crt_progressive_samples; 0 starts a new frame)";
+        return CRT_ERR_INVALID;
+    }
+    if ((uint64_t)first_sample + n_samples > 0xFFFFFFFFull) { ctx->error = std::string(what) + ": more than 2^32 - 1 samples"; return CRT_ERR_INVALID; }
+    const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
+    if (pixels == 0) return CRT_OK;
+    int rc;
+    if ((rc = progressive_check(ctx, what, nullptr, pixels)) || (rc = query_begin(ctx, ctx->stream, CALL_RADIANCE))) return rc;
+    crt_query_state *q = ctx->query;
+    if ((rc = reserve_all(ctx, q->prog_sum, 3 * pixels, q->prog_rgb, 3 * pixels, q->prog_rays, pixels, q->prog_keys, pixels))) return rc;
+    const ShootGi gi{q->prog_keys.p, 0u};
+    for (uint32_t s = first_sample; s - first_sample < n_samples; s++) {   // one at a time and in order: the fold's order is the frame's
+        if (s == 0) std::fill(q->level_peak, q->level_peak + MAX_GENERATIONS, 0ull);
+        if ((rc = launch_sample_rays(ctx, options->gi_seed, s, nullptr, pixels, q->prog_rays.p, q->prog_keys.p, ctx->stream)) ||
+            (rc = shoot_run(ctx, q->prog_rays.p, pixels, CRT_RAY_PRIMARY, options, q->prog_rgb.p, ctx->stream, pass, &gi)) ||
+            (rc = launch_accumulate(ctx, q->prog_rgb.p, nullptr, pixels, s, q->prog_sum.p, ctx->d_frame, ctx->stream)))
+            return rc;
+        q->prog_samples = s + 1;
+        if (s == 0 && (rc = progressive_headroom(ctx, options, std::min(pixels, pass)))) return rc;
+    }
+    if (out_rgb) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, ctx->d_frame, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return CRT_OK;
+}

@@ -629,5 +629,6 @@ extern "C" int crt_set_camera(crt_ctx *ctx, const float position[3], const float
     if (!ctx || !position || !matrix) return CRT_ERR_INVALID;
     memcpy(ctx->frame.cam_pos, position, 3 * sizeof(float));
     memcpy(ctx->frame.cam, matrix, 9 * sizeof(float));
+    query_progressive_reset(ctx);   // a progressive frame is one camera's
     return CRT_OK;
 }

@@ -1,5 +1,6 @@
 #include "RayTracer.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -329,6 +330,43 @@ std::vector<std::vector<Color>> RayTracer::render(const std::string &pathToImage
   const unsigned int W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
   int rc = renderFlat(pathToImage, ro, frame.data());
   if (rc != CRT_OK) throw std::runtime_error(std::string("render failed: ") + (multi ? crt_multi_last_error(multi) : crt_last_error(ctx)));
+  std::vector<std::vector<Color>> colorBuffer(H, std::vector<Color>(W));
+  for (unsigned int y = 0; y < H; y++)
+    for (unsigned int x = 0; x < W; x++) {
+      const float *p = &frame[((size_t)y * W + x) * 3];
+      colorBuffer[y][x] = Color(p[0], p[1], p[2]);
+    }
+  return colorBuffer;
+}
+
+std::vector<std::vector<Color>> RayTracer::renderProgressive(const std::string &pathToImage, RenderOptions ro, unsigned int samplesPerCall) {
+  if (multi) throw std::runtime_error("renderProgressive: not available on a multi-device tracer");
+  const unsigned int W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
+  crt_options o{};
+  o.max_depth = ro.MAX_DEPTH;
+  o.shadow_bias = ro.SHADOW_BIAS;
+  o.reflection_bias = ro.REFLECTION_BIAS;
+  o.refraction_bias = ro.REFRACTION_BIAS;
+  o.use_gi = ro.USE_GI ? 1u : 0u;
+  o.gi_sample_size = ro.GI_SAMPLE_SIZE;
+  o.monte_carlo_bias = ro.MONTE_CARLO_BIAS;
+  o.gi_seed = ro.USE_GI ? giSeed++ : 0u;  // as renderFlat takes it
+  const unsigned int samples = ro.RAYS_PER_PIXEL ? ro.RAYS_PER_PIXEL : 1u;  // (0 renders like 1, as in the reference)
+  samplesPerCall = std::min(std::max(samplesPerCall, 1u), samples);
+  const Matrix3 &m = camera.getRotationMatrix();
+  const float pos[3] = {camera.getPosition().x, camera.getPosition().y, camera.getPosition().z};
+  int rc = crt_set_camera(ctx, pos, &m.m[0][0]);  // (starts a new frame)
+  for (unsigned int done = 0; rc == CRT_OK && done < samples;) {
+    const unsigned int k = std::min(samplesPerCall, samples - done);
+    rc = crt_render_progressive(ctx, &o, done, k, done + k == samples ? frame.data() : nullptr);  // the host copy of the last call's mean only
+    done += k;
+  }
+  if (rc == CRT_OK && !pathToImage.empty()) {
+    std::vector<uint8_t> q((size_t)W * H * 3);
+    rc = crt_read_quantized(ctx, q.data());
+    if (rc == CRT_OK) writePPMQuantized(pathToImage, q.data(), W, H);
+  }
+  if (rc != CRT_OK) throw std::runtime_error(std::string("renderProgressive failed: ") + crt_last_error(ctx));
   std::vector<std::vector<Color>> colorBuffer(H, std::vector<Color>(W));
   for (unsigned int y = 0; y < H; y++)
     for (unsigned int x = 0; x < W; x++) {

@@ -117,6 +117,12 @@ class RayTracer {
   std::vector<float> shootRaysGI(const std::vector<crt_ray> &rays, const std::vector<uint32_t> &keys, const RenderOptions &renderOptions,
                                  unsigned int rayType = CRT_RAY_REFLECTION, crt_shoot_stats *stats = nullptr);
 
+  // ---- progressive GI frames (crt_hip.h: crt_render_progressive): render()'s USE_GI frame with renderOptions.RAYS_PER_PIXEL rays per
+  // pixel, samplesPerCall samples a call, in memory that does not depend on RAYS_PER_PIXEL; the frame's seed is taken as render() takes
+  // it.  EVERY pixel of the frame is rendered: where render()'s bucket grid covers the frame (RayTracer.cpp:141-152 can leave edge rows
+  // out) the PPM is render()'s byte for byte.  Single-device tracers only; USE_GI must be set.
+  std::vector<std::vector<Color>> renderProgressive(const std::string &pathToImage, RenderOptions renderOptions, unsigned int samplesPerCall = 1);
+
   // flat access for callers that do not want the vector-of-vectors copy
   int renderFlat(const std::string &pathToImage, const RenderOptions &renderOptions, float *outRGB, unsigned int counters = 0);
   crt_ctx *context() const { return multi ? crt_multi_context(multi, 0) : ctx; }

@@ -503,6 +503,51 @@ int crt_get_shoot_report(crt_ctx *ctx, crt_shoot_report *out);
 /* changes whenever any query scratch array is reallocated */
 uint64_t crt_query_scratch_generation(const crt_ctx *ctx);
 
+/* ---- Progressive GI frames: a frame with rays_per_pixel = R rendered sample pass by sample pass, in memory that does not depend on R,
+ * displayable after every pass, continuable, and THE ONE-SHOT FRAME BIT FOR BIT when the last pass is in.  Kernels: csrc/kernel_progressive.h
+ * around the GI radiance queries'.  Single-device contexts only.  No frame kernel is involved.
+ *
+ * The fold.  A GI frame's rule for pixel p is a plain left fold (RayTracer.cpp:90-104; oracle/cpu_ref.c: render_pixel): sum = 0;
+ *   sum = sum + c_s for s = 0 .. n - 1, where c_s is shootRay's colour for the ray of sample s under the key
+ *   crt_gi_mix(crt_gi_mix(gi_seed, p), s); sample 0 goes through the pixel centre, the others through (px + u(key, 0), py + u(key, 1));
+ *   the pixel is sum * (1 / (float)n).  A colour is a function of (scene, ray, key, options) alone, so the fold can be cut anywhere:
+ *   after samples 0 .. k in order, the mean below is the GI frame with rays_per_pixel = k + 1 -- the same floats, `0 + c_0` included.
+ * crt_camera_sample_rays_device: for i < n, pixel p = d_pixels ? d_pixels[i] : i (row-major); d_keys[i] = crt_gi_mix(crt_gi_mix(gi_seed,
+ *   p), sample) (d_keys may be NULL); d_rays[i] = RayTracer::getRay for that pixel with the camera of crt_set_camera: sample == 0 the
+ *   pixel centre -- crt_camera_rays_device's bits --, otherwise the jittered position above, the direction normalised ONCE, as getRay
+ *   returns it (crt_shoot_rays_gi* does shootRay's own normalisation on entry).  With d_pixels == NULL, n must be width * height:
+ *   anything else is CRT_ERR_INVALID.  With a list, an index >= width * height gives a ray with zero direction and key 0, and nothing
+ *   is read through that index.
+ * crt_accumulate_samples_device: for i < n and pixel p as above (the same rule for a NULL list), channel by channel
+ *   d_sum[3p + c] = (sample == 0 ? 0.0f : d_sum[3p + c]) + d_rgb[3i + c], and where d_mean != NULL
+ *   d_mean[3p + c] = d_sum[3p + c] * (1.0f / (float)(sample + 1)).  d_sum and d_mean are width * height * 3 floats of the caller's; an
+ *   out-of-range p is skipped.  THE PIXELS OF ONE CALL MUST BE DISTINCT: a pixel listed twice is two threads on one sum, the caller's
+ *   race.  Samples must arrive in order from 0 for the mean to be the frame's.
+ * Both only ENQUEUE on `stream` (a hipStream_t, NULL = default): no wait, no allocation, no readback, so they can be captured into a
+ *   hipGraph like crt_shoot_rays_gi_enqueue, with which they compose: rays and keys of a sample -> colours -> fold, on one stream.
+ *   Pixel lists give adaptive sampling to a caller who wants it.
+ * crt_render_progressive: samples first_sample .. first_sample + n_samples - 1 of EVERY pixel of the frame (render()'s bucket grid can
+ *   leave edge rows of a frame unrendered; this call has no grid), shot through crt_shoot_rays_gi_device's path in its usual passes --
+ *   the level arrays are bounded by one pass whatever the sample count --, one sample at a time and in order, and folded into a
+ *   context-owned width * height * 3 sum (allocated on first use, freed by crt_destroy).  The mean goes to the context's persistent colour
+ *   buffer, so crt_read_quantized works unchanged, and to out_rgb (host memory, may be NULL); the call returns when it is there.
+ *   Of `options` the fields crt_shoot_rays_gi* reads are read, and gi_seed; rays_per_pixel is NOT read.
+ *   first_sample == 0 starts a new frame, whatever the context holds.  CRT_ERR_INVALID, with nothing changed: any other
+ *   first_sample != crt_progressive_samples(ctx);
+ *   use_gi == 0; whatever the GI radiance calls refuse (gi_sample_size > 64, max_depth + 1 > 64, levels that cannot be held, NULL options).
+ *   n_samples == 0 is CRT_OK and touches nothing.  crt_set_camera and crt_render* reset crt_progressive_samples to 0.
+ *   The call waits for a pending crt_render_async frame, as the queries do; it leaves crt_stats, the ray queues' sizing and
+ *   fallback_frames as they were; crt_get_shoot_stats describes the last sample.  Behind a frame's sample 0 the level arrays are given a
+ *   quarter of headroom, so that later samples -- whose levels differ by the pixels whose jittered ray meets another material -- do not
+ *   regrow them (crt_query_scratch_generation tells when one did). */
+int crt_camera_sample_rays_device(crt_ctx *ctx, uint32_t gi_seed, uint32_t sample, const uint32_t *d_pixels, uint64_t n, crt_ray *d_rays,
+                                  uint32_t *d_keys, void *stream);
+int crt_accumulate_samples_device(crt_ctx *ctx, const float *d_rgb, const uint32_t *d_pixels, uint64_t n, uint32_t sample, float *d_sum,
+                                  float *d_mean, void *stream);
+int crt_render_progressive(crt_ctx *ctx, const crt_options *options, uint32_t first_sample, uint32_t n_samples, float *out_rgb);
+/* samples folded into the context's sum so far */
+uint32_t crt_progressive_samples(const crt_ctx *ctx);
+
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
  * stream per listed device (a device may be listed more than once); the covered 8x8 tiles are dealt round-robin, every
