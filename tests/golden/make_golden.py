@@ -21,6 +21,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import degenerate_sets  # noqa: E402
 import scale_sets  # noqa: E402
 from helpers import small_case  # noqa: E402
 from oracle import oracle_api as oa  # noqa: E402
@@ -177,9 +178,35 @@ def scale_frames():
               len(np.unique(rgb.reshape(-1, 3), axis=0)))
 
 
+def degenerate():
+    """The real reference's frame of the scenes with ill-formed triangles (tests/degenerate_sets.py: zero-area, underflowing near-collinear,
+    needle): what pins the oracle -- and through it every kernel path -- on NaN hits and the plane triangle.  `mixed` also keeps the
+    reference's own PPM: NaN * 255 through PPMColor's conversion on x86 (Color.cpp:12-21)."""
+    oa.build()
+    for case in degenerate_sets.CASES:
+        scene, _ = degenerate_sets.build(sc, case)
+        blob = sc.to_blob(scene)
+        ppm = None
+        with tempfile.TemporaryDirectory() as td:
+            ppm_path = os.path.join(td, "out.ppm") if case == "mixed" else None
+            rgb, _ = oa.reference_render(blob, max_depth=degenerate_sets.DEPTH, ppm_path=ppm_path)
+            if ppm_path:
+                ppm = open(ppm_path, "rb").read()
+        rgb_bvh, _ = oa.reference_render(blob, max_depth=degenerate_sets.DEPTH, mode="bvh")
+        same = (rgb.view(np.uint32) == rgb_bvh.view(np.uint32)) | (np.isnan(rgb) & np.isnan(rgb_bvh))
+        assert same.all(), case
+        out = {"blob": np.frombuffer(blob, dtype=np.uint8), "depth": np.int32(degenerate_sets.DEPTH), "rgb": rgb}
+        if ppm is not None:
+            out["ppm_gz"] = np.frombuffer(gzip.compress(ppm, 9, mtime=0), dtype=np.uint8)
+        np.savez_compressed(os.path.join(HERE, "degenerate_%s.npz" % case), **out)
+        print("degenerate", case, rgb.shape, "blob", len(blob), "bytes, NaN pixels", int(np.isnan(rgb).any(axis=2).sum()))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "gi":
         gi_stats()
+    elif len(sys.argv) > 1 and sys.argv[1] == "degenerate":
+        degenerate()
     elif len(sys.argv) > 1 and sys.argv[1] == "scale":
         scale_cases()
         scale_frames()
@@ -188,3 +215,4 @@ if __name__ == "__main__":
         gi_stats()
         scale_cases()
         scale_frames()
+        degenerate()

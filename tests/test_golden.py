@@ -42,6 +42,10 @@ def test_quantiser_truncates(oracle):
     q = oracle.quantize(v)
     assert q.tolist() == [0, 0, 0, int(np.float32(0.00392157) * np.float32(255)), 127, 254, 255, 255,
                           int(np.float32(254.9999 / 255) * np.float32(255))]
+    # std::clamp passes a NaN on (both compares are false), and the x86 conversion of NaN * 255 to an integer gives 0 in the low bits
+    # that PPMColor keeps (Color.cpp:12-21; tests/golden/degenerate_mixed.npz holds the reference's own bytes for such pixels)
+    odd = np.array([np.nan, -np.nan, np.inf, -np.inf], dtype=np.float32)
+    assert oracle.quantize(odd).tolist() == [0, 0, 255, 0]
 
 
 def test_blob_roundtrip(scenes):

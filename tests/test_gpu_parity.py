@@ -180,7 +180,8 @@ def test_uncovered_pixels_keep_their_previous_value(pkg, scenes, oracle):
 
 
 def test_empty_and_degenerate_scenes(pkg, scenes, oracle):
-    # no objects at all; a mesh with a degenerate (zero-area) triangle; a constant-material mesh; no lights
+    # no objects at all; a constant-material mesh; no lights; a frame that is no multiple of the tile (zero-area, near-collinear and
+    # needle triangles: tests/test_gpu_degenerate.py)
     base = scenes.make("hw07", width=48, height=32, detail=0.3)
     empty = dict(base, objects=[])
     t = make_tracer(pkg, scenes, empty)

@@ -4,6 +4,7 @@ binary); skipped elsewhere."""
 import numpy as np
 import pytest
 
+import degenerate_sets
 import scale_sets
 from helpers import assert_same_floats
 
@@ -44,6 +45,19 @@ def test_restatement_is_bit_exact_at_scale(oracle, scenes, base, case):
     got, _ = oracle.OracleScene(blob).render(3)
     assert len(np.unique(want.reshape(-1, 3), axis=0)) > 50          # a picture, not a blank frame
     assert_same_floats(got, want, "%s %s" % (base, case))
+
+
+def test_restatement_is_bit_exact_on_ill_formed_triangles(oracle, scenes):
+    # tests/degenerate_sets.py's `mixed` scene (zero-area, underflowing near-collinear and needle triangles) at another frame size than its fixture
+    if not _have(oracle, True):
+        pytest.skip("oracle/_ref not built here")
+    scene, _ = degenerate_sets.build(scenes, "mixed")
+    scene["settings"] = dict(scene["settings"], image_settings={"width": 72, "height": 48, "bucket_size": 16})
+    blob = scenes.to_blob(scene)
+    want, _ = oracle.reference_render(blob, max_depth=degenerate_sets.DEPTH)
+    got, _ = oracle.OracleScene(blob).render(degenerate_sets.DEPTH)
+    assert np.isnan(want).any()                                        # NaN winners are on this frame too
+    assert_same_floats(got, want, "mixed")
 
 
 def test_camera_change_matches_reference(oracle, scenes):
