@@ -131,6 +131,22 @@ class ShootReport(C.Structure):
                 ("hits", C.c_uint64), ("shadow_records", C.c_uint64), ("rerouted", C.c_uint64)]
 
 
+class Adaptive(C.Structure):
+    """crt_adaptive: the stopping rule's settings of an adaptively sampled GI frame (make_adaptive fills it)"""
+    _fields_ = [("size", C.c_uint32), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("threshold", C.c_float), ("floor", C.c_float)]
+
+
+def make_adaptive(**fields):
+    """crt_adaptive_defaults (4, 64, 0.05, 1e-4) with the given fields replaced, e.g. make_adaptive(min_samples=2, max_samples=8)."""
+    a = Adaptive()
+    lib().crt_adaptive_defaults(C.byref(a))
+    for k, v in fields.items():
+        if k not in dict(Adaptive._fields_) or k == "size":
+            raise KeyError("crt_adaptive has no field %r" % k)
+        setattr(a, k, v)
+    return a
+
+
 # crt_hit as a numpy record (what Tracer.trace_rays returns, and the layout of a torch.uint8 [n, 48] output tensor)
 HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, 3), ("normal", np.float32, 3), ("u", np.float32), ("v", np.float32),
                       ("mesh", np.uint32), ("triangle", np.uint32), ("hit", np.uint32)])
@@ -182,6 +198,7 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_st
                   "crt_shoot_rays", "crt_shoot_rays_device", "crt_get_shoot_stats", "crt_shoot_rays_gi", "crt_shoot_rays_gi_device",
                   "crt_shoot_rays_enqueue", "crt_shoot_rays_gi_enqueue", "crt_get_shoot_report", "crt_query_scratch_generation",
                   "crt_camera_sample_rays_device", "crt_accumulate_samples_device", "crt_render_progressive", "crt_progressive_samples",
+                  "crt_adaptive_defaults", "crt_adaptive_work_bytes", "crt_adaptive_step_device", "crt_render_adaptive", "crt_progressive_active",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -252,6 +269,14 @@ def lib():
     L.crt_render_progressive.argtypes = [vp, C.POINTER(Options), u32, u32, vp]
     L.crt_progressive_samples.argtypes = [vp]
     L.crt_progressive_samples.restype = u32
+    L.crt_adaptive_defaults.argtypes = [C.POINTER(Adaptive)]
+    L.crt_adaptive_defaults.restype = None
+    L.crt_adaptive_work_bytes.argtypes = [C.c_uint64]
+    L.crt_adaptive_work_bytes.restype = C.c_size_t
+    L.crt_adaptive_step_device.argtypes = [vp, vp, vp, C.c_uint64, u32, C.POINTER(Adaptive), vp, vp, vp, vp, vp, vp, vp, vp]
+    L.crt_render_adaptive.argtypes = [vp, C.POINTER(Options), C.POINTER(Adaptive), u32, u32, vp, vp]
+    L.crt_progressive_active.argtypes = [vp]
+    L.crt_progressive_active.restype = C.c_uint64
     L.crt_host_shoot_stats_layout.argtypes = [C.POINTER(u32), u32]
     L.crt_host_shoot_stats_layout.restype = u32
     L.crt_get_kernel_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -805,6 +830,48 @@ class Tracer:
             if on_pass is not None and on_pass(done, rgb.copy()) is False:
                 break
         return rgb
+
+    # ---- adaptive sampling (include/crt_hip.h: crt_adaptive_step_device, crt_render_adaptive, crt_progressive_active)
+    @staticmethod
+    def adaptive_work_bytes(n) -> int:
+        """Bytes of the work area adaptive_step_device needs for a list of n entries."""
+        return int(lib().crt_adaptive_work_bytes(int(n)))
+
+    def adaptive_step_device(self, d_rgb_ptr, sample, adaptive, d_sum_ptr, d_sq_ptr, d_counts_ptr, d_next_pixels_ptr, d_next_n_ptr, d_work_ptr,
+                             d_mean_ptr=None, n=None, d_pixels_ptr=None, stream_ptr=None):
+        """One step of the fold and of the stopping rule for the listed pixels (distinct!) or all of them, and the next pass's list: sum
+        and mean float32 [H * W * 3], sq float32 [H * W], counts uint32 [H * W], next_pixels uint32 [>= n] (the kept pixels in the order
+        they had), next_n uint32 [1], work adaptive_work_bytes(n) bytes -- device arrays of the caller's.  Enqueues and returns."""
+        self._single("adaptive_step_device")
+        n = self.width * self.height if n is None else n
+        self._check(lib().crt_adaptive_step_device(self.ctx, C.c_void_p(d_rgb_ptr), C.c_void_p(d_pixels_ptr or 0), n, int(sample), C.byref(adaptive),
+                                                   C.c_void_p(d_sum_ptr), C.c_void_p(d_sq_ptr), C.c_void_p(d_mean_ptr or 0), C.c_void_p(d_counts_ptr),
+                                                   C.c_void_p(d_next_pixels_ptr), C.c_void_p(d_next_n_ptr), C.c_void_p(d_work_ptr),
+                                                   C.c_void_p(stream_ptr or 0)))
+
+    def progressive_active(self) -> int:
+        """Pixels the next pass of the context's progressive or adaptive frame would shoot (0: the frame is done, or none is under way)."""
+        self._single("progressive_active")
+        return int(lib().crt_progressive_active(self.ctx))
+
+    def render_adaptive(self, options, adaptive, per_call=1, on_pass=None):
+        """The GI frame of `options` (use_gi set; rays_per_pixel is not read) sampled adaptively: every pixel is shot until the rule of
+        `adaptive` (make_adaptive) stops it, at most adaptive.max_samples times, per_call passes a call.  on_pass(passes_done, mean, counts)
+        is called after every call and may return False to stop.  Returns (rgb float32 [H, W, 3], counts uint32 [H, W]): a pixel with
+        count k holds the one-shot frame of rays_per_pixel = k."""
+        self._single("render_adaptive")
+        if per_call < 1:
+            raise ValueError("per_call: at least one pass a call")
+        rgb = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        counts = np.zeros((self.height, self.width), dtype=np.uint32)
+        done = 0
+        while done == 0 or (done < adaptive.max_samples and self.progressive_active()):
+            k = min(int(per_call), adaptive.max_samples - done)
+            self._check(lib().crt_render_adaptive(self.ctx, C.byref(options), C.byref(adaptive), done, k, _p(rgb), _p(counts)))
+            done += k
+            if on_pass is not None and on_pass(done, rgb.copy(), counts.copy()) is False:
+                break
+        return rgb, counts
 
     def shoot_stats(self) -> ShootStats:
         """rays / levels / level_rays / shadow_records / rerouted / kernel_ms of the last radiance query (waits for it)."""

@@ -5,7 +5,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -18,6 +20,8 @@ int main(int argc, char **argv) {
                  "usage: %s scene.crtscene out.ppm [--folder DIR] [--depth N] [--mode 0..9] [--device D | --devices 0-7 | --devices 0,2,5] [--repeat K]\n"
                  "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL [--seed S] [--progressive K]]   (RenderOptions::USE_GI, RayTracer.h:27-30;\n"
                  "        --progressive: the same frame K samples a call, in memory that does not depend on RAYS_PER_PIXEL)\n"
+                 "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL --adaptive THRESHOLD MIN MAX [--counts FILE]]   (every pixel is shot until the rule of\n"
+                 "        crt_hip.h's crt_adaptive stops it, MIN .. MAX times; RAYS_PER_PIXEL is not read; --counts: the samples per pixel as a P2 PGM)\n"
                  "       [--probe ROW COL]   (no render: the closest hit of that pixel's camera ray; out.ppm is not written)\n",
                  argv[0]);
     return 2;
@@ -28,6 +32,10 @@ int main(int argc, char **argv) {
   std::vector<int> devices;  // --devices: the frame's tiles over several GPUs (first one gathers)
   bool useGI = false;
   unsigned giSamples = 2, raysPerPixel = 1, seed = 0, progressive = 0;
+  bool adaptive = false;
+  float adaptiveThreshold = 0.0f;
+  unsigned adaptiveMin = 0, adaptiveMax = 0;
+  std::string countsPath;
   bool probe = false;
   unsigned probeRow = 0, probeCol = 0;
   for (int i = 3; i < argc; i++) {
@@ -51,10 +59,22 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--gi") && i + 2 < argc) { useGI = true; giSamples = (unsigned)atoi(argv[++i]); raysPerPixel = (unsigned)atoi(argv[++i]); }
     else if (!strcmp(argv[i], "--seed") && i + 1 < argc) seed = (unsigned)strtoul(argv[++i], nullptr, 0);
     else if (!strcmp(argv[i], "--progressive") && i + 1 < argc) progressive = (unsigned)atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--adaptive") && i + 3 < argc) {
+      adaptive = true; adaptiveThreshold = (float)atof(argv[++i]); adaptiveMin = (unsigned)atoi(argv[++i]); adaptiveMax = (unsigned)atoi(argv[++i]);
+    }
+    else if (!strcmp(argv[i], "--counts") && i + 1 < argc) countsPath = argv[++i];
     else if (!strcmp(argv[i], "--probe") && i + 2 < argc) { probe = true; probeRow = (unsigned)atoi(argv[++i]); probeCol = (unsigned)atoi(argv[++i]); }
   }
   if (progressive && (!useGI || devices.size() > 0)) {
     std::fprintf(stderr, "error: --progressive needs --gi and one device\n");
+    return 2;
+  }
+  if (adaptive && (!useGI || devices.size() > 0 || progressive)) {
+    std::fprintf(stderr, "error: --adaptive needs --gi and one device, and excludes --progressive\n");
+    return 2;
+  }
+  if (!countsPath.empty() && !adaptive) {
+    std::fprintf(stderr, "error: --counts needs --adaptive\n");
     return 2;
   }
   try {
@@ -81,7 +101,23 @@ int main(int argc, char **argv) {
     double best = 1e30;
     for (int r = 0; r < repeat; r++) {
       auto a = std::chrono::high_resolution_clock::now();
-      if (progressive) tracer.renderProgressive(r + 1 == repeat ? outPath : std::string(), options, progressive);
+      if (adaptive) {
+        crt_adaptive a;
+        crt_adaptive_defaults(&a);
+        a.threshold = adaptiveThreshold; a.min_samples = adaptiveMin; a.max_samples = adaptiveMax;
+        std::vector<uint32_t> counts;
+        tracer.renderAdaptive(r + 1 == repeat ? outPath : std::string(), options, a, 1, &counts);
+        if (r + 1 == repeat && !countsPath.empty()) {
+          const unsigned W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
+          FILE *f = std::fopen(countsPath.c_str(), "w");
+          if (!f) throw std::runtime_error("cannot write " + countsPath);
+          std::fprintf(f, "P2\n%u %u\n%u\n", W, H, std::max(adaptiveMax, 1u));
+          for (unsigned y = 0; y < H; y++)
+            for (unsigned x = 0; x < W; x++) std::fprintf(f, "%u%c", counts[(size_t)y * W + x], x + 1 == W ? '\n' : ' ');
+          std::fclose(f);
+        }
+      }
+      else if (progressive) tracer.renderProgressive(r + 1 == repeat ? outPath : std::string(), options, progressive);
       else tracer.render(r + 1 == repeat ? outPath : std::string(), options);
       auto b = std::chrono::high_resolution_clock::now();
       best = std::min(best, std::chrono::duration<double>(b - a).count());

@@ -19,6 +19,8 @@
 //   a progressive frame  crt_render_progressive, at the end of this file: a GI frame sample pass by sample pass -- the rays and keys of one
 //                     sample (crt_camera_sample_rays_device), shoot_run, one step of the pixel's fold (crt_accumulate_samples_device);
 //                     kernels: csrc/kernel_progressive.h
+//   an adaptive frame  crt_render_adaptive, behind it: the same loop over a pixel list that shrinks -- the step, the rule and the
+//                     compaction of crt_adaptive_step_device; kernels: csrc/kernel_adaptive.h, the rule: csrc/adaptive_rule.h
 #include "crt_internal.h"
 #include "glibc_powf.h"
 #include "gi_random.h"
@@ -39,6 +41,7 @@ namespace {
 #include "kernel_shade.h"
 #include "kernel_radiance.h"
 #include "kernel_progressive.h"
+#include "kernel_adaptive.h"
 #pragma clang diagnostic pop
 
 // radiance queries: what a level may hold at most is SHOOT_LEVEL_RAYS (shoot_caps.h: a level is at most twice as wide as the one above
@@ -174,6 +177,7 @@ struct QueryPinned {
     uint32_t words[QW_WORDS];   // the words of the last call, copied behind its last launch
     uint64_t shoot[SH_SLOTS];   // SH_*
     crt_shoot_report report;    // crt_query_state::d_report, copied behind the last launch of an enqueue call
+    uint32_t adaptive_n;        // crt_render_adaptive: the next pass's list length, copied behind a pass's scatter
 };
 
 }  // namespace
@@ -212,6 +216,15 @@ struct crt_query_state {
     DeviceArray<crt_ray> prog_rays;
     DeviceArray<uint32_t> prog_keys;
     uint32_t prog_samples = 0;
+    // crt_render_adaptive: the frame above with one float and one count more per pixel, two pixel lists (this pass's and the next one's),
+    // the next list's length, the compaction's work area; which kind of frame is under way, its latched settings and its list
+    DeviceArray<float> prog_sq;
+    DeviceArray<uint32_t> prog_counts, prog_list[2], prog_next_n;
+    DeviceArray<unsigned long long> prog_work;
+    bool prog_is_adaptive = false;
+    crt_adaptive prog_adaptive{};
+    uint64_t prog_active = 0;   // entries of prog_list[prog_cur]; pass 0 has no list (every pixel)
+    int prog_cur = 0;
     uint64_t level_peak[MAX_GENERATIONS] = {};   // the widest level g of a pass since a progressive frame's sample 0 began (shoot_numbers)
     // the radiance queries' own device words: made by the first radiance call of a context (shoot_words_reserve)
     bool shoot_words_made() const { return swords.p && d_report.p && d_hits0.p; }
@@ -233,7 +246,9 @@ void query_destroy(crt_ctx *ctx) {
 
 // crt_set_camera and crt_render*: the progressive frame under way, if any, is no longer the context's frame
 void query_progressive_reset(crt_ctx *ctx) {
-    if (ctx->query) ctx->query->prog_samples = 0;
+    if (!ctx->query) return;
+    ctx->query->prog_samples = 0;
+    ctx->query->prog_active = 0;
 }
 
 // a radiance pass's numbers, once its last copy has arrived
@@ -1059,6 +1074,10 @@ extern "C" int crt_render_progressive(crt_ctx *ctx, const crt_options *options, 
                      std::to_string(crt_progressive_samples(ctx)) + " samples (crt_progressive_samples; 0 starts a new frame)";
         return CRT_ERR_INVALID;
     }
+    if (first_sample != 0 && ctx->query->prog_is_adaptive) {   // (first_sample == the count > 0: the context has a query state)
+        ctx->error = std::string(what) + ": the frame under way is an ADAPTIVE frame (crt_render_adaptive continues it; first_sample 0 starts a new frame)";
+        return CRT_ERR_INVALID;
+    }
     if ((uint64_t)first_sample + n_samples > 0xFFFFFFFFull) { ctx->error = std::string(what) + ": more than 2^32 - 1 samples"; return CRT_ERR_INVALID; }
     const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
     if (pixels == 0) return CRT_OK;
@@ -1068,7 +1087,11 @@ extern "C" int crt_render_progressive(crt_ctx *ctx, const crt_options *options, 
     if ((rc = reserve_all(ctx, q->prog_sum, 3 * pixels, q->prog_rgb, 3 * pixels, q->prog_rays, pixels, q->prog_keys, pixels))) return rc;
     const ShootGi gi{q->prog_keys.p, 0u};
     for (uint32_t s = first_sample; s - first_sample < n_samples; s++) {   // one at a time and in order: the fold's order is the frame's
-        if (s == 0) std::fill(q->level_peak, q->level_peak + MAX_GENERATIONS, 0ull);
+        if (s == 0) {
+            std::fill(q->level_peak, q->level_peak + MAX_GENERATIONS, 0ull);
+            q->prog_is_adaptive = false;
+            q->prog_active = pixels;   // (a uniform frame shoots every pixel in every pass)
+        }
         if ((rc = launch_sample_rays(ctx, options->gi_seed, s, nullptr, pixels, q->prog_rays.p, q->prog_keys.p, ctx->stream)) ||
             (rc = shoot_run(ctx, q->prog_rays.p, pixels, CRT_RAY_PRIMARY, options, q->prog_rgb.p, ctx->stream, pass, &gi)) ||
             (rc = launch_accumulate(ctx, q->prog_rgb.p, nullptr, pixels, s, q->prog_sum.p, ctx->d_frame, ctx->stream)))
@@ -1077,6 +1100,158 @@ extern "C" int crt_render_progressive(crt_ctx *ctx, const crt_options *options, 
         if (s == 0 && (rc = progressive_headroom(ctx, options, std::min(pixels, pass)))) return rc;
     }
     if (out_rgb) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, ctx->d_frame, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return CRT_OK;
+}
+
+// ---- adaptive sampling (csrc/kernel_adaptive.h, csrc/adaptive_rule.h): the progressive frame's loop over a pixel list that shrinks.
+
+extern "C" void crt_adaptive_defaults(crt_adaptive *a) {
+    if (!a) return;
+    a->size = (uint32_t)sizeof(crt_adaptive);
+    a->min_samples = 4;
+    a->max_samples = 64;
+    a->threshold = 0.05f;
+    a->floor = 1e-4f;
+}
+
+static uint64_t adaptive_blocks(const uint64_t n) { return (n + BLOCK - 1) / BLOCK; }
+
+extern "C" size_t crt_adaptive_work_bytes(uint64_t n) {
+    const uint64_t blocks = adaptive_blocks(n);
+    return (size_t)(blocks * ADAPTIVE_WAVES * sizeof(unsigned long long) + 2 * blocks * sizeof(uint32_t));
+}
+
+static int adaptive_check(crt_ctx *ctx, const char *what, const crt_adaptive *a) {
+    const char *why = nullptr;
+    if (!a) why = "adaptive is NULL";
+    else if (a->size != sizeof(crt_adaptive)) why = "adaptive->size is not sizeof(crt_adaptive)";
+    else if (a->min_samples == 0) why = "min_samples is 0";
+    else if (a->max_samples < a->min_samples) why = "max_samples < min_samples";
+    else if (!(a->threshold >= 0.0f) || !std::isfinite(a->threshold)) why = "threshold is negative or not finite";
+    else if (!(a->floor >= 0.0f) || !std::isfinite(a->floor)) why = "floor is negative or not finite";
+    if (!why) return CRT_OK;
+    ctx->error = std::string(what) + ": " + why;
+    return CRT_ERR_INVALID;
+}
+
+// the step, the scan and the scatter of n > 0 entries, one behind the other on `stream`
+static int launch_adaptive(crt_ctx *ctx, const float *d_rgb, const uint32_t *d_pixels, uint64_t n, uint32_t sample, const crt_adaptive *a, float *d_sum,
+                           float *d_sq, float *d_mean, uint32_t *d_counts, uint32_t *d_next, uint32_t *d_next_n, void *d_work, hipStream_t stream) {
+    const uint32_t blocks = (uint32_t)adaptive_blocks(n);
+    AdaptiveWork work{};
+    work.masks = (unsigned long long *)d_work;
+    work.counts = (uint32_t *)(work.masks + (uint64_t)blocks * ADAPTIVE_WAVES);
+    work.offsets = work.counts + blocks;
+    AdaptiveStepArgs S{};
+    S.rgb = d_rgb; S.pixels = d_pixels; S.n = n; S.frame_pixels = (uint64_t)ctx->width * ctx->height; S.sample = sample;
+    S.rule = crt_adaptive_rule{a->min_samples, a->max_samples, a->threshold, a->floor};
+    S.sum = d_sum; S.sq = d_sq; S.mean = d_mean; S.count = d_counts; S.work = work;
+    hipLaunchKernelGGL(adaptive_step, dim3(blocks), dim3(BLOCK), 0, stream, S);
+    CRT_HIP_CHECK(ctx, hipGetLastError());
+    const AdaptiveScanArgs C{work.counts, work.offsets, d_next_n, blocks};
+    hipLaunchKernelGGL(adaptive_scan, dim3(1), dim3(BLOCK), 0, stream, C);
+    CRT_HIP_CHECK(ctx, hipGetLastError());
+    const AdaptiveScatterArgs T{d_pixels, n, work, d_next};
+    hipLaunchKernelGGL(adaptive_scatter, dim3(blocks), dim3(BLOCK), 0, stream, T);
+    CRT_HIP_CHECK(ctx, hipGetLastError());
+    return CRT_OK;
+}
+
+extern "C" int crt_adaptive_step_device(crt_ctx *ctx, const float *d_rgb, const uint32_t *d_pixels, uint64_t n, uint32_t sample, const crt_adaptive *adaptive,
+                                        float *d_sum, float *d_sq, float *d_mean, uint32_t *d_counts, uint32_t *d_next_pixels, uint32_t *d_next_n,
+                                        void *d_work, void *stream) {
+    const char *what = "crt_adaptive_step_device";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = adaptive_check(ctx, what, adaptive)) return rc;
+    if (int rc = progressive_check(ctx, what, d_pixels, n)) return rc;
+    if (n > 0xFFFFFFFFull) { ctx->error = std::string(what) + ": the next list's length is one 32-bit word: n = " + std::to_string(n) + " > 2^32 - 1"; return CRT_ERR_INVALID; }
+    if (!d_next_n) { ctx->error = std::string(what) + ": d_next_n is NULL"; return CRT_ERR_INVALID; }
+    if (n != 0) {
+        if (!d_rgb || !d_sum || !d_sq || !d_counts || !d_next_pixels || !d_work) {
+            ctx->error = std::string(what) + ": d_rgb, d_sum, d_sq, d_counts, d_next_pixels or d_work is NULL";
+            return CRT_ERR_INVALID;
+        }
+        if (d_next_pixels == d_pixels) { ctx->error = std::string(what) + ": d_next_pixels must not alias d_pixels"; return CRT_ERR_INVALID; }
+        if ((uintptr_t)d_work % alignof(unsigned long long)) { ctx->error = std::string(what) + ": d_work must be aligned to 8 bytes"; return CRT_ERR_INVALID; }
+        if (sample == 0xFFFFFFFFu) { ctx->error = std::string(what) + ": sample + 1 does not fit 32 bits"; return CRT_ERR_INVALID; }
+    }
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (n == 0) {   // no entry: the next list is empty, and nothing else is written
+        CRT_HIP_CHECK(ctx, hipMemsetAsync(d_next_n, 0, sizeof(uint32_t), (hipStream_t)stream));
+        return CRT_OK;
+    }
+    return launch_adaptive(ctx, d_rgb, d_pixels, n, sample, adaptive, d_sum, d_sq, d_mean, d_counts, d_next_pixels, d_next_n, d_work, (hipStream_t)stream);
+}
+
+extern "C" uint64_t crt_progressive_active(const crt_ctx *ctx) {
+    return ctx && ctx->query && ctx->query->prog_samples ? ctx->query->prog_active : 0ull;
+}
+
+static bool same_adaptive(const crt_adaptive &a, const crt_adaptive &b) {
+    return a.min_samples == b.min_samples && a.max_samples == b.max_samples && a.threshold == b.threshold && a.floor == b.floor;
+}
+
+extern "C" int crt_render_adaptive(crt_ctx *ctx, const crt_options *options, const crt_adaptive *adaptive, uint32_t first_pass, uint32_t n_passes,
+                                   float *out_rgb, uint32_t *out_counts) {
+    const char *what = "crt_render_adaptive";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n_passes == 0) return CRT_OK;
+    uint64_t pass = 0;
+    if (int rc = query_check(ctx, shoot_needs(what, ctx, options, ctx, CRT_RAY_PRIMARY, true, &pass))) return rc;
+    if (int rc = adaptive_check(ctx, what, adaptive)) return rc;
+    if (first_pass != 0 && first_pass != crt_progressive_samples(ctx)) {   // (0 starts a new frame, whatever the context holds)
+        ctx->error = std::string(what) + ": first_pass is " + std::to_string(first_pass) + ", but the context's frame holds " +
+                     std::to_string(crt_progressive_samples(ctx)) + " passes (crt_progressive_samples; 0 starts a new frame)";
+        return CRT_ERR_INVALID;
+    }
+    if (first_pass != 0 && !ctx->query->prog_is_adaptive) {
+        ctx->error = std::string(what) + ": the frame under way is a UNIFORM progressive frame (crt_render_progressive continues it; first_pass 0 starts a new frame)";
+        return CRT_ERR_INVALID;
+    }
+    if (first_pass != 0 && !same_adaptive(*adaptive, ctx->query->prog_adaptive)) {
+        ctx->error = std::string(what) + ": adaptive differs from the settings latched by the frame's pass 0";
+        return CRT_ERR_INVALID;
+    }
+    if ((uint64_t)first_pass + n_passes > 0xFFFFFFFFull) { ctx->error = std::string(what) + ": more than 2^32 - 1 passes"; return CRT_ERR_INVALID; }
+    const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
+    if (pixels == 0) return CRT_OK;
+    int rc;
+    if ((rc = progressive_check(ctx, what, nullptr, pixels)) || (rc = query_begin(ctx, ctx->stream, CALL_RADIANCE))) return rc;
+    crt_query_state *q = ctx->query;
+    if ((rc = reserve_all(ctx, q->prog_sum, 3 * pixels, q->prog_rgb, 3 * pixels, q->prog_rays, pixels, q->prog_keys, pixels, q->prog_sq, pixels,
+                          q->prog_counts, pixels, q->prog_list[0], pixels, q->prog_list[1], pixels, q->prog_next_n, 1, q->prog_work,
+                          (crt_adaptive_work_bytes(pixels) + 7) / 8)))
+        return rc;
+    const ShootGi gi{q->prog_keys.p, 0u};
+    for (uint32_t s = first_pass; s - first_pass < n_passes; s++) {   // one at a time and in order: the fold's order is the frame's
+        if (s == 0) {
+            std::fill(q->level_peak, q->level_peak + MAX_GENERATIONS, 0ull);
+            q->prog_is_adaptive = true;
+            q->prog_adaptive = *adaptive;
+            q->prog_active = pixels;
+        }
+        const uint64_t n = q->prog_active;
+        if (n != 0) {   // (an empty list launches nothing: every pixel has stopped, or reached max_samples)
+            const uint32_t *list = s == 0 ? nullptr : q->prog_list[q->prog_cur].p;   // pass 0: every pixel
+            uint32_t *next = q->prog_list[s == 0 ? 0 : q->prog_cur ^ 1].p;
+            if ((rc = launch_sample_rays(ctx, options->gi_seed, s, list, n, q->prog_rays.p, q->prog_keys.p, ctx->stream)) ||
+                (rc = shoot_run(ctx, q->prog_rays.p, n, CRT_RAY_PRIMARY, options, q->prog_rgb.p, ctx->stream, pass, &gi)) ||
+                (rc = launch_adaptive(ctx, q->prog_rgb.p, list, n, s, adaptive, q->prog_sum.p, q->prog_sq.p, ctx->d_frame, q->prog_counts.p, next,
+                                      q->prog_next_n.p, q->prog_work.p, ctx->stream)))
+                return rc;
+            // the next list's length: 4 bytes through pinned memory, once a pass
+            CRT_HIP_CHECK(ctx, hipMemcpyAsync(&q->pin->adaptive_n, q->prog_next_n.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+            q->prog_active = q->pin->adaptive_n;
+            if (s != 0) q->prog_cur ^= 1;
+            else q->prog_cur = 0;
+        }
+        q->prog_samples = s + 1;
+        if (s == 0 && (rc = progressive_headroom(ctx, options, std::min(pixels, pass)))) return rc;
+    }
+    if (out_rgb) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, ctx->d_frame, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (out_counts) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_counts, q->prog_counts.p, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return CRT_OK;
 }

@@ -376,6 +376,45 @@ std::vector<std::vector<Color>> RayTracer::renderProgressive(const std::string &
   return colorBuffer;
 }
 
+std::vector<std::vector<Color>> RayTracer::renderAdaptive(const std::string &pathToImage, RenderOptions ro, const crt_adaptive &adaptive,
+                                                          unsigned int passesPerCall, std::vector<uint32_t> *counts) {
+  if (multi) throw std::runtime_error("renderAdaptive: not available on a multi-device tracer");
+  const unsigned int W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
+  crt_options o{};
+  o.max_depth = ro.MAX_DEPTH;
+  o.shadow_bias = ro.SHADOW_BIAS;
+  o.reflection_bias = ro.REFLECTION_BIAS;
+  o.refraction_bias = ro.REFRACTION_BIAS;
+  o.use_gi = ro.USE_GI ? 1u : 0u;
+  o.gi_sample_size = ro.GI_SAMPLE_SIZE;
+  o.monte_carlo_bias = ro.MONTE_CARLO_BIAS;
+  o.gi_seed = ro.USE_GI ? giSeed++ : 0u;  // as renderFlat takes it
+  passesPerCall = std::max(passesPerCall, 1u);
+  std::vector<uint32_t> held((size_t)W * H, 0u);
+  const Matrix3 &m = camera.getRotationMatrix();
+  const float pos[3] = {camera.getPosition().x, camera.getPosition().y, camera.getPosition().z};
+  int rc = crt_set_camera(ctx, pos, &m.m[0][0]);  // (starts a new frame)
+  for (unsigned int done = 0; rc == CRT_OK && (done == 0 || (done < adaptive.max_samples && crt_progressive_active(ctx)));) {
+    const unsigned int k = std::min(passesPerCall, std::max(adaptive.max_samples, 1u) - done);
+    rc = crt_render_adaptive(ctx, &o, &adaptive, done, k, frame.data(), held.data());
+    done += k;
+  }
+  if (rc == CRT_OK && !pathToImage.empty()) {
+    std::vector<uint8_t> q((size_t)W * H * 3);
+    rc = crt_read_quantized(ctx, q.data());
+    if (rc == CRT_OK) writePPMQuantized(pathToImage, q.data(), W, H);
+  }
+  if (rc != CRT_OK) throw std::runtime_error(std::string("renderAdaptive failed: ") + crt_last_error(ctx));
+  if (counts) counts->swap(held);
+  std::vector<std::vector<Color>> colorBuffer(H, std::vector<Color>(W));
+  for (unsigned int y = 0; y < H; y++)
+    for (unsigned int x = 0; x < W; x++) {
+      const float *p = &frame[((size_t)y * W + x) * 3];
+      colorBuffer[y][x] = Color(p[0], p[1], p[2]);
+    }
+  return colorBuffer;
+}
+
 void RayTracer::exportPPM(const std::string &pathToImage, const std::vector<std::vector<Color>> &colorBuffer) {
   const unsigned int W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
   std::vector<float> flatRGB((size_t)W * H * 3, 0.0f);

@@ -123,6 +123,13 @@ class RayTracer {
   // out) the PPM is render()'s byte for byte.  Single-device tracers only; USE_GI must be set.
   std::vector<std::vector<Color>> renderProgressive(const std::string &pathToImage, RenderOptions renderOptions, unsigned int samplesPerCall = 1);
 
+  // ---- adaptive sampling (crt_hip.h: crt_render_adaptive): that frame with every pixel shot until the rule of `adaptive` stops it, at most
+  // adaptive.max_samples times (RAYS_PER_PIXEL is not read), passesPerCall passes a call; the calls end when no pixel is left.  counts, if
+  // given, receives the samples each pixel holds (row-major): a pixel with k samples is render()'s pixel with RAYS_PER_PIXEL = k.
+  // Single-device tracers only; USE_GI must be set.
+  std::vector<std::vector<Color>> renderAdaptive(const std::string &pathToImage, RenderOptions renderOptions, const crt_adaptive &adaptive,
+                                                 unsigned int passesPerCall = 1, std::vector<uint32_t> *counts = nullptr);
+
   // flat access for callers that do not want the vector-of-vectors copy
   int renderFlat(const std::string &pathToImage, const RenderOptions &renderOptions, float *outRGB, unsigned int counters = 0);
   crt_ctx *context() const { return multi ? crt_multi_context(multi, 0) : ctx; }

@@ -548,6 +548,70 @@ int crt_render_progressive(crt_ctx *ctx, const crt_options *options, uint32_t fi
 /* samples folded into the context's sum so far */
 uint32_t crt_progressive_samples(const crt_ctx *ctx);
 
+/* ---- Adaptive sampling for progressive GI frames: a pixel whose samples agree stops being shot.  A per-pixel noise estimate, a stopping
+ * rule and a device-side compaction of "which pixels go on" into the next pass's pixel list, beside the two primitives above.  Kernels:
+ * csrc/kernel_adaptive.h; the rule, one header for host and device: csrc/adaptive_rule.h.  A pixel that stopped after k samples is the
+ * one-shot GI frame with rays_per_pixel = k AT THAT PIXEL, bit for bit.  Single-device contexts only.  No frame kernel is involved.
+ *
+ * The rule.  State per pixel: the fold's sum[3], one float sq, one uint32 count.  Step for sample s with colour (r, g, b) and n = s + 1,
+ * every operation in float32 with one rounding:
+ *   sum_c   = (s == 0 ? 0.0f : sum_c) + c
+ *   sq      = (s == 0 ? 0.0f : sq) + ((r*r + g*g) + b*b)
+ *   inv     = 1.0f / (float)n
+ *   mean_c  = sum_c * inv
+ *   q       = sq * inv
+ *   mm      = (mean_r*mean_r + mean_g*mean_g) + mean_b*mean_b
+ *   var     = q - mm
+ *   bound   = ((threshold*threshold) * (float)n) * (mm > floor ? mm : floor)
+ *   converged = (var <= bound)
+ *   count   = n
+ *   keep    = (n < max_samples) && !(n >= min_samples && converged)
+ * converged is false when either side is NaN, and a negative var converges.  In words: the squared standard error of the mean is at most
+ * threshold^2 times max(|mean|^2, floor); no division, no square root.  A pixel with a NaN or infinite sample never converges and runs to
+ * max_samples; a pixel of identical samples has var <= 0 and stops at min_samples.
+ * crt_adaptive: size must be sizeof(crt_adaptive), min_samples >= 1, max_samples >= min_samples, threshold and floor >= 0 and finite:
+ *   anything else is CRT_ERR_INVALID.  crt_adaptive_defaults: 4, 64, 0.05f, 1e-4f.
+ * crt_adaptive_step_device: for i < n and pixel p = d_pixels ? d_pixels[i] : i, the step above on d_sum[3p ..], d_sq[p], d_counts[p] with the
+ *   colour d_rgb[3i ..] (d_mean[3p ..], where d_mean != NULL, receives the means), and d_next_pixels[0 .. *d_next_n) = the pixels whose keep
+ *   is true IN THE ORDER THEY HAD (stable: a list that started as "all pixels" stays ascending; no atomic decides a position, so the list is
+ *   the same on every run).  d_sum and d_mean are width * height * 3 floats, d_sq width * height floats, d_counts width * height uint32;
+ *   d_next_pixels holds at least n entries and must not alias d_pixels; d_next_n is one uint32 word; d_work is the caller's, at least
+ *   crt_adaptive_work_bytes(n) bytes (wave masks, workgroup counts and offsets), aligned to 8 bytes.  The NULL and n rules are
+ *   crt_accumulate_samples_device's: with d_pixels == NULL, n must be width * height.  n > 2^32 - 1, a NULL array other than d_pixels and
+ *   d_mean, and sample == 2^32 - 1 are CRT_ERR_INVALID.  n == 0 is CRT_OK: it writes *d_next_n = 0 and nothing else.  An index outside the
+ *   frame is skipped and not kept; a pixel that is not listed is not touched in any array; THE PIXELS OF ONE CALL MUST BE DISTINCT.  Three
+ *   launches on `stream` -- step, a prefix sum over the workgroups' counts by one workgroup, scatter -- and nothing else: no wait, no
+ *   allocation, no readback, so the call can be captured into a hipGraph and composes with its two siblings and crt_shoot_rays_gi_enqueue.
+ * crt_render_adaptive: crt_render_progressive's loop with a list.  Pass s shoots the active list A_s, A_0 being every pixel: the rays and
+ *   keys of sample s of the listed pixels, crt_shoot_rays_gi_device's path in its usual passes, the step into context-owned sum, sq and
+ *   counts with the mean into the persistent colour buffer (crt_read_quantized works unchanged); A_(s+1) is the kept pixels.  Its length
+ *   is read back through pinned memory, 4 bytes, once per pass.  A pass with an empty list launches nothing; passes at s >= max_samples
+ *   are empty by construction.  crt_progressive_samples counts PASSES here and advances by n_passes regardless, so the first_pass rule is
+ *   crt_render_progressive's: 0 starts a new frame, otherwise it must equal the count.  `adaptive` is latched at first_pass == 0: a
+ *   continuing call whose adaptive differs is CRT_ERR_INVALID.  Continuing an adaptive frame with crt_render_progressive, or a uniform
+ *   one with crt_render_adaptive, is CRT_ERR_INVALID, and the message says which kind of frame is under way.  Everything
+ *   crt_render_progressive refuses is refused here, with nothing changed; n_passes == 0 is CRT_OK and touches nothing; crt_set_camera and
+ *   crt_render* reset it.  out_rgb (height * width * 3 floats) and out_counts (height * width uint32, the samples each pixel holds) are
+ *   host memory and may be NULL; the call returns when both are there.  It leaves crt_stats, the ray queues' sizing and fallback_frames
+ *   alone; crt_get_shoot_stats describes the last non-empty pass.
+ * crt_progressive_active: the pixels the next pass would shoot (every pixel while a uniform frame is under way); 0 when the frame is done
+ *   or none is under way. */
+typedef struct crt_adaptive {
+    uint32_t size;          /* sizeof(crt_adaptive) */
+    uint32_t min_samples;   /* >= 1 */
+    uint32_t max_samples;   /* >= min_samples */
+    float threshold;        /* >= 0, finite */
+    float floor;            /* >= 0, finite: |mean|^2 below which the error is absolute */
+} crt_adaptive;
+void crt_adaptive_defaults(crt_adaptive *a);   /* 4, 64, 0.05f, 1e-4f */
+size_t crt_adaptive_work_bytes(uint64_t n);    /* wave masks + workgroup counts + offsets for a list of n entries */
+int crt_adaptive_step_device(crt_ctx *ctx, const float *d_rgb, const uint32_t *d_pixels, uint64_t n, uint32_t sample, const crt_adaptive *adaptive,
+                             float *d_sum, float *d_sq, float *d_mean, uint32_t *d_counts, uint32_t *d_next_pixels, uint32_t *d_next_n, void *d_work,
+                             void *stream);
+int crt_render_adaptive(crt_ctx *ctx, const crt_options *options, const crt_adaptive *adaptive, uint32_t first_pass, uint32_t n_passes,
+                        float *out_rgb, uint32_t *out_counts);
+uint64_t crt_progressive_active(const crt_ctx *ctx);
+
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
  * stream per listed device (a device may be listed more than once); the covered 8x8 tiles are dealt round-robin, every
