@@ -63,6 +63,7 @@ def lib():
         L.oracle_box_hit.argtypes = [C.c_void_p] * 4
         L.oracle_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.oracle_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]
+        L.oracle_occluded_gi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int]
         L.oracle_shoot.argtypes = [C.c_void_p, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_int, C.c_uint,
                                    C.c_void_p]
         L.oracle_camera_ray.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p]
@@ -140,9 +141,12 @@ class OracleScene:
         hit = self._L.oracle_trace(self._h, _p(o), _p(d), ray_type, _p(out))
         return bool(hit), out[:11].copy()
 
-    def occluded(self, origin, direction, distance):
+    def occluded(self, origin, direction, distance, gi=False):
+        """checkForIntersection for a shadow ray; gi=True: the GI build's rule, under which no mesh is skipped"""
         o = np.ascontiguousarray(origin, dtype=np.float32)
         d = np.ascontiguousarray(direction, dtype=np.float32)
+        if gi:
+            return bool(self._L.oracle_occluded_gi(self._h, _p(o), _p(d), float(distance), 1))
         return bool(self._L.oracle_occluded(self._h, _p(o), _p(d), float(distance)))
 
     def shoot(self, origin, direction, ray_type=0, depth=0, max_depth=5):
@@ -287,3 +291,66 @@ def reference_render(blob: bytes, max_depth=5, mode="bvhpool", textured=None, pp
         rgb = np.fromfile(op, dtype=np.float32)
         rgb = rgb.reshape(-1, info["height"], info["width"], 3) if all_frames else rgb.reshape(info["height"], info["width"], 3)
     return rgb, info
+
+
+# ---- single rays through the real reference (oracle/ref_driver.cpp --rays): its own intersect, checkForIntersection and shootRay
+REF_HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, 3), ("normal", np.float32, 3), ("u", np.float32), ("v", np.float32),
+                          ("mesh", np.uint32), ("triangle", np.uint32), ("hit", np.uint32)])   # triangle: index within its mesh
+
+
+def _reference_rays(blob, payload, what, ray_types, textured, extra, dtype):
+    """one run of the driver's ray mode; ray_types: a list (its trees take longer to build than a few thousand rays to answer)"""
+    if textured is None:
+        textured = blob[80:84] != b"\x00\x00\x00\x00"
+    exe = REF_TEX if textured else REF_PLAIN
+    if not os.path.exists(exe):
+        raise FileNotFoundError(exe)
+    with tempfile.TemporaryDirectory() as td:
+        sp, rp, op = (os.path.join(td, n) for n in ("scene.crts", "rays.bin", "out.bin"))
+        with open(sp, "wb") as f:
+            f.write(blob)
+        with open(rp, "wb") as f:
+            for a in payload:
+                f.write(np.ascontiguousarray(a, dtype="<f4").tobytes())
+        subprocess.run([exe, "--rays", sp, rp, op, "--what", what, "--type", ",".join(str(int(t)) for t in ray_types)] + extra,
+                       capture_output=True, text=True, check=True, timeout=900)
+        return np.fromfile(op, dtype=dtype)
+
+
+def _rays6(rays):
+    rays = np.ascontiguousarray(rays, dtype=np.float32)
+    if rays.ndim != 2 or rays.shape[1] != 6:
+        raise ValueError("rays: expected shape [n, 6], got %r" % (rays.shape,))
+    return rays
+
+
+def reference_trace(blob: bytes, rays, ray_type, textured=None):
+    """AccelerationStructure(scene).intersect(Ray(origin, direction, ray_type)) of the real reference for every ray (float32 [n, 6],
+    directions as given) -> REF_HIT_DTYPE [n]; no hit: every field 0.  u, v come from the USE_TEXTURES build only (textured=True runs
+    that build on a scene without textures too: its materials become constant-albedo textures, Texture.cpp:14-16).  ray_type may be
+    a list: -> [len(ray_type), n] from one run."""
+    rays = _rays6(rays)
+    types = list(ray_type) if np.ndim(ray_type) else [ray_type]
+    out = _reference_rays(blob, [rays], "trace", types, textured, [], REF_HIT_DTYPE).reshape(len(types), len(rays))
+    return out if np.ndim(ray_type) else out[0]
+
+
+def reference_occluded(blob: bytes, rays, distances, gi=False):
+    """checkForIntersection(ray, distances[i], useGI=gi) of the real reference for every ray as a ShadowRay -> bool [n]."""
+    rays = _rays6(rays)
+    dist = np.ascontiguousarray(np.broadcast_to(np.asarray(distances, dtype=np.float32), (len(rays),)))
+    out = _reference_rays(blob, [rays, dist], "occluded", [1], None, ["--gi-occlusion"] if gi else [], np.uint8)
+    assert out.shape == (len(rays),)
+    return out.astype(bool)
+
+
+def reference_shoot(blob: bytes, rays, ray_type, max_depth):
+    """RayTracer::shootRay(Ray(origin, direction, ray_type), 0) of the real reference with MAX_DEPTH = max_depth and the tracer's state
+    as render() leaves it for the default tree mode -> float32 [n, 3].  ray_type and max_depth may both be lists:
+    -> [len(ray_type), len(max_depth), n, 3] from one run."""
+    rays = _rays6(rays)
+    lists = bool(np.ndim(ray_type))
+    types, depths = (list(ray_type), list(max_depth)) if lists else ([ray_type], [max_depth])
+    out = _reference_rays(blob, [rays], "shoot", types, None, ["--depth", ",".join(str(int(d)) for d in depths)], np.float32)
+    out = out.reshape(len(types), len(depths), len(rays), 3)
+    return out if lists else out[0, 0]

@@ -16,16 +16,50 @@
 //   drives the reference's own Camera (Camera.cpp:33-70).  ops.txt: first line = position (3) and row-major matrix (9)
 //   as hexadecimal float bit patterns; every further line = "<truck|pan|tilt|roll> <3 bit patterns>", applied one after the
 //   other to the same camera.  out.txt: the 12 bit patterns of the camera after every operation, one line each.
+// usage: ref_render --rays <scene.crts> <rays.bin> <out.bin> --what trace|occluded|shoot --type T [--depth N] [--gi-occlusion]
+//   answers single rays with the reference's own functions on the scene of the blob; T = 0..4, the value of enum RayType (Ray.h:14).
+//   T and N may be comma-separated lists: the trees are built once and out.bin holds one block of records per type (and, for shoot,
+//   per type and depth, the depth running fastest), each block in ray order.
+//   rays.bin: little-endian float32, 6 per ray (origin xyz, direction xyz; the direction is handed over as given), followed, for
+//   `occluded`, by one float32 distance per ray (all rays first, then all distances).  out.bin, one fixed-size record per ray:
+//     trace     48 bytes: float32 t, point[3], normal[3], u, v; uint32 mesh, triangle, hit -- what
+//               AccelerationStructure(scene).intersect(Ray(o, d, T)) returns (KDTree.cpp:127-192).  mesh = index into scene.objects and
+//               triangle = index into that mesh's `triangles`, both from the returned pointers; u, v only in the USE_TEXTURES build
+//               (the other build's IntersectionInformation has no such members, Scene.h:44-47: 0 there); no hit: 48 zero bytes.
+//     occluded  1 byte: checkForIntersection(Ray(o, d, T), distance, useGI) (AccelerationStructure.cpp:56-94), useGI = --gi-occlusion.
+//     shoot     12 bytes: float32 r, g, b of RayTracer::shootRay(ray, 0) (RayTracer.cpp:419-451) on a RayTracer whose renderOptions,
+//               useBounding and boundingType are what render() leaves behind for the default tree mode with MAX_DEPTH = N
+//               (RayTracer.cpp:205, 270-273).  shootRay and those members are private (RayTracer.h:60-94): this translation unit
+//               alone includes that header with `private` spelt `public`, after every standard header; access is no part of a
+//               mangled name, so it links against the reference's unmodified objects.
+#include <algorithm>
+#include <array>
+#include <atomic>
 #include <chrono>
+#include <cmath>
+#include <condition_variable>
+#include <cstddef>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <functional>
+#include <iostream>
+#include <limits>
+#include <mutex>
+#include <optional>
+#include <ostream>
+#include <queue>
+#include <random>
+#include <stack>
 #include <string>
 #include <thread>
 #include <vector>
 
+#define private public   // for RayTracer::shootRay (see --rays above); every standard header is already in
 #include "tracer/RayTracer.h"
+#undef private
 #include "tracer/Scene.h"
 
 #include "scene_blob.h"
@@ -90,27 +124,10 @@ static int cameraOps(const char *opsPath, const char *outPath) {
   return 0;
 }
 
-int main(int argc, char **argv) {
-  if (argc == 4 && std::string(argv[1]) == "--camera-ops") return cameraOps(argv[2], argv[3]);
-  if (argc < 3) {
-    std::fprintf(stderr, "usage: %s scene.crts out.f32 [--depth N] [--mode NAME] [--ppm P] [--repeat K] [--gi SAMPLES RAYS_PER_PIXEL] [--all-frames]\n", argv[0]);
-    return 2;
-  }
-  std::string blobPath = argv[1], outPath = argv[2], ppmPath, mode = "bvhpool";
-  unsigned depth = 5;
-  int repeat = 1;
-  bool useGI = false, allFrames = false;
-  unsigned giSamples = 2, raysPerPixel = 1;
-  for (int i = 3; i < argc; i++) {
-    std::string a = argv[i];
-    if (a == "--depth" && i + 1 < argc) depth = std::atoi(argv[++i]);
-    else if (a == "--mode" && i + 1 < argc) mode = argv[++i];
-    else if (a == "--ppm" && i + 1 < argc) ppmPath = argv[++i];
-    else if (a == "--repeat" && i + 1 < argc) repeat = std::atoi(argv[++i]);
-    else if (a == "--gi" && i + 2 < argc) { useGI = true; giSamples = (unsigned)std::atoi(argv[++i]); raysPerPixel = (unsigned)std::atoi(argv[++i]); }
-    else if (a == "--all-frames") allFrames = true;
-  }
+struct TexRec { uint32_t kind; float a[3], b[3], s; uint32_t w, h; std::string file; };
 
+// fills `scene` from the CRTS blob at blobPath; bitmaps go through files named after outPath (removed by the caller)
+static int loadScene(const std::string &blobPath, const std::string &outPath, Scene &scene, std::vector<TexRec> &texRecs) {
   std::ifstream in(blobPath, std::ios::binary);
   std::vector<char> data((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
   blob_cursor c;
@@ -121,7 +138,6 @@ int main(int argc, char **argv) {
     return 2;
   }
 
-  Scene scene;
   scene.sceneSettings.image.width = blob_u32(&c);
   scene.sceneSettings.image.height = blob_u32(&c);
   scene.sceneSettings.bucketSize = blob_u32(&c);
@@ -134,8 +150,6 @@ int main(int argc, char **argv) {
   scene.camera.setRotationMatrix() = Matrix<3>(std::vector<float>(f, f + 9));
 
   // ---- textures
-  struct TexRec { uint32_t kind; float a[3], b[3], s; uint32_t w, h; std::string file; };
-  std::vector<TexRec> texRecs;
   uint32_t nTex = blob_u32(&c);
   for (uint32_t t = 0; t < nTex; t++) {
     TexRec r;
@@ -229,6 +243,152 @@ int main(int argc, char **argv) {
     return 2;
   }
 
+  return 0;
+}
+
+static void removeBitmaps(const std::vector<TexRec> &texRecs) {
+  for (auto &r : texRecs)
+    if (!r.file.empty()) std::remove(r.file.c_str());
+}
+
+struct HitRecord { float t, point[3], normal[3], u, v; uint32_t mesh, triangle, hit; };
+static_assert(sizeof(HitRecord) == 48, "HitRecord");
+
+static int rayQueries(int argc, char **argv) {
+  if (argc < 5) {
+    std::fprintf(stderr, "usage: %s --rays scene.crts rays.bin out.bin --what trace|occluded|shoot --type T [--depth N] [--gi-occlusion]\n", argv[0]);
+    return 2;
+  }
+  std::string blobPath = argv[2], raysPath = argv[3], outPath = argv[4], what;
+  std::vector<int> types;
+  std::vector<unsigned> depths;
+  bool giOcclusion = false;
+  auto numbers = [](const std::string &list) {   // "2" or "0,1,2,3"
+    std::vector<int> v;
+    for (size_t at = 0; at <= list.size();) {
+      size_t comma = std::min(list.find(',', at), list.size());
+      v.push_back(std::atoi(list.substr(at, comma - at).c_str()));
+      at = comma + 1;
+    }
+    return v;
+  };
+  for (int i = 5; i < argc; i++) {
+    std::string a = argv[i];
+    if (a == "--what" && i + 1 < argc) what = argv[++i];
+    else if (a == "--type" && i + 1 < argc) types = numbers(argv[++i]);
+    else if (a == "--depth" && i + 1 < argc) { for (int d : numbers(argv[++i])) depths.push_back((unsigned)d); }
+    else if (a == "--gi-occlusion") giOcclusion = true;
+    else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
+  }
+  if (depths.empty()) depths.push_back(5);
+  bool typesOk = !types.empty();
+  for (int t : types) typesOk = typesOk && t >= (int)PrimaryRay && t <= (int)DiffuseRay;
+  if ((what != "trace" && what != "occluded" && what != "shoot") || !typesOk) {
+    std::fprintf(stderr, "--what trace|occluded|shoot and --type 0..4 are required\n");
+    return 2;
+  }
+
+  std::ifstream in(raysPath, std::ios::binary);
+  std::vector<char> bytes((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+  const size_t perRay = what == "occluded" ? 28 : 24;
+  if (!in.good() && !in.eof()) return 2;
+  if (bytes.size() % perRay != 0) {
+    std::fprintf(stderr, "%s: %zu bytes is no multiple of %zu\n", raysPath.c_str(), bytes.size(), perRay);
+    return 2;
+  }
+  const size_t n = bytes.size() / perRay;
+  std::vector<float> values(bytes.size() / 4);
+  std::memcpy(values.data(), bytes.data(), bytes.size());
+  const float *rays = values.data(), *distances = values.data() + 6 * n;
+
+  Scene scene;
+  std::vector<TexRec> texRecs;
+  if (int rc = loadScene(blobPath, outPath, scene, texRecs)) return rc;
+
+  std::ofstream out(outPath, std::ios::binary);
+  auto rayOf = [&](size_t i, int type) {
+    const RayType rayType = (RayType)type;
+    return Ray(Vector(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]), Vector(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]), rayType);
+  };
+  if (what == "shoot") {
+    RayTracer tracer(scene);
+    // the state render() leaves behind for the default tree mode (RayTracer.cpp:205, 270-273), set directly: no frame is wanted
+    tracer.useBounding = true;
+    tracer.boundingType = Tree;
+    std::vector<float> rgb(3 * n);
+    for (int type : types)
+      for (unsigned depth : depths) {
+        tracer.renderOptions = RenderOptions(BVHBucketsThreadPool, depth);
+        for (size_t i = 0; i < n; i++) {
+          Ray ray = rayOf(i, type);
+          Color c = tracer.shootRay(ray, 0);
+          for (int k = 0; k < 3; k++) rgb[3 * i + k] = c[k];
+        }
+        out.write((const char *)rgb.data(), (std::streamsize)rgb.size() * 4);
+      }
+  } else {
+    AccelerationStructure accel(scene);
+    for (int type : types) {
+      if (what == "occluded") {
+        std::vector<uint8_t> occ(n);
+        for (size_t i = 0; i < n; i++) occ[i] = accel.checkForIntersection(rayOf(i, type), distances[i], giOcclusion) ? 1 : 0;
+        out.write((const char *)occ.data(), (std::streamsize)n);
+      } else {
+        std::vector<HitRecord> recs(n);
+        std::memset(recs.data(), 0, n * sizeof(HitRecord));
+        for (size_t i = 0; i < n; i++) {
+          std::optional<IntersectionInformation> info = accel.intersect(rayOf(i, type));
+          if (!info.has_value()) continue;
+          HitRecord &r = recs[i];
+          r.t = info->intersection.distance;
+          for (int k = 0; k < 3; k++) {
+            r.point[k] = info->intersection.hitPoint[k];
+            r.normal[k] = info->intersection.hitNormal[k];
+          }
+#if (defined USE_TEXTURES) && USE_TEXTURES
+          r.u = info->u;
+          r.v = info->v;
+#endif
+          r.mesh = (uint32_t)(info->object - scene.objects.data());
+          r.triangle = (uint32_t)(info->triangle - info->object->triangles.data());
+          r.hit = 1;
+        }
+        out.write((const char *)recs.data(), (std::streamsize)(n * sizeof(HitRecord)));
+      }
+    }
+  }
+  out.close();
+  removeBitmaps(texRecs);
+  std::printf("\n{\"rays\": %zu, \"what\": \"%s\", \"types\": %zu, \"depths\": %zu}\n", n, what.c_str(), types.size(), depths.size());
+  return out.good() ? 0 : 2;
+}
+
+int main(int argc, char **argv) {
+  if (argc == 4 && std::string(argv[1]) == "--camera-ops") return cameraOps(argv[2], argv[3]);
+  if (argc >= 2 && std::string(argv[1]) == "--rays") return rayQueries(argc, argv);
+  if (argc < 3) {
+    std::fprintf(stderr, "usage: %s scene.crts out.f32 [--depth N] [--mode NAME] [--ppm P] [--repeat K] [--gi SAMPLES RAYS_PER_PIXEL] [--all-frames]\n", argv[0]);
+    return 2;
+  }
+  std::string blobPath = argv[1], outPath = argv[2], ppmPath, mode = "bvhpool";
+  unsigned depth = 5;
+  int repeat = 1;
+  bool useGI = false, allFrames = false;
+  unsigned giSamples = 2, raysPerPixel = 1;
+  for (int i = 3; i < argc; i++) {
+    std::string a = argv[i];
+    if (a == "--depth" && i + 1 < argc) depth = std::atoi(argv[++i]);
+    else if (a == "--mode" && i + 1 < argc) mode = argv[++i];
+    else if (a == "--ppm" && i + 1 < argc) ppmPath = argv[++i];
+    else if (a == "--repeat" && i + 1 < argc) repeat = std::atoi(argv[++i]);
+    else if (a == "--gi" && i + 2 < argc) { useGI = true; giSamples = (unsigned)std::atoi(argv[++i]); raysPerPixel = (unsigned)std::atoi(argv[++i]); }
+    else if (a == "--all-frames") allFrames = true;
+  }
+
+  Scene scene;
+  std::vector<TexRec> texRecs;
+  if (int rc = loadScene(blobPath, outPath, scene, texRecs)) return rc;
+
   const unsigned W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
   auto t0 = std::chrono::high_resolution_clock::now();
   RayTracer tracer(scene);
@@ -254,8 +414,7 @@ int main(int argc, char **argv) {
       out.write((const char *)flat.data(), (std::streamsize)flat.size() * 4);
     }
   }
-  for (auto &r : texRecs)
-    if (!r.file.empty()) std::remove(r.file.c_str());
+  removeBitmaps(texRecs);
 
   std::printf("\n{\"render_s\": %.6f, \"render_s_mean\": %.6f, \"build_s\": %.6f, \"width\": %u, \"height\": %u, "
               "\"depth\": %u, \"mode\": \"%s\", \"threads\": %u, \"repeat\": %d}\n",

@@ -202,8 +202,31 @@ def degenerate():
         print("degenerate", case, rgb.shape, "blob", len(blob), "bytes, NaN pixels", int(np.isnan(rgb).any(axis=2).sum()))
 
 
+def queries(names=None):
+    """tests/golden/query_<scene>.npz: the real reference's own intersect, checkForIntersection and shootRay (oracle/ref_driver.cpp
+    --rays) for the ray sets of tests/reference_ray_sets.py, which are built from its answers.  Nothing is written unless the set meets
+    reference_ray_sets.check_census; the files come out byte for byte the same from a fresh reference build."""
+    import reference_ray_sets as rrs
+    oa.build()
+    limit = max(os.path.getsize(os.path.join(HERE, f)) for f in os.listdir(HERE) if not f.startswith("query_"))
+    for name in names or rrs.SCENES:
+        scene = rrs.make_scene(sc, name)
+        blob = sc.to_blob(scene)
+        rs = rrs.build(scene, oa.OracleScene(blob), lambda rays, t: oa.reference_trace(blob, rays, t, textured=True), rrs.FIXTURE_SEED)
+        ans = rrs.reference_answers(oa, blob, scene, rs, name)
+        c = rrs.census(scene, rs, ans)
+        print("query", name, "rays", len(rs["rays"]), c)
+        rrs.check_census(name, c)
+        path = rrs.fixture_path(name)
+        rrs.save_fixture(path, blob, rs, ans)
+        print("     ", os.path.getsize(path), "bytes (limit %d)" % limit)
+        assert os.path.getsize(path) <= limit, "larger than the largest fixture there was: cut ray counts"
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "gi":
+    if len(sys.argv) > 1 and sys.argv[1] == "queries":      # optionally followed by scene names
+        queries(sys.argv[2:])
+    elif len(sys.argv) > 1 and sys.argv[1] == "gi":
         gi_stats()
     elif len(sys.argv) > 1 and sys.argv[1] == "degenerate":
         degenerate()
@@ -216,3 +239,4 @@ if __name__ == "__main__":
         scale_cases()
         scale_frames()
         degenerate()
+        queries()

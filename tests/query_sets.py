@@ -20,16 +20,16 @@ def scene_bounds(scene):
     return v.min(axis=0), v.max(axis=0)
 
 
-def in_plane_rays(scene):
+def in_plane_rays(scene, n=300, seed=7):
     """Rays that start ON a bounding plane of the scene and run IN it: d . n is exactly 0 for every triangle in that plane, the
     reference divides by it (Ray.cpp:19), and a non-primary ray gets hits at t = NaN / inf -- the rays whose filter miss the miss
-    check refutes.  1800 rays: for each axis, for each of lo[axis], hi[axis], 300 times."""
-    rng = np.random.default_rng(7)
+    check refutes.  6 n rays (1800): for each axis, for each of lo[axis], hi[axis], n times."""
+    rng = np.random.default_rng(seed)
     lo, hi = scene_bounds(scene)
     rays = []
     for axis in range(3):
         for plane in (lo[axis], hi[axis]):
-            for _ in range(300):
+            for _ in range(n):
                 o = rng.uniform(lo - 2, hi + 2)
                 o[axis] = plane
                 d = rng.normal(size=3)

@@ -5,8 +5,9 @@ import numpy as np
 import pytest
 
 import degenerate_sets
+import reference_ray_sets as rrs
 import scale_sets
-from helpers import assert_same_floats
+from helpers import assert_same_floats, assert_same_hits
 
 
 def _have(oracle, textured):
@@ -73,3 +74,44 @@ def test_camera_change_matches_reference(oracle, scenes):
     o.set_camera(scene["camera"]["position"], scene["camera"]["matrix"])  # same scene, camera set afterwards
     got, _ = o.render(4)
     assert_same_floats(got, want, "camera")
+
+
+# the ray sets of the query fixtures (tests/reference_ray_sets.py) at ANOTHER seed: the oracle cannot be fitted to tests/golden/query_*.npz
+@pytest.mark.parametrize("name", rrs.SCENES)
+def test_single_rays_match_the_live_reference(oracle, scenes, name):
+    if not (_have(oracle, True) and _have(oracle, False)):
+        pytest.skip("oracle/_ref not built here")
+    scene = rrs.make_scene(scenes, name)
+    blob = scenes.to_blob(scene)
+    o = oracle.OracleScene(blob)
+    rs = rrs.build(scene, o, lambda rays, t: oracle.reference_trace(blob, rays, t, textured=True), rrs.LIVE_SEED)
+    want = rrs.reference_answers(oracle, blob, scene, rs, name, check_plain=False)
+    rrs.check_census(name, rrs.census(scene, rs, want))
+    got = rrs.oracle_answers(o, scene, rs, lambda origin, direction, d: o.occluded(origin, direction, d, gi=True), name)
+    assert np.array_equal(got["shoot_skip"], want["shoot_skip"])
+    for cls in rrs.CLASSES:
+        rows = np.flatnonzero(rs["labels"] == rrs.CLASSES.index(cls))
+        for t in rrs.RAY_TYPES:
+            assert_same_hits(got["hits"][t][rows], want["hits"][t][rows], "%s %s type %d" % (name, cls, t))
+            for d in rrs.DEPTHS:
+                assert_same_floats(got["shoot"][(t, d)][rows], want["shoot"][(t, d)][rows], "%s %s type %d depth %d" % (name, cls, t, d))
+    for rule in ("occ", "occ_gi"):      # occ_gi: checkForIntersection with useGI, under which no mesh is skipped
+        bad = np.flatnonzero(got[rule] != want[rule])
+        assert bad.size == 0, "%s %s: %d of %d pairs differ, first: ray %d distance %r" % (name, rule, bad.size, len(got[rule]), rs["occ_index"][bad[0]],
+                                                                                         rs["occ_dist"][bad[0]])
+
+
+def test_shoot_ray_of_the_driver_is_the_frame_s_pixel(oracle, scenes):
+    """oracle/ref_driver.cpp --rays sets renderOptions, useBounding and boundingType by hand instead of rendering a frame first: its
+    shootRay of a camera ray has to be the colour render() gives that pixel (getRay's normalisation followed by shootRay's)."""
+    if not _have(oracle, False):
+        pytest.skip("oracle/_ref not built here")
+    scene = scenes.make("hw11", width=64, height=36, detail=0.2)
+    blob = scenes.to_blob(scene)
+    frame, _ = oracle.reference_render(blob, max_depth=4)
+    o = oracle.OracleScene(blob)
+    rays = np.array([np.concatenate(o.camera_ray(r, c)) for r in range(o.height) for c in range(o.width)], dtype=np.float32)
+    got = oracle.reference_shoot(blob, rays, 0, 4).reshape(frame.shape)
+    rendered = (frame.view(np.uint32) != 0).any(axis=2)          # (the bucket grid may leave edge pixels unrendered: +0, 0, 0)
+    assert rendered.sum() >= 0.9 * rendered.size and len(np.unique(frame.reshape(-1, 3), axis=0)) > 50
+    assert_same_floats(got[rendered], frame[rendered], "shootRay of the camera rays against render()")
