@@ -90,6 +90,11 @@ def lib():
         L.oracle_sincos_array.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.oracle_gi_array.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.oracle_sincos_vs_libm.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.oracle_shoot_gi.argtypes = [C.c_void_p, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        L.oracle_camera_sample_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.oracle_render_pixels.argtypes = [C.c_void_p, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.oracle_gi_pair_search.restype = C.c_uint64
+        L.oracle_gi_pair_search.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
         _lib = L
     return _lib
 
@@ -161,6 +166,30 @@ class OracleScene:
         out = np.zeros(6, dtype=np.float32)
         self._L.oracle_camera_ray(self._h, row, col, _p(out))
         return out[:3].copy(), out[3:].copy()
+
+    def shoot_gi(self, rays, keys, ray_type=0, options=None):
+        """shoot_ray(ray i with key keys[i], depth 0) in the GI mode: rays float32 [n, 6], keys uint32 [n] -> float32 [n, 3]"""
+        rays = np.ascontiguousarray(rays, dtype=np.float32)
+        keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        assert rays.shape == (len(keys), 6)
+        rgb = np.zeros((len(rays), 3), dtype=np.float32)
+        o = options or make_options(use_gi=1)
+        self._L.oracle_shoot_gi(self._h, C.byref(o), _p(rays), _p(keys), len(rays), ray_type, _p(rgb))
+        return rgb
+
+    def camera_sample_rays(self, rows, cols, keys):
+        """the jittered camera ray of the sample with key keys[i] at pixel (rows[i], cols[i]) -> float32 [n, 6]"""
+        rows, cols, keys = (np.ascontiguousarray(a, dtype=np.uint32) for a in (rows, cols, keys))
+        rays = np.zeros((len(keys), 6), dtype=np.float32)
+        self._L.oracle_camera_sample_rays(self._h, _p(rows), _p(cols), _p(keys), len(keys), _p(rays))
+        return rays
+
+    def render_pixels(self, rows, cols, seeds, options):
+        """pixel (rows[i], cols[i]) of the frame of `options` with gi_seed = seeds[i] -> float32 [n, 3]"""
+        rows, cols, seeds = (np.ascontiguousarray(a, dtype=np.uint32) for a in (rows, cols, seeds))
+        rgb = np.zeros((len(seeds), 3), dtype=np.float32)
+        self._L.oracle_render_pixels(self._h, C.byref(options), _p(rows), _p(cols), _p(seeds), len(seeds), _p(rgb))
+        return rgb
 
     @property
     def mesh_count(self):
@@ -257,6 +286,44 @@ def gi_mix(a, b):
     return int(lib().oracle_gi_mix(a, b))
 
 
+# ---- the generator's inverse, in numpy (nothing of cpu_ref.c is used, so that gi_mix can check it).  gi_mix(a, b) =
+# fmix32(fmix32(a ^ C1) + (b ^ C2) * C3) is a bijection in a for fixed b: fmix32 is xor-shifts and multiplications by odd constants.
+_M32 = np.uint64(0xFFFFFFFF)
+_C1, _C2, _C3 = 0x9E3779B9, 0x7F4A7C15, 0x9E3779B1
+_INV_M1, _INV_M2 = pow(0x85EBCA6B, -1, 1 << 32), pow(0xC2B2AE35, -1, 1 << 32)
+GI_CHILD, GI_DRAW = 0x40000000, 0x80000000       # gi_child_key(K, c) = gi_mix(K, GI_CHILD + c); gi_uniform(K, d) reads gi_mix(K, GI_DRAW + d)
+
+
+def _fmix32_inverse(h):
+    h = h ^ (h >> np.uint64(16))
+    h = (h * np.uint64(_INV_M2)) & _M32
+    h = h ^ (h >> np.uint64(13)) ^ (h >> np.uint64(26))
+    h = (h * np.uint64(_INV_M1)) & _M32
+    return h ^ (h >> np.uint64(16))
+
+
+def gi_mix_inverse(value, b):
+    """The a with gi_mix(a, b) == value, elementwise (uint32 arrays or scalars -> uint32 array).  For a key K: the pixel key that puts K
+    on sample k is gi_mix_inverse(K, k), the frame seed that puts that pixel key on pixel p is gi_mix_inverse(pixel key, p), and the
+    parent key whose child c is K is gi_mix_inverse(K, GI_CHILD + c)."""
+    v = np.asarray(value, dtype=np.uint32).astype(np.uint64)
+    bb = np.asarray(b, dtype=np.uint32).astype(np.uint64)
+    inner = (_fmix32_inverse(v) + np.uint64(1 << 32) - (((bb ^ np.uint64(_C2)) * np.uint64(_C3)) & _M32)) & _M32
+    return (_fmix32_inverse(inner) ^ np.uint64(_C1)).astype(np.uint32)
+
+
+def gi_pair_search(table_bits, d0, first_key=0, n_keys=1 << 32, cap=1 << 16):
+    """Every key K of [first_key, first_key + n_keys) whose draws (gi_uniform(K, d0), gi_uniform(K, d0 + 1)) are, as float bit patterns,
+    a row of table_bits (uint32 [n, 2]) -> (keys uint32 [m], row indices uint32 [m]), in key order."""
+    table = np.ascontiguousarray(table_bits, dtype=np.uint32)
+    assert table.ndim == 2 and table.shape[1] == 2
+    keys, index = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+    m = int(lib().oracle_gi_pair_search(_p(table), len(table), d0, first_key, n_keys, _p(keys), _p(index), cap))
+    if m > cap:
+        raise ValueError("gi_pair_search: %d matches, room for %d" % (m, cap))
+    return keys[:m].copy(), index[:m].copy()
+
+
 # ----------------------------------------------------------------------------- the REAL reference
 def reference_available(textured=False) -> bool:
     return os.path.exists(REF_TEX if textured else REF_PLAIN)
@@ -298,8 +365,9 @@ REF_HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, 3), ("normal"
                           ("mesh", np.uint32), ("triangle", np.uint32), ("hit", np.uint32)])   # triangle: index within its mesh
 
 
-def _reference_rays(blob, payload, what, ray_types, textured, extra, dtype):
-    """one run of the driver's ray mode; ray_types: a list (its trees take longer to build than a few thousand rays to answer)"""
+def _reference_rays(blob, payload, what, ray_types, textured, extra, dtype, seeds=None):
+    """one run of the driver's ray mode; ray_types: a list (its trees take longer to build than a few thousand rays to answer);
+    seeds: uint32 per ray, handed over as --seeds (the GI variants)"""
     if textured is None:
         textured = blob[80:84] != b"\x00\x00\x00\x00"
     exe = REF_TEX if textured else REF_PLAIN
@@ -311,7 +379,11 @@ def _reference_rays(blob, payload, what, ray_types, textured, extra, dtype):
             f.write(blob)
         with open(rp, "wb") as f:
             for a in payload:
-                f.write(np.ascontiguousarray(a, dtype="<f4").tobytes())
+                f.write(np.ascontiguousarray(a, dtype="<u4" if a.dtype == np.uint32 else "<f4").tobytes())
+        if seeds is not None:
+            with open(os.path.join(td, "seeds.bin"), "wb") as f:
+                f.write(np.ascontiguousarray(seeds, dtype="<u4").tobytes())
+            extra = extra + ["--seeds", os.path.join(td, "seeds.bin")]
         subprocess.run([exe, "--rays", sp, rp, op, "--what", what, "--type", ",".join(str(int(t)) for t in ray_types)] + extra,
                        capture_output=True, text=True, check=True, timeout=900)
         return np.fromfile(op, dtype=dtype)
@@ -354,3 +426,41 @@ def reference_shoot(blob: bytes, rays, ray_type, max_depth):
     out = _reference_rays(blob, [rays], "shoot", types, None, ["--depth", ",".join(str(int(d)) for d in depths)], np.float32)
     out = out.reshape(len(types), len(depths), len(rays), 3)
     return out if lists else out[0, 0]
+
+
+# ---- the GI mode of the real reference on a known stream: the driver seeds RayTracer::engine (the reference's own thread_local member)
+# before every ray, so shootRay's and getRay's draws are the reference's distribution(engine) for that seed
+def reference_gi_draws(first, count):
+    """For every seed of [first, first + count): the engine seeded with it, then distribution(engine) twice -> uint32 [count, 2], the
+    float32 bit patterns of the two draws."""
+    if not os.path.exists(REF_PLAIN):
+        raise FileNotFoundError(REF_PLAIN)
+    with tempfile.TemporaryDirectory() as td:
+        op = os.path.join(td, "draws.bin")
+        subprocess.run([REF_PLAIN, "--gi-draws", str(int(first)), str(int(count)), op], capture_output=True, text=True, check=True, timeout=900)
+        return np.fromfile(op, dtype="<u4").reshape(int(count), 2)
+
+
+def _gi_extra(gi_sample_size, max_depth, monte_carlo_bias):
+    return ["--gi", str(int(gi_sample_size)), "--depth", str(int(max_depth)), "--monte-carlo-bias", repr(float(monte_carlo_bias))]
+
+
+def reference_shoot_gi(blob: bytes, rays, seeds, ray_type, max_depth, gi_sample_size=1, monte_carlo_bias=1e-4):
+    """RayTracer::shootRay(Ray(origin, direction, ray_type), 0) of the real reference in the GI mode (USE_GI, GI_SAMPLE_SIZE, MAX_DEPTH,
+    MONTE_CARLO_BIAS as given), the engine seeded with seeds[i] before ray i -> float32 [n, 3]."""
+    rays = _rays6(rays)
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+    assert seeds.shape == (len(rays),)
+    out = _reference_rays(blob, [rays], "shoot", [ray_type], None, _gi_extra(gi_sample_size, max_depth, monte_carlo_bias), np.float32, seeds=seeds)
+    return out.reshape(len(rays), 3)
+
+
+def reference_camera_rays(blob: bytes, rows, cols, seeds, centre=False, max_depth=1, gi_sample_size=1, monte_carlo_bias=1e-4):
+    """centre=False: the Ray RayTracer::getRay(row, col, true) returns with the engine seeded with seeds[i] -> float32 [n, 6].
+    centre=True: getRay(row, col, false) and, the engine seeded, shootRay of that ray in the GI mode -> (float32 [n, 6], float32 [n, 3])."""
+    pixels = np.ascontiguousarray(np.stack([rows, cols], axis=1), dtype=np.uint32)
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+    assert seeds.shape == (len(pixels),)
+    extra = _gi_extra(gi_sample_size, max_depth, monte_carlo_bias) + (["--centre"] if centre else [])
+    out = _reference_rays(blob, [pixels], "camera", [0], None, extra, np.float32, seeds=seeds).reshape(len(pixels), 9 if centre else 6)
+    return (np.ascontiguousarray(out[:, :6]), np.ascontiguousarray(out[:, 6:])) if centre else out

@@ -16,7 +16,8 @@
 //   drives the reference's own Camera (Camera.cpp:33-70).  ops.txt: first line = position (3) and row-major matrix (9)
 //   as hexadecimal float bit patterns; every further line = "<truck|pan|tilt|roll> <3 bit patterns>", applied one after the
 //   other to the same camera.  out.txt: the 12 bit patterns of the camera after every operation, one line each.
-// usage: ref_render --rays <scene.crts> <rays.bin> <out.bin> --what trace|occluded|shoot --type T [--depth N] [--gi-occlusion]
+// usage: ref_render --rays <scene.crts> <rays.bin> <out.bin> --what trace|occluded|shoot|camera --type T [--depth N] [--gi-occlusion]
+//                    [--gi N --seeds <seeds.bin> [--monte-carlo-bias X] [--centre]]
 //   answers single rays with the reference's own functions on the scene of the blob; T = 0..4, the value of enum RayType (Ray.h:14).
 //   T and N may be comma-separated lists: the trees are built once and out.bin holds one block of records per type (and, for shoot,
 //   per type and depth, the depth running fastest), each block in ray order.
@@ -32,6 +33,16 @@
 //               (RayTracer.cpp:205, 270-273).  shootRay and those members are private (RayTracer.h:60-94): this translation unit
 //               alone includes that header with `private` spelt `public`, after every standard header; access is no part of a
 //               mangled name, so it links against the reference's unmodified objects.
+//   --gi N --seeds seeds.bin [--monte-carlo-bias X]  (shoot, camera): the GI build's renderOptions -- USE_GI, GI_SAMPLE_SIZE = N, RAYS_PER_PIXEL
+//               = 1, MONTE_CARLO_BIAS = X (default 1e-4) -- and, before every ray, RayTracer::engine.seed(seeds[i]) on this (the main) thread
+//               (seeds.bin: one little-endian uint32 per ray).  The engine is the reference's own thread_local member
+//               (RayTracer.cpp:28-29); seeding it replaces clock() ^ thread id and nothing else, so the draws of shootRay and getRay
+//               are the reference's distribution(engine) on a known stream.
+//     camera    rays.bin: uint32 (row, col) per entry.  24 bytes: the Ray getRay(row, col, true) returns under the entry's seed
+//               (RayTracer.cpp:61-80).  With --centre, 36 bytes: getRay(row, col, false), then -- the engine seeded -- shootRay(that ray, 0).
+// usage: ref_render --gi-draws FIRST COUNT <out.bin>
+//   for every seed in [FIRST, FIRST + COUNT): RayTracer::engine.seed(seed), then RayTracer::distribution(RayTracer::engine) twice;
+//   out.bin: the two float32 bit patterns per seed.
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -254,6 +265,21 @@ static void removeBitmaps(const std::vector<TexRec> &texRecs) {
 struct HitRecord { float t, point[3], normal[3], u, v; uint32_t mesh, triangle, hit; };
 static_assert(sizeof(HitRecord) == 48, "HitRecord");
 
+static int giDraws(const char *first, const char *count, const char *outPath) {
+  const unsigned long long f = std::strtoull(first, nullptr, 0), n = std::strtoull(count, nullptr, 0);
+  std::vector<float> draws(2 * (size_t)n);
+  for (unsigned long long i = 0; i < n; i++) {
+    RayTracer::engine.seed((unsigned long)(f + i));
+    draws[2 * i] = RayTracer::distribution(RayTracer::engine);
+    draws[2 * i + 1] = RayTracer::distribution(RayTracer::engine);
+  }
+  std::ofstream out(outPath, std::ios::binary);
+  out.write((const char *)draws.data(), (std::streamsize)draws.size() * 4);
+  out.close();
+  std::printf("\n{\"first\": %llu, \"count\": %llu}\n", f, n);
+  return out.good() ? 0 : 2;
+}
+
 static int rayQueries(int argc, char **argv) {
   if (argc < 5) {
     std::fprintf(stderr, "usage: %s --rays scene.crts rays.bin out.bin --what trace|occluded|shoot --type T [--depth N] [--gi-occlusion]\n", argv[0]);
@@ -262,7 +288,10 @@ static int rayQueries(int argc, char **argv) {
   std::string blobPath = argv[2], raysPath = argv[3], outPath = argv[4], what;
   std::vector<int> types;
   std::vector<unsigned> depths;
-  bool giOcclusion = false;
+  bool giOcclusion = false, useGI = false, centre = false;
+  unsigned giSamples = 0;
+  float monteCarloBias = 1e-4;
+  std::string seedsPath;
   auto numbers = [](const std::string &list) {   // "2" or "0,1,2,3"
     std::vector<int> v;
     for (size_t at = 0; at <= list.size();) {
@@ -278,19 +307,28 @@ static int rayQueries(int argc, char **argv) {
     else if (a == "--type" && i + 1 < argc) types = numbers(argv[++i]);
     else if (a == "--depth" && i + 1 < argc) { for (int d : numbers(argv[++i])) depths.push_back((unsigned)d); }
     else if (a == "--gi-occlusion") giOcclusion = true;
+    else if (a == "--gi" && i + 1 < argc) { useGI = true; giSamples = (unsigned)std::atoi(argv[++i]); }
+    else if (a == "--seeds" && i + 1 < argc) seedsPath = argv[++i];
+    else if (a == "--monte-carlo-bias" && i + 1 < argc) monteCarloBias = std::strtof(argv[++i], nullptr);
+    else if (a == "--centre") centre = true;
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
   if (depths.empty()) depths.push_back(5);
   bool typesOk = !types.empty();
   for (int t : types) typesOk = typesOk && t >= (int)PrimaryRay && t <= (int)DiffuseRay;
-  if ((what != "trace" && what != "occluded" && what != "shoot") || !typesOk) {
-    std::fprintf(stderr, "--what trace|occluded|shoot and --type 0..4 are required\n");
+  if (what == "camera" && types.empty()) { types.push_back((int)PrimaryRay); typesOk = true; }
+  if ((what != "trace" && what != "occluded" && what != "shoot" && what != "camera") || !typesOk) {
+    std::fprintf(stderr, "--what trace|occluded|shoot|camera and --type 0..4 are required\n");
+    return 2;
+  }
+  if (useGI != !seedsPath.empty() || (useGI && what != "shoot" && what != "camera") || (what == "camera" && !useGI)) {
+    std::fprintf(stderr, "--gi N and --seeds FILE go together, with --what shoot or camera; camera needs them\n");
     return 2;
   }
 
   std::ifstream in(raysPath, std::ios::binary);
   std::vector<char> bytes((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
-  const size_t perRay = what == "occluded" ? 28 : 24;
+  const size_t perRay = what == "occluded" ? 28 : what == "camera" ? 8 : 24;
   if (!in.good() && !in.eof()) return 2;
   if (bytes.size() % perRay != 0) {
     std::fprintf(stderr, "%s: %zu bytes is no multiple of %zu\n", raysPath.c_str(), bytes.size(), perRay);
@@ -300,6 +338,17 @@ static int rayQueries(int argc, char **argv) {
   std::vector<float> values(bytes.size() / 4);
   std::memcpy(values.data(), bytes.data(), bytes.size());
   const float *rays = values.data(), *distances = values.data() + 6 * n;
+  std::vector<uint32_t> seeds;
+  if (useGI) {
+    std::ifstream sin(seedsPath, std::ios::binary);
+    std::vector<char> sb((std::istreambuf_iterator<char>(sin)), std::istreambuf_iterator<char>());
+    if (sb.size() != 4 * n) {
+      std::fprintf(stderr, "%s: %zu bytes, expected one uint32 for each of %zu rays\n", seedsPath.c_str(), sb.size(), n);
+      return 2;
+    }
+    seeds.resize(n);
+    std::memcpy(seeds.data(), sb.data(), sb.size());
+  }
 
   Scene scene;
   std::vector<TexRec> texRecs;
@@ -318,14 +367,35 @@ static int rayQueries(int argc, char **argv) {
     std::vector<float> rgb(3 * n);
     for (int type : types)
       for (unsigned depth : depths) {
-        tracer.renderOptions = RenderOptions(BVHBucketsThreadPool, depth);
+        tracer.renderOptions = useGI ? RenderOptions(BVHBucketsThreadPool, depth, true, giSamples, 1, 1e-4, 1e-4, 1e-4, monteCarloBias)
+                                     : RenderOptions(BVHBucketsThreadPool, depth);
         for (size_t i = 0; i < n; i++) {
           Ray ray = rayOf(i, type);
+          if (useGI) RayTracer::engine.seed(seeds[i]);
           Color c = tracer.shootRay(ray, 0);
           for (int k = 0; k < 3; k++) rgb[3 * i + k] = c[k];
         }
         out.write((const char *)rgb.data(), (std::streamsize)rgb.size() * 4);
       }
+  } else if (what == "camera") {
+    RayTracer tracer(scene);
+    tracer.useBounding = true;
+    tracer.boundingType = Tree;
+    tracer.renderOptions = RenderOptions(BVHBucketsThreadPool, depths[0], true, giSamples, 1, 1e-4, 1e-4, 1e-4, monteCarloBias);
+    std::vector<uint32_t> pixels(2 * n);
+    std::memcpy(pixels.data(), bytes.data(), bytes.size());
+    for (size_t i = 0; i < n; i++) {
+      float rec[9];
+      RayTracer::engine.seed(seeds[i]);
+      Ray ray = tracer.getRay(pixels[2 * i], pixels[2 * i + 1], !centre);
+      for (int k = 0; k < 3; k++) { rec[k] = ray.origin[k]; rec[3 + k] = ray.direction[k]; }
+      if (centre) {
+        RayTracer::engine.seed(seeds[i]);
+        Color c = tracer.shootRay(ray, 0);
+        for (int k = 0; k < 3; k++) rec[6 + k] = c[k];
+      }
+      out.write((const char *)rec, centre ? 36 : 24);
+    }
   } else {
     AccelerationStructure accel(scene);
     for (int type : types) {
@@ -366,6 +436,7 @@ static int rayQueries(int argc, char **argv) {
 int main(int argc, char **argv) {
   if (argc == 4 && std::string(argv[1]) == "--camera-ops") return cameraOps(argv[2], argv[3]);
   if (argc >= 2 && std::string(argv[1]) == "--rays") return rayQueries(argc, argv);
+  if (argc == 5 && std::string(argv[1]) == "--gi-draws") return giDraws(argv[2], argv[3], argv[4]);
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s scene.crts out.f32 [--depth N] [--mode NAME] [--ppm P] [--repeat K] [--gi SAMPLES RAYS_PER_PIXEL] [--all-frames]\n", argv[0]);
     return 2;

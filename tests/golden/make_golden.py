@@ -223,9 +223,42 @@ def queries(names=None):
         assert os.path.getsize(path) <= limit, "larger than the largest fixture there was: cut ray counts"
 
 
+def gi_pairs(names=None):
+    """tests/golden/gi_pairs_<scene>.npz: the GI mode of the real reference on a known stream (oracle/ref_driver.cpp seeds its engine)
+    for the cases of tests/gi_reference_sets.py.  First the pair search: the reference's first two draws for every engine seed of
+    [SEED_FIRST, SEED_FIRST + SEED_COUNT), then all 2^32 keys for draws 2, 3 (hit pairs) and draws 0, 1 (jitter pairs) among them,
+    compared as float bit patterns.  Expected per kind: SEED_COUNT * 2^32 / 2^48 * 4/9 (the share of seeds whose two draws are both
+    multiples of 2^-24), about 230 for 2^25 seeds.  Nothing is written unless every scene's set meets gi_reference_sets.check_census."""
+    import time
+    import gi_reference_sets as grs
+    oa.build()
+    t0 = time.time()
+    pairs = grs.find_pairs(oa)
+    estimate = grs.SEED_COUNT * 2.0 ** 32 / 2.0 ** 48 * 4 / 9
+    print("gi_pairs: seeds [%d, %d), 2^32 keys: %d hit pairs, %d jitter pairs (estimate %.0f each) in %.0f s" % (
+        grs.SEED_FIRST, grs.SEED_FIRST + grs.SEED_COUNT, len(pairs["hit"][0]), len(pairs["jitter"][0]), estimate, time.time() - t0))
+    limit = max(os.path.getsize(os.path.join(HERE, f)) for f in os.listdir(HERE) if not f.startswith(("query_", "gi_pairs_")))
+    done = []
+    for name in names or grs.SCENES:
+        scene = grs.rrs.make_scene(sc, name)
+        blob = sc.to_blob(scene)
+        fx = grs.build(oa, scene, blob, pairs)
+        c = grs.census(oa, scene, oa.OracleScene(blob), lambda rays, t: oa.reference_trace(blob, rays, t, textured=True), fx)
+        print("gi_pairs", name, c)
+        grs.check_census(name, scene, c)
+        done.append((name, blob, fx))
+    for name, blob, fx in done:
+        path = grs.fixture_path(name)
+        grs.save_fixture(path, blob, fx)
+        print("     ", name, os.path.getsize(path), "bytes (limit %d)" % limit)
+        assert os.path.getsize(path) <= limit, "larger than the largest fixture there was: cut case counts"
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "queries":      # optionally followed by scene names
         queries(sys.argv[2:])
+    elif len(sys.argv) > 1 and sys.argv[1] == "gi_pairs":   # optionally followed by scene names
+        gi_pairs(sys.argv[2:])
     elif len(sys.argv) > 1 and sys.argv[1] == "gi":
         gi_stats()
     elif len(sys.argv) > 1 and sys.argv[1] == "degenerate":
@@ -240,3 +273,4 @@ if __name__ == "__main__":
         scale_frames()
         degenerate()
         queries()
+        gi_pairs()

@@ -1,7 +1,11 @@
 """The GI / multi-sample mode (RayTracer.cpp:90-104, 331-354).
 
-The reference seeds that mode's generator from clock() ^ thread id, so none of its frames can be pinned; what is defined is the
-DISTRIBUTION of its frames.  The tests therefore come in three layers:
+The reference seeds that mode's generator from clock() ^ thread id, so none of its frames AS IT RENDERS THEM can be pinned; what is
+defined is the DISTRIBUTION of its frames.  The tests here therefore come in three layers (a fourth, exact one is elsewhere: the driver
+can seed the reference's engine, and for keys whose draws are the very floats of a seeded engine the reference's shootRay and getRay are
+pinned bit for bit -- tests/gi_reference_sets.py, tests/test_gi_reference_host.py, tests/test_gpu_gi_reference.py.  That layer covers one
+sample per hit and one ray per pixel; the moment tests below stay the only check of GI_SAMPLE_SIZE > 1 and RAYS_PER_PIXEL > 1 against the
+reference):
   1. the arithmetic the mode adds -- glibc's sinf / cosf, restated in oracle/cpu_ref.c and (independently) in
      csrc/glibc_sincosf.h, and the counter-based generator both sides define -- bit for bit against libm / each other;
   2. the oracle with that generator against per-pixel moments of the REAL reference's frames (tests/golden/gi_stats.npz, made by

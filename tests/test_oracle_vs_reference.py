@@ -115,3 +115,29 @@ def test_shoot_ray_of_the_driver_is_the_frame_s_pixel(oracle, scenes):
     rendered = (frame.view(np.uint32) != 0).any(axis=2)          # (the bucket grid may leave edge pixels unrendered: +0, 0, 0)
     assert rendered.sum() >= 0.9 * rendered.size and len(np.unique(frame.reshape(-1, 3), axis=0)) > 50
     assert_same_floats(got[rendered], frame[rendered], "shootRay of the camera rays against render()")
+
+
+# the GI mode on matched (key, engine seed) pairs (tests/gi_reference_sets.py) that are NOT in tests/golden/gi_pairs_*.npz: the search
+# repeated on another seed range and an eighth of the keys, the fixture's rays and pixels with the fresh pairs, the reference run now
+LIVE_GI_SEEDS, LIVE_GI_KEYS = ((1 << 25) + 1, 1 << 23), (0, 1 << 29)
+
+
+def test_gi_mode_matches_the_live_reference_on_fresh_pairs(oracle, scenes):
+    import gi_reference_sets as grs
+    if not _have(oracle, False):
+        pytest.skip("oracle/_ref not built here")
+    pairs = grs.find_pairs(oracle, *LIVE_GI_SEEDS, *LIVE_GI_KEYS)
+    blob, fx = grs.load_fixture("hw11")
+    print("fresh pairs: %d hit, %d jitter" % (len(pairs["hit"][0]), len(pairs["jitter"][0])))
+    # expected 2^23 * 2^29 / 2^48 * 4/9 = 7 of each kind; the ranges are fixed, so the counts are too
+    assert len(pairs["hit"][0]) >= 3 and len(pairs["jitter"][0]) >= 3
+    assert not np.isin(pairs["hit"][1], fx["hit_seeds"]).any() and not np.isin(pairs["jitter"][1], fx["jitter_seeds"]).any()
+    o = oracle.OracleScene(blob)
+    live = grs.with_pairs(oracle, blob, fx, pairs, o.width)
+    got = grs.oracle_answers(oracle, o, live)
+    assert_same_floats(got["q_rgb"], live["q_rgb"], "shootRay, N = 1, MAX_DEPTH = 1")
+    assert_same_floats(got["m_rgb"], live["m_rgb"], "shootRay below a mirror")
+    assert_same_floats(got["p_rgb"], grs.frame_pixel(live["p_rgb"]), "frame pixels")
+    assert np.array_equal(got["p_ray"].view(np.uint32), live["p_ray"].view(np.uint32)), "getRay(row, col, false)"
+    assert np.array_equal(got["j_rays"].view(np.uint32), live["j_rays"].view(np.uint32)), "getRay(row, col, true)"
+    assert (live["q_rgb"] != fx["q_rgb"]).any(axis=1).mean() > 0.8, "other draws, other colours"
