@@ -147,6 +147,23 @@ def make_adaptive(**fields):
     return a
 
 
+class Denoise(C.Structure):
+    """crt_denoise: the settings of the GI frames' denoiser (make_denoise fills it)"""
+    _fields_ = [("size", C.c_uint32), ("iterations", C.c_uint32), ("normal_squarings", C.c_uint32), ("sigma_colour", C.c_float),
+                ("sigma_plane", C.c_float), ("floor", C.c_float)]
+
+
+def make_denoise(**fields):
+    """crt_denoise_defaults (4, 5, 2.0, 0.02, 1e-6) with the given fields replaced, e.g. make_denoise(iterations=3)."""
+    d = Denoise()
+    lib().crt_denoise_defaults(C.byref(d))
+    for k, v in fields.items():
+        if k not in dict(Denoise._fields_) or k == "size":
+            raise KeyError("crt_denoise has no field %r" % k)
+        setattr(d, k, v)
+    return d
+
+
 # crt_hit as a numpy record (what Tracer.trace_rays returns, and the layout of a torch.uint8 [n, 48] output tensor)
 HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, 3), ("normal", np.float32, 3), ("u", np.float32), ("v", np.float32),
                       ("mesh", np.uint32), ("triangle", np.uint32), ("hit", np.uint32)])
@@ -199,6 +216,7 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_st
                   "crt_shoot_rays_enqueue", "crt_shoot_rays_gi_enqueue", "crt_get_shoot_report", "crt_query_scratch_generation",
                   "crt_camera_sample_rays_device", "crt_accumulate_samples_device", "crt_render_progressive", "crt_progressive_samples",
                   "crt_adaptive_defaults", "crt_adaptive_work_bytes", "crt_adaptive_step_device", "crt_render_adaptive", "crt_progressive_active",
+                  "crt_denoise_defaults", "crt_denoise_work_bytes", "crt_sample_variance_device", "crt_denoise_device", "crt_render_denoised",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -277,6 +295,13 @@ def lib():
     L.crt_render_adaptive.argtypes = [vp, C.POINTER(Options), C.POINTER(Adaptive), u32, u32, vp, vp]
     L.crt_progressive_active.argtypes = [vp]
     L.crt_progressive_active.restype = C.c_uint64
+    L.crt_denoise_defaults.argtypes = [C.POINTER(Denoise)]
+    L.crt_denoise_defaults.restype = None
+    L.crt_denoise_work_bytes.argtypes = [u32, u32]
+    L.crt_denoise_work_bytes.restype = C.c_size_t
+    L.crt_sample_variance_device.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
+    L.crt_denoise_device.argtypes = [vp, C.POINTER(Denoise), u32, u32, vp, vp, vp, vp, vp, vp, vp]
+    L.crt_render_denoised.argtypes = [vp, C.POINTER(Denoise), vp, vp]
     L.crt_host_shoot_stats_layout.argtypes = [C.POINTER(u32), u32]
     L.crt_host_shoot_stats_layout.restype = u32
     L.crt_get_kernel_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -872,6 +897,40 @@ class Tracer:
             if on_pass is not None and on_pass(done, rgb.copy(), counts.copy()) is False:
                 break
         return rgb, counts
+
+    # ---- denoising (include/crt_hip.h: crt_sample_variance_device, crt_denoise_device, crt_render_denoised)
+    @staticmethod
+    def denoise_work_bytes(width, height) -> int:
+        """Bytes of the work area denoise_device needs for a width x height image."""
+        return int(lib().crt_denoise_work_bytes(int(width), int(height)))
+
+    def sample_variance_device(self, d_sum_ptr, d_sq_ptr, d_counts_ptr, n_pixels, d_mean_ptr, d_var_ptr, stream_ptr=None):
+        """The mean and the variance of the mean of the adaptive fold's state: sum float32 [n * 3], sq float32 [n], counts uint32 [n] ->
+        mean float32 [n * 3], var float32 [n]; device arrays of the caller's.  Enqueues and returns."""
+        self._single("sample_variance_device")
+        self._check(lib().crt_sample_variance_device(self.ctx, C.c_void_p(d_sum_ptr), C.c_void_p(d_sq_ptr), C.c_void_p(d_counts_ptr), int(n_pixels),
+                                                     C.c_void_p(d_mean_ptr), C.c_void_p(d_var_ptr), C.c_void_p(stream_ptr or 0)))
+
+    def denoise_device(self, denoise, width, height, d_rgb_ptr, d_var_ptr, d_hits_ptr, d_out_rgb_ptr, d_work_ptr, d_out_var_ptr=None,
+                       stream_ptr=None):
+        """The a-trous filter on a width x height image of the caller's: rgb float32 [H * W * 3], var float32 [H * W], hits uint8 [H * W, 48]
+        (crt_hit records, e.g. trace_rays_device's) -> out_rgb (may be rgb), out_var (or None); work denoise_work_bytes(width, height)
+        bytes, 16-byte aligned.  Enqueues and returns."""
+        self._single("denoise_device")
+        self._check(lib().crt_denoise_device(self.ctx, C.byref(denoise), int(width), int(height), C.c_void_p(d_rgb_ptr), C.c_void_p(d_var_ptr),
+                                             C.c_void_p(d_hits_ptr), C.c_void_p(d_out_rgb_ptr), C.c_void_p(d_out_var_ptr or 0),
+                                             C.c_void_p(d_work_ptr), C.c_void_p(stream_ptr or 0)))
+
+    def render_denoised(self, denoise=None, rgb8=False):
+        """The context's adaptive frame, under way or finished (render_adaptive), denoised with `denoise` (make_denoise; None: the
+        defaults) -> rgb float32 [H, W, 3]; with rgb8 also the PPMColor quantisation, (rgb, uint8 [H, W, 3]).  The frame itself is left
+        exactly as it was and can be continued."""
+        self._single("render_denoised")
+        d = denoise if denoise is not None else make_denoise()
+        rgb = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        q8 = np.zeros((self.height, self.width, 3), dtype=np.uint8) if rgb8 else None
+        self._check(lib().crt_render_denoised(self.ctx, C.byref(d), _p(rgb), _p(q8) if rgb8 else None))
+        return (rgb, q8) if rgb8 else rgb
 
     def shoot_stats(self) -> ShootStats:
         """rays / levels / level_rays / shadow_records / rerouted / kernel_ms of the last radiance query (waits for it)."""

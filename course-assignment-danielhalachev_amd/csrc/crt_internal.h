@@ -6,6 +6,7 @@
 //   crt_multi.hip     one scene on several devices behind one call
 //   crt_query.hip     the queries for what the caller supplies, behind one call path: ray queries (closest hit / occlusion, the camera's rays),
 //                     direct lighting of hit records and points, radiance queries; their scratch and statistics
+//   crt_denoise.hip   the denoiser's primitives: the variance of the fold's state, the a-trous filter on first-hit guides
 //   crt_testhooks.hip unit-test hooks (libcrt_hip_test.so only)
 #pragma once
 
@@ -165,6 +166,12 @@ CRT_INTERNAL int fetch_counters(crt_ctx *ctx, const crt_options *o, uint64_t pix
 // ---- crt_query.hip
 CRT_INTERNAL void query_destroy(crt_ctx *ctx);
 CRT_INTERNAL void query_progressive_reset(crt_ctx *ctx);   // crt_set_camera, crt_render*: crt_progressive_samples is 0 again
+// ---- crt_denoise.hip: the denoiser's settings check and launches, for crt_render_denoised (crt_query.hip)
+CRT_INTERNAL int denoise_check(crt_ctx *ctx, const char *what, const crt_denoise *d);
+CRT_INTERNAL int denoise_launch_variance(crt_ctx *ctx, const float *d_sum, const float *d_sq, const uint32_t *d_counts, uint64_t n, float *d_mean,
+                                         float *d_var, hipStream_t stream);
+CRT_INTERNAL int denoise_launch(crt_ctx *ctx, const crt_denoise *d, uint32_t width, uint32_t height, const float *d_rgb, const float *d_var,
+                                const crt_hit *d_hits, float *d_out_rgb, float *d_out_var, void *d_work, hipStream_t stream);
 // ---- crt_abi.hip
 CRT_INTERNAL uint64_t coverage_items(uint32_t width, uint32_t height, const crt_rect *rects, uint32_t n_rects, std::vector<WorkItem> &items);
 CRT_INTERNAL void launch_unpack_items(const float *packed, const WorkItem *items, uint32_t n_items, float *frame, uint32_t width, uint32_t height,

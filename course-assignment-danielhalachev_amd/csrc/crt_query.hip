@@ -21,6 +21,8 @@
 //                     kernels: csrc/kernel_progressive.h
 //   an adaptive frame  crt_render_adaptive, behind it: the same loop over a pixel list that shrinks -- the step, the rule and the
 //                     compaction of crt_adaptive_step_device; kernels: csrc/kernel_adaptive.h, the rule: csrc/adaptive_rule.h
+//   a denoised frame  crt_render_denoised, last: the adaptive frame's state through the denoiser's primitives (crt_denoise.hip), guided by
+//                     the first hits of the camera's rays; it changes nothing of the frame
 #include "crt_internal.h"
 #include "glibc_powf.h"
 #include "gi_random.h"
@@ -225,6 +227,13 @@ struct crt_query_state {
     crt_adaptive prog_adaptive{};
     uint64_t prog_active = 0;   // entries of prog_list[prog_cur]; pass 0 has no list (every pixel)
     int prog_cur = 0;
+    // crt_render_denoised: the guides (the first hits of the camera's centre rays, traced at a frame's first denoise call and kept until the
+    // frame is reset), the mean and variance of the fold's state, the denoised frame, the primitive's work area, the quantised frame
+    DeviceArray<crt_hit> den_hits;
+    DeviceArray<float> den_mean, den_var, den_out;
+    DeviceArray<float4> den_work;
+    DeviceArray<uint8_t> den_q8;
+    bool den_guides = false;
     uint64_t level_peak[MAX_GENERATIONS] = {};   // the widest level g of a pass since a progressive frame's sample 0 began (shoot_numbers)
     // the radiance queries' own device words: made by the first radiance call of a context (shoot_words_reserve)
     bool shoot_words_made() const { return swords.p && d_report.p && d_hits0.p; }
@@ -249,6 +258,7 @@ void query_progressive_reset(crt_ctx *ctx) {
     if (!ctx->query) return;
     ctx->query->prog_samples = 0;
     ctx->query->prog_active = 0;
+    ctx->query->den_guides = false;
 }
 
 // a radiance pass's numbers, once its last copy has arrived
@@ -1090,6 +1100,7 @@ extern "C" int crt_render_progressive(crt_ctx *ctx, const crt_options *options, 
         if (s == 0) {
             std::fill(q->level_peak, q->level_peak + MAX_GENERATIONS, 0ull);
             q->prog_is_adaptive = false;
+            q->den_guides = false;
             q->prog_active = pixels;   // (a uniform frame shoots every pixel in every pass)
         }
         if ((rc = launch_sample_rays(ctx, options->gi_seed, s, nullptr, pixels, q->prog_rays.p, q->prog_keys.p, ctx->stream)) ||
@@ -1228,6 +1239,7 @@ extern "C" int crt_render_adaptive(crt_ctx *ctx, const crt_options *options, con
         if (s == 0) {
             std::fill(q->level_peak, q->level_peak + MAX_GENERATIONS, 0ull);
             q->prog_is_adaptive = true;
+            q->den_guides = false;     // (a new frame: crt_render_denoised traces its guides again)
             q->prog_adaptive = *adaptive;
             q->prog_active = pixels;
         }
@@ -1252,6 +1264,50 @@ extern "C" int crt_render_adaptive(crt_ctx *ctx, const crt_options *options, con
     }
     if (out_rgb) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, ctx->d_frame, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (out_counts) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_counts, q->prog_counts.p, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return CRT_OK;
+}
+
+// ---- denoising (crt_denoise.hip, csrc/kernel_denoise.h, csrc/denoise_rule.h): the adaptive frame under way or finished, filtered into a
+// buffer of its own.  Nothing of the frame changes: the persistent colour buffer, sum, sq, counts, the lists and crt_progressive_samples
+// are only read, so the frame can be denoised after any pass and continued.
+
+extern "C" int crt_render_denoised(crt_ctx *ctx, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8) {
+    const char *what = "crt_render_denoised";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = denoise_check(ctx, what, denoise)) return rc;
+    if (crt_progressive_samples(ctx) == 0) {
+        ctx->error = std::string(what) + ": no adaptive frame is under way (crt_render_adaptive starts one; crt_set_camera and crt_render* end it)";
+        return CRT_ERR_INVALID;
+    }
+    if (!ctx->query->prog_is_adaptive) {
+        ctx->error = std::string(what) + ": the frame under way is a UNIFORM progressive frame, which keeps no second moment (sq): use crt_render_adaptive "
+                                         "with min_samples = max_samples";
+        return CRT_ERR_INVALID;
+    }
+    const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
+    if (pixels >= (1ull << 31)) { ctx->error = std::string(what) + ": width * height >= 2^31"; return CRT_ERR_INVALID; }
+    int rc;
+    if ((rc = query_begin(ctx, ctx->stream, CALL_QUERY))) return rc;
+    crt_query_state *q = ctx->query;
+    if ((rc = reserve_all(ctx, q->den_hits, pixels, q->den_mean, 3 * pixels, q->den_var, pixels, q->den_out, 3 * pixels, q->den_work,
+                          (crt_denoise_work_bytes(ctx->width, ctx->height) + sizeof(float4) - 1) / sizeof(float4), q->den_q8, 3 * pixels)))
+        return rc;
+    if (!q->den_guides) {   // the first hits of the camera's centre rays, as CRT_RAY_PRIMARY: the rays of a pass are scratch between passes
+        if ((rc = crt_camera_rays_device(ctx, q->prog_rays.p, ctx->stream)) ||
+            (rc = query_run(ctx, closest_call(q->prog_rays.p, pixels, CRT_RAY_PRIMARY, q->den_hits.p), ctx->stream, true)))
+            return rc;
+        q->den_guides = true;
+    }
+    if ((rc = denoise_launch_variance(ctx, q->prog_sum.p, q->prog_sq.p, q->prog_counts.p, pixels, q->den_mean.p, q->den_var.p, ctx->stream)) ||
+        (rc = denoise_launch(ctx, denoise, ctx->width, ctx->height, q->den_mean.p, q->den_var.p, q->den_hits.p, q->den_out.p, nullptr, q->den_work.p,
+                             ctx->stream)))
+        return rc;
+    if (out_rgb) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, q->den_out.p, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (out_rgb8) {
+        if ((rc = crt_quantize_device(ctx, q->den_out.p, 3 * pixels, q->den_q8.p, ctx->stream))) return rc;
+        CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb8, q->den_q8.p, 3 * pixels, hipMemcpyDeviceToHost, ctx->stream));
+    }
     CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return CRT_OK;
 }

@@ -415,6 +415,23 @@ std::vector<std::vector<Color>> RayTracer::renderAdaptive(const std::string &pat
   return colorBuffer;
 }
 
+std::vector<std::vector<Color>> RayTracer::renderDenoised(const std::string &pathToImage, const crt_denoise &denoise) {
+  if (multi) throw std::runtime_error("renderDenoised: not available on a multi-device tracer");
+  const unsigned int W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
+  std::vector<float> denoised((size_t)W * H * 3, 0.0f);
+  std::vector<uint8_t> q(pathToImage.empty() ? 0 : (size_t)W * H * 3);
+  const int rc = crt_render_denoised(ctx, &denoise, denoised.data(), pathToImage.empty() ? nullptr : q.data());
+  if (rc != CRT_OK) throw std::runtime_error(std::string("renderDenoised failed: ") + crt_last_error(ctx));
+  if (!pathToImage.empty()) writePPMQuantized(pathToImage, q.data(), W, H);
+  std::vector<std::vector<Color>> colorBuffer(H, std::vector<Color>(W));
+  for (unsigned int y = 0; y < H; y++)
+    for (unsigned int x = 0; x < W; x++) {
+      const float *p = &denoised[((size_t)y * W + x) * 3];
+      colorBuffer[y][x] = Color(p[0], p[1], p[2]);
+    }
+  return colorBuffer;
+}
+
 void RayTracer::exportPPM(const std::string &pathToImage, const std::vector<std::vector<Color>> &colorBuffer) {
   const unsigned int W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
   std::vector<float> flatRGB((size_t)W * H * 3, 0.0f);

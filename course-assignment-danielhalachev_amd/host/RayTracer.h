@@ -130,6 +130,12 @@ class RayTracer {
   std::vector<std::vector<Color>> renderAdaptive(const std::string &pathToImage, RenderOptions renderOptions, const crt_adaptive &adaptive,
                                                  unsigned int passesPerCall = 1, std::vector<uint32_t> *counts = nullptr);
 
+  // ---- denoising (crt_hip.h: crt_render_denoised): the adaptive frame renderAdaptive left, under way or finished, through the
+  // variance-guided a-trous filter with the settings of `denoise` (crt_denoise_defaults), guided by the first hits of the camera's rays.
+  // The frame itself is left as it was.  The PPM, if a path is given, is the denoised frame quantised by the PPMColor rule.
+  // Single-device tracers only.
+  std::vector<std::vector<Color>> renderDenoised(const std::string &pathToImage, const crt_denoise &denoise);
+
   // flat access for callers that do not want the vector-of-vectors copy
   int renderFlat(const std::string &pathToImage, const RenderOptions &renderOptions, float *outRGB, unsigned int counters = 0);
   crt_ctx *context() const { return multi ? crt_multi_context(multi, 0) : ctx; }

@@ -612,6 +612,107 @@ int crt_render_adaptive(crt_ctx *ctx, const crt_options *options, const crt_adap
                         float *out_rgb, uint32_t *out_counts);
 uint64_t crt_progressive_active(const crt_ctx *ctx);
 
+/* ---- Denoising: a spatial, variance-guided, edge-avoiding a-trous wavelet filter for GI frames of a few samples per pixel -- SVGF's
+ * spatial half, with no temporal part.  It uses what the calls above already compute: the per-pixel variance that the adaptive fold's
+ * sum[3], sq and count stand for, and the first hit of every pixel (crt_camera_rays_device + crt_trace_rays_device: point, normal, t, mesh)
+ * as edge-stopping guides.  Kernels: csrc/kernel_denoise.h; the rule, one header for host and device: csrc/denoise_rule.h.  It is
+ * additive: no frame, query, radiance, progressive or adaptive kernel is involved, and a frame that is denoised and then continued is the
+ * same frame as before.  Single-device contexts only.
+ *
+ * The rule.  Every line is one float32 operation with one rounding, in the order written.
+ * Definitions.  finite(x) is (x - x) == 0.0f.  A pixel is usable when its three colour channels and its variance are all finite.  A guide is
+ *   {n[3], x[3], t, mesh}, taken from a crt_hit: normal, point, t and mesh; mesh = 0xFFFFFFFF when hit == 0.
+ *   h = {1/16, 1/4, 3/8, 1/4, 1/16}.  g3 = {1,2,1; 2,4,2; 1,2,1} as floats.
+ * From the fold's state (crt_sample_variance_device).  n = count.  When n == 0, colour and variance are 0.  Otherwise:
+ *     inv = 1.0f / (float)n
+ *     C_c = sum_c * inv                              // the adaptive rule's mean
+ *     q   = sq * inv
+ *     mm  = (C_r*C_r + C_g*C_g) + C_b*C_b
+ *     var = q - mm
+ *     V   = (var > 0 ? var : 0) * inv                // the variance OF THE MEAN
+ * Iteration k (step = 1 << k), centre p = (y, x).  A centre that is not usable passes through: C' = C, V' = V.  Otherwise:
+ *     vnum = 0; vden = 0
+ *     for dy in -1..1, dx in -1..1 (row-major), q = (y+dy, x+dx) inside the frame and finite(V_q):
+ *         vnum = vnum + g3[dy+1][dx+1] * V_q
+ *         vden = vden + g3[dy+1][dx+1]
+ *     vp  = vnum / vden
+ *     s2  = sigma_colour * sigma_colour
+ *     den = s2 * vp + floor
+ *     tol = sigma_plane * t_p
+ *     acc = {0,0,0}; accv = 0; wsum = 0
+ *     for dy in -2..2, dx in -2..2 (row-major), q = (y + dy*step, x + dx*step) in signed arithmetic:
+ *         skip q outside the frame
+ *         skip q not usable
+ *         skip q with mesh_q != mesh_p
+ *         if mesh_p is a hit:
+ *             d  = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z
+ *             d  = d > 0 ? d : 0
+ *             d  = d * d, normal_squarings times
+ *             e  = (n_p.x*(x_q.x - x_p.x) + n_p.y*(x_q.y - x_p.y)) + n_p.z*(x_q.z - x_p.z)
+ *             ae = fabsf(e)
+ *             skip unless ae <= tol                  // a NaN skips
+ *             wz = tol > 0 ? 1.0f - ae / tol : 1.0f
+ *             g  = d * wz
+ *         else:
+ *             g = 1.0f
+ *         dr, dg, db = C_q - C_p
+ *         d2 = (dr*dr + dg*dg) + db*db
+ *         wl = den / (den + d2)
+ *         w  = ((h[dy+2] * h[dx+2]) * g) * wl
+ *         acc_c = acc_c + w * C_q,c
+ *         accv  = accv + (w*w) * V_q
+ *         wsum  = wsum + w
+ *     if wsum > 0:
+ *         inv = 1.0f / wsum
+ *         C'_c = acc_c * inv
+ *         V'   = accv * (inv * inv)
+ *     else:
+ *         pass through
+ *   iterations == 0 copies input to output.  A NaN that arises from overflow is whatever these lines give.
+ * Known limits.  There is no albedo demodulation, because the library has no albedo query: texture detail inside one mesh is protected by
+ *   the colour weight alone.  Reflections in a flat mirror are guided by the mirror's own plane.  With count == 1 every variance is 0, so
+ *   the filter hardly smooths: use at least 2 samples.
+ * crt_denoise: size must be sizeof(crt_denoise) = 24, iterations <= 8, normal_squarings <= 16, sigma_colour and sigma_plane >= 0 and finite,
+ *   floor > 0 and finite: anything else is CRT_ERR_INVALID, with nothing enqueued.  crt_denoise_defaults: 4, 5, 2.0f, 0.02f, 1e-6f.
+ * crt_sample_variance_device: for i < n_pixels the lines "from the fold's state" on d_sum[3i ..], d_sq[i], d_counts[i] -- the arrays
+ *   crt_adaptive_step_device keeps -- into d_mean[3i ..] and d_var[i].  n_pixels == 0 is CRT_OK and touches nothing; a NULL array is
+ *   CRT_ERR_INVALID.
+ * crt_denoise_device: `iterations` iterations of the rule on the width x height image d_rgb (3 floats a pixel), d_var (one float a pixel) with
+ *   the guides of d_hits (one crt_hit a pixel, row-major; e.g. what crt_trace_rays_device wrote for crt_camera_rays_device's rays), into
+ *   d_out_rgb and d_out_var.  width and height are the CALLER'S, not the scene's: the primitive serves any image with guides.  d_out_var may
+ *   be NULL.  d_out_rgb may be d_rgb (and d_out_var d_var), because the pack kernel copies first; any other overlap is not allowed.  d_work
+ *   is the caller's, at least crt_denoise_work_bytes(width, height) bytes (64 a pixel: a 32-byte guide record and two 16-byte {r, g, b, V}
+ *   records that ping-pong between the iterations), aligned to 16 bytes; nothing may overlap it.  CRT_ERR_INVALID, with nothing enqueued:
+ *   an invalid crt_denoise (above), width * height >= 2^31, a NULL required array, a misaligned d_work.  width * height of 0 with non-NULL
+ *   arrays is CRT_OK and touches nothing.  One launch to pack and one an iteration (iterations == 0: device-to-device copies).
+ * Both device calls only ENQUEUE on `stream` (a hipStream_t, NULL = default): no wait, no allocation, no readback.  They compose with
+ *   crt_shoot_rays_gi_enqueue, crt_adaptive_step_device and crt_trace_rays_device on one stream.
+ * crt_render_denoised acts on the ADAPTIVE frame under way or finished (crt_progressive_samples(ctx) > 0, started by crt_render_adaptive).
+ *   Anything else is CRT_ERR_INVALID, with a message that says why; a uniform crt_render_progressive frame keeps no sq: the message says
+ *   to use crt_render_adaptive with min_samples = max_samples.  The guides are the first hits of the camera's centre rays --
+ *   crt_camera_rays_device's rays traced as CRT_RAY_PRIMARY through crt_trace_rays_device's path (crt_get_query_stats describes that
+ *   trace) --, traced at a frame's first denoise call and kept until the frame is reset (crt_set_camera, crt_render*, a new first pass).
+ *   Then variance, pack and the iterations run into a context-owned buffer of their own, and the result goes to out_rgb (height * width * 3
+ *   floats) and / or out_rgb8 (crt_quantize_device's rule); host memory, either may be NULL; the call returns when they are there.  It
+ *   leaves the persistent colour buffer, sum, sq and counts, the active list, crt_progressive_samples, crt_stats and the ray queues'
+ *   sizing exactly as they were, so a frame can be denoised after any pass and continued.  Its buffers are allocated on first use and
+ *   freed by crt_destroy. */
+typedef struct crt_denoise {
+    uint32_t size;              /* sizeof(crt_denoise) = 24 */
+    uint32_t iterations;        /* 0..8 */
+    uint32_t normal_squarings;  /* 0..16 */
+    float sigma_colour;         /* >= 0, finite: colour distances are weighed against sigma_colour^2 x the local variance of the mean */
+    float sigma_plane;          /* >= 0, finite: a tap may lie sigma_plane x t off the centre's tangent plane */
+    float floor;                /* > 0, finite: added to that variance term, so that a pixel of variance 0 still averages with its equals */
+} crt_denoise;
+void crt_denoise_defaults(crt_denoise *d);       /* 4, 5, 2.0f, 0.02f, 1e-6f */
+size_t crt_denoise_work_bytes(uint32_t width, uint32_t height);
+int crt_sample_variance_device(crt_ctx *ctx, const float *d_sum, const float *d_sq, const uint32_t *d_counts, uint64_t n_pixels, float *d_mean,
+                               float *d_var, void *stream);
+int crt_denoise_device(crt_ctx *ctx, const crt_denoise *denoise, uint32_t width, uint32_t height, const float *d_rgb, const float *d_var,
+                       const crt_hit *d_hits, float *d_out_rgb, float *d_out_var, void *d_work, void *stream);
+int crt_render_denoised(crt_ctx *ctx, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8);
+
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
  * stream per listed device (a device may be listed more than once); the covered 8x8 tiles are dealt round-robin, every
