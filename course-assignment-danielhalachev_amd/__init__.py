@@ -164,6 +164,40 @@ def make_denoise(**fields):
     return d
 
 
+class Temporal(C.Structure):
+    """crt_temporal: the settings of the GI frames' temporal accumulation (make_temporal fills it)"""
+    _fields_ = [("size", C.c_uint32), ("max_history", C.c_float), ("normal_min", C.c_float), ("sigma_plane", C.c_float)]
+
+
+class CameraPose(C.Structure):
+    """crt_camera_pose: what crt_set_camera takes"""
+    _fields_ = [("position", C.c_float * 3), ("matrix", C.c_float * 9)]
+
+
+def make_temporal(**fields):
+    """crt_temporal_defaults (64.0, 0.9, 0.02) with the given fields replaced, e.g. make_temporal(max_history=16.0)."""
+    t = Temporal()
+    lib().crt_temporal_defaults(C.byref(t))
+    for k, v in fields.items():
+        if k not in dict(Temporal._fields_) or k == "size":
+            raise KeyError("crt_temporal has no field %r" % k)
+        setattr(t, k, v)
+    return t
+
+
+def make_pose(position, matrix):
+    """a crt_camera_pose of 3 and 9 floats"""
+    pose = CameraPose()
+    pose.position[:] = [float(v) for v in np.asarray(position, dtype=np.float32).reshape(3)]
+    pose.matrix[:] = [float(v) for v in np.asarray(matrix, dtype=np.float32).reshape(9)]
+    return pose
+
+
+# crt_history_pixel as a numpy record (64 bytes; the layout of a torch.uint8 [n, 64] tensor)
+HISTORY_DTYPE = np.dtype([("n", np.float32, 3), ("t", np.float32), ("x", np.float32, 3), ("mesh", np.uint32), ("c", np.float32, 3),
+                          ("m2", np.float32), ("weight", np.float32), ("pad", np.float32, 3)])
+
+
 # crt_hit as a numpy record (what Tracer.trace_rays returns, and the layout of a torch.uint8 [n, 48] output tensor)
 HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, 3), ("normal", np.float32, 3), ("u", np.float32), ("v", np.float32),
                       ("mesh", np.uint32), ("triangle", np.uint32), ("hit", np.uint32)])
@@ -217,6 +251,7 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_st
                   "crt_camera_sample_rays_device", "crt_accumulate_samples_device", "crt_render_progressive", "crt_progressive_samples",
                   "crt_adaptive_defaults", "crt_adaptive_work_bytes", "crt_adaptive_step_device", "crt_render_adaptive", "crt_progressive_active",
                   "crt_denoise_defaults", "crt_denoise_work_bytes", "crt_sample_variance_device", "crt_denoise_device", "crt_render_denoised",
+                  "crt_temporal_defaults", "crt_temporal_device", "crt_render_accumulated", "crt_history_reset", "crt_history_frames",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -302,6 +337,13 @@ def lib():
     L.crt_sample_variance_device.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
     L.crt_denoise_device.argtypes = [vp, C.POINTER(Denoise), u32, u32, vp, vp, vp, vp, vp, vp, vp]
     L.crt_render_denoised.argtypes = [vp, C.POINTER(Denoise), vp, vp]
+    L.crt_temporal_defaults.argtypes = [C.POINTER(Temporal)]
+    L.crt_temporal_defaults.restype = None
+    L.crt_temporal_device.argtypes = [vp, C.POINTER(Temporal), u32, u32, C.POINTER(CameraPose)] + [vp] * 10
+    L.crt_render_accumulated.argtypes = [vp, C.POINTER(Temporal), C.POINTER(Denoise), vp, vp, vp]
+    L.crt_history_reset.argtypes = [vp]
+    L.crt_history_frames.argtypes = [vp]
+    L.crt_history_frames.restype = u32
     L.crt_host_shoot_stats_layout.argtypes = [C.POINTER(u32), u32]
     L.crt_host_shoot_stats_layout.restype = u32
     L.crt_get_kernel_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -931,6 +973,45 @@ class Tracer:
         q8 = np.zeros((self.height, self.width, 3), dtype=np.uint8) if rgb8 else None
         self._check(lib().crt_render_denoised(self.ctx, C.byref(d), _p(rgb), _p(q8) if rgb8 else None))
         return (rgb, q8) if rgb8 else rgb
+
+    # ---- temporal accumulation (include/crt_hip.h: crt_temporal_device, crt_render_accumulated, crt_history_reset, crt_history_frames)
+    def temporal_device(self, temporal, width, height, prev_pose, d_prev_ptr, d_sum_ptr, d_sq_ptr, d_counts_ptr, d_hits_ptr, d_next_ptr, d_out_rgb_ptr,
+                        d_out_var_ptr=None, d_out_valid_ptr=None, stream_ptr=None):
+        """The previous frame's history (prev uint8 [H * W, 64], crt_history_pixel records, with its pose: make_pose; or None and None)
+        reprojected and merged with the fold's state sum float32 [H * W * 3], sq float32 [H * W], counts uint32 [H * W] under the guides of
+        hits uint8 [H * W, 48] -> next uint8 [H * W, 64], out_rgb float32 [H * W * 3], out_var float32 [H * W] (or None), out_valid uint8
+        [H * W] (or None); device arrays of the caller's, prev and next aligned to 16 bytes.  Enqueues and returns."""
+        self._single("temporal_device")
+        self._check(lib().crt_temporal_device(self.ctx, C.byref(temporal), int(width), int(height), C.byref(prev_pose) if prev_pose is not None else None,
+                                              C.c_void_p(d_prev_ptr or 0), C.c_void_p(d_sum_ptr), C.c_void_p(d_sq_ptr), C.c_void_p(d_counts_ptr),
+                                              C.c_void_p(d_hits_ptr), C.c_void_p(d_next_ptr), C.c_void_p(d_out_rgb_ptr), C.c_void_p(d_out_var_ptr or 0),
+                                              C.c_void_p(d_out_valid_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def render_accumulated(self, temporal=None, denoise=None, rgb8=False, valid=False):
+        """The context's adaptive frame, under way or finished (render_adaptive), merged with the last frame's history with `temporal`
+        (make_temporal; None: the defaults) and then filtered with `denoise` (make_denoise; None: no spatial filter) -> rgb float32
+        [H, W, 3]; with rgb8 also the PPMColor quantisation uint8 [H, W, 3], with valid also the valid taps per pixel uint8 [H, W], as a
+        tuple in that order.  The frame itself is left exactly as it was and can be continued; the history survives set_camera.  Give
+        consecutive frames different gi_seed values."""
+        self._single("render_accumulated")
+        t = temporal if temporal is not None else make_temporal()
+        rgb = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        q8 = np.zeros((self.height, self.width, 3), dtype=np.uint8) if rgb8 else None
+        taps = np.zeros((self.height, self.width), dtype=np.uint8) if valid else None
+        self._check(lib().crt_render_accumulated(self.ctx, C.byref(t), C.byref(denoise) if denoise is not None else None, _p(rgb),
+                                                 _p(q8) if rgb8 else None, _p(taps) if valid else None))
+        out = (rgb,) + ((q8,) if rgb8 else ()) + ((taps,) if valid else ())
+        return out if len(out) > 1 else rgb
+
+    def history_reset(self):
+        """Drops the accumulated history: the next render_accumulated is a first frame again."""
+        self._single("history_reset")
+        self._check(lib().crt_history_reset(self.ctx))
+
+    def history_frames(self) -> int:
+        """The frames merged into the history since the last history_reset."""
+        self._single("history_frames")
+        return int(lib().crt_history_frames(self.ctx))
 
     def shoot_stats(self) -> ShootStats:
         """rays / levels / level_rays / shadow_records / rerouted / kernel_ms of the last radiance query (waits for it)."""

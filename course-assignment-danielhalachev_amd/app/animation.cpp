@@ -5,6 +5,9 @@
 // What differs is the plumbing around the same frames: --in-flight K (default 2) keeps K frames in flight on the GPU
 // (crt::RayTracer::renderAsync), and the P3 text files -- about 25 MB each at 1920x1080, an order of magnitude more host
 // time than the frame takes to render -- are formatted by a few writer threads while the next frames render.
+// --gi SAMPLE_SIZE --adaptive T MIN MAX renders the same orbit as GI frames, one at a time on the one context, each with renderAdaptive to
+// completion and the seed base + frame index; --denoise [K] writes each frame through the a-trous filter, and --temporal [MAX_HISTORY]
+// merges each frame with the history of the frames before it first (renderAccumulated).
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -67,7 +70,10 @@ struct Writers {  // a few threads that turn quantised frames into PPM files
 int main(int argc, char **argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s scene.crtscene out_prefix [--folder DIR] [--depth N] [--fps F] [--seconds S] [--radius R] [--device D] "
-                         "[--in-flight K] [--writers N] [--no-ppm]\n", argv[0]);
+                         "[--in-flight K] [--writers N] [--no-ppm]\n"
+                         "       [--gi SAMPLE_SIZE --adaptive THRESHOLD MIN MAX [--seed S] [--denoise [ITERATIONS]] [--temporal [MAX_HISTORY]]]   (GI frames, one at a\n"
+                         "        time: every pixel is shot MIN .. MAX times; --denoise: through crt_hip.h's crt_denoise; --temporal: merged with the\n"
+                         "        history of the frames before it, crt_hip.h's crt_temporal, then through the filter if --denoise is given)\n", argv[0]);
     return 2;
   }
   std::string scenePath = argv[1], prefix = argv[2], folder;
@@ -77,6 +83,11 @@ int main(int argc, char **argv) {
   int device = 0;
   unsigned inFlight = 2, nWriters = 4;
   bool writeFiles = true;
+  bool useGI = false, adaptive = false, denoise = false, temporal = false;
+  unsigned giSamples = 2, adaptiveMin = 0, adaptiveMax = 0, seed = 0;
+  float adaptiveThreshold = 0.0f, maxHistory = -1.0f;  // (-1: crt_temporal_defaults')
+  int denoiseIterations = -1;                          // (-1: crt_denoise_defaults')
+  auto number = [&](int i) { return i < argc && ((argv[i][0] >= '0' && argv[i][0] <= '9') || argv[i][0] == '.'); };
   for (int i = 3; i < argc; i++) {
     if (!strcmp(argv[i], "--folder") && i + 1 < argc) folder = argv[++i];
     else if (!strcmp(argv[i], "--depth") && i + 1 < argc) depth = (unsigned)atoi(argv[++i]);
@@ -87,6 +98,18 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--in-flight") && i + 1 < argc) inFlight = (unsigned)atoi(argv[++i]);
     else if (!strcmp(argv[i], "--writers") && i + 1 < argc) nWriters = (unsigned)atoi(argv[++i]);
     else if (!strcmp(argv[i], "--no-ppm")) writeFiles = false;
+    else if (!strcmp(argv[i], "--gi") && i + 1 < argc) { useGI = true; giSamples = (unsigned)atoi(argv[++i]); }
+    else if (!strcmp(argv[i], "--seed") && i + 1 < argc) seed = (unsigned)strtoul(argv[++i], nullptr, 10);
+    else if (!strcmp(argv[i], "--adaptive") && i + 3 < argc) {
+      adaptive = true; adaptiveThreshold = (float)atof(argv[++i]); adaptiveMin = (unsigned)atoi(argv[++i]); adaptiveMax = (unsigned)atoi(argv[++i]);
+    }
+    else if (!strcmp(argv[i], "--denoise")) { denoise = true; if (number(i + 1)) denoiseIterations = atoi(argv[++i]); }
+    else if (!strcmp(argv[i], "--temporal")) { temporal = true; if (number(i + 1)) maxHistory = (float)atof(argv[++i]); }
+  }
+  if (useGI != adaptive || ((denoise || temporal) && !useGI)) {
+    std::fprintf(stderr, "error: --gi needs --adaptive and --adaptive needs --gi; --denoise and --temporal need both\n"
+                         "usage: %s scene.crtscene out_prefix --gi SAMPLE_SIZE --adaptive THRESHOLD MIN MAX [--denoise [ITERATIONS]] [--temporal [MAX_HISTORY]]\n", argv[0]);
+    return 2;
   }
   try {
     crt::SceneParser parser;
@@ -94,10 +117,12 @@ int main(int argc, char **argv) {
     crt::RayTracer tracer(scene, device);
     tracer.setFramesInFlight(inFlight ? inFlight : 1);
     const unsigned W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
-    crt::RenderOptions options(crt::BVHBucketsThreadPool, depth, false);
+    crt::RenderOptions options(crt::BVHBucketsThreadPool, depth, useGI, giSamples, 1);
+    if (useGI) tracer.setGISeed(seed);  // frame k uses seed + k: renderAdaptive takes the next one
     Writers writers(writeFiles ? (nWriters ? nWriters : 1) : 0, W, H);
     const float DEG_CHANGE = 360.0f / (FPS * SECONDS);
     float degrees = 0;
+    double shareSum = 0.0;  // --temporal: the share of hit pixels with at least one valid history tap, summed over the frames
     std::deque<std::pair<int, std::string>> inflight;  // (slot, file) of the frames enqueued and not yet collected
     auto collect = [&]() {
       const std::pair<int, std::string> f = inflight.front();
@@ -117,6 +142,28 @@ int main(int argc, char **argv) {
       tracer.setCamera().setRotationMatrix() = crt::Matrix3::identity();
       float lookAtAngle = std::atan2(deltaX, deltaZ) * (180.0f / M_PIf);
       tracer.setCamera().pan(lookAtAngle);
+      if (useGI) {  // one frame at a time: the adaptive frame to completion, then what is written of it
+        const std::string path = writeFiles ? prefix + std::to_string(t) + ".ppm" : std::string();
+        crt_adaptive a;
+        crt_adaptive_defaults(&a);
+        a.threshold = adaptiveThreshold; a.min_samples = adaptiveMin; a.max_samples = adaptiveMax;
+        crt_denoise d;
+        crt_denoise_defaults(&d);
+        if (denoiseIterations >= 0) d.iterations = (uint32_t)denoiseIterations;
+        tracer.renderAdaptive(denoise || temporal ? std::string() : path, options, a);
+        if (temporal) {
+          crt_temporal h;
+          crt_temporal_defaults(&h);
+          if (maxHistory >= 0.0f) h.max_history = maxHistory;
+          double share = 0.0;
+          tracer.renderAccumulated(path, h, denoise ? &d : nullptr, &share);
+          shareSum += share;
+        }
+        else if (denoise) tracer.renderDenoised(path, d);
+        frames++;
+        degrees += DEG_CHANGE;
+        continue;
+      }
       if (inflight.size() >= tracer.framesInFlight()) collect();  // the ring is full: the oldest frame first
       inflight.emplace_back(tracer.renderAsync(options), prefix + std::to_string(t) + ".ppm");
       frames++;
@@ -127,10 +174,16 @@ int main(int argc, char **argv) {
     writers.close();
     const auto t2 = std::chrono::steady_clock::now();
     const double render_s = std::chrono::duration<double>(t1 - t0).count(), total_s = std::chrono::duration<double>(t2 - t0).count();
-    std::printf("{\"frames\": %u, \"width\": %u, \"height\": %u, \"depth\": %u, \"frames_in_flight\": %u, \"render_s\": %.6f, "
-                "\"frames_per_s\": %.3f, \"with_ppm_s\": %.6f, \"frames_per_s_with_ppm\": %.3f, \"ppm_files\": %s}\n",
-                frames, W, H, depth, tracer.framesInFlight(), render_s, frames / render_s, total_s, frames / total_s,
-                writeFiles ? "true" : "false");
+    if (useGI)
+      std::printf("{\"frames\": %u, \"width\": %u, \"height\": %u, \"depth\": %u, \"gi_sample_size\": %u, \"adaptive\": [%g, %u, %u], \"denoise\": %s, "
+                  "\"temporal\": %s, \"valid_history_share\": %.6f, \"render_s\": %.6f, \"frames_per_s\": %.3f, \"ppm_files\": %s}\n",
+                  frames, W, H, depth, giSamples, (double)adaptiveThreshold, adaptiveMin, adaptiveMax, denoise ? "true" : "false", temporal ? "true" : "false",
+                  temporal && frames ? shareSum / frames : 0.0, total_s, frames / total_s, writeFiles ? "true" : "false");
+    else
+      std::printf("{\"frames\": %u, \"width\": %u, \"height\": %u, \"depth\": %u, \"frames_in_flight\": %u, \"render_s\": %.6f, "
+                  "\"frames_per_s\": %.3f, \"with_ppm_s\": %.6f, \"frames_per_s_with_ppm\": %.3f, \"ppm_files\": %s}\n",
+                  frames, W, H, depth, tracer.framesInFlight(), render_s, frames / render_s, total_s, frames / total_s,
+                  writeFiles ? "true" : "false");
   } catch (const std::exception &e) {
     std::fprintf(stderr, "error: %s\n", e.what());
     return 1;

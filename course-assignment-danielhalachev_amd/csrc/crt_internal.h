@@ -7,6 +7,7 @@
 //   crt_query.hip     the queries for what the caller supplies, behind one call path: ray queries (closest hit / occlusion, the camera's rays),
 //                     direct lighting of hit records and points, radiance queries; their scratch and statistics
 //   crt_denoise.hip   the denoiser's primitives: the variance of the fold's state, the a-trous filter on first-hit guides
+//   crt_temporal.hip  the temporal accumulation's primitive: the last frame's history reprojected and merged with the fold's state
 //   crt_testhooks.hip unit-test hooks (libcrt_hip_test.so only)
 #pragma once
 
@@ -172,6 +173,11 @@ CRT_INTERNAL int denoise_launch_variance(crt_ctx *ctx, const float *d_sum, const
                                          float *d_var, hipStream_t stream);
 CRT_INTERNAL int denoise_launch(crt_ctx *ctx, const crt_denoise *d, uint32_t width, uint32_t height, const float *d_rgb, const float *d_var,
                                 const crt_hit *d_hits, float *d_out_rgb, float *d_out_var, void *d_work, hipStream_t stream);
+// ---- crt_temporal.hip: the temporal accumulation's settings check and launch, for crt_render_accumulated (crt_query.hip)
+CRT_INTERNAL int temporal_check(crt_ctx *ctx, const char *what, const crt_temporal *t);
+CRT_INTERNAL int temporal_launch(crt_ctx *ctx, const crt_temporal *t, uint32_t width, uint32_t height, const crt_camera_pose *prev_pose,
+                                 const crt_history_pixel *d_prev, const float *d_sum, const float *d_sq, const uint32_t *d_counts, const crt_hit *d_hits,
+                                 crt_history_pixel *d_next, float *d_out_rgb, float *d_out_var, uint8_t *d_out_valid, hipStream_t stream);
 // ---- crt_abi.hip
 CRT_INTERNAL uint64_t coverage_items(uint32_t width, uint32_t height, const crt_rect *rects, uint32_t n_rects, std::vector<WorkItem> &items);
 CRT_INTERNAL void launch_unpack_items(const float *packed, const WorkItem *items, uint32_t n_items, float *frame, uint32_t width, uint32_t height,

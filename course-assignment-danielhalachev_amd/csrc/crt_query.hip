@@ -23,6 +23,8 @@
 //                     compaction of crt_adaptive_step_device; kernels: csrc/kernel_adaptive.h, the rule: csrc/adaptive_rule.h
 //   a denoised frame  crt_render_denoised, last: the adaptive frame's state through the denoiser's primitives (crt_denoise.hip), guided by
 //                     the first hits of the camera's rays; it changes nothing of the frame
+//   an accumulated frame  crt_render_accumulated: that state merged with the last frame's history through the temporal primitive
+//                     (crt_temporal.hip), then through the denoiser's launches; the context's two history slots
 #include "crt_internal.h"
 #include "glibc_powf.h"
 #include "gi_random.h"
@@ -234,6 +236,18 @@ struct crt_query_state {
     DeviceArray<float4> den_work;
     DeviceArray<uint8_t> den_q8;
     bool den_guides = false;
+    // crt_render_accumulated: the frame's serial number (it advances wherever den_guides is dropped), the two history slots with the pose
+    // of the frame that wrote each -- hist[hist_cur] is `current`, the other one `previous` --, the serial `current` was written at, the
+    // frames merged since crt_history_reset, and the merged colour, variance and valid-tap counts
+    uint64_t frame_serial = 0, hist_serial = 0;
+    DeviceArray<crt_history_pixel> hist[2];
+    crt_camera_pose hist_pose[2] = {};
+    int hist_cur = 0;
+    bool hist_has_cur = false, hist_has_prev = false;
+    uint32_t hist_frames = 0;
+    DeviceArray<float> acc_rgb, acc_var;
+    DeviceArray<uint8_t> acc_valid;
+    void new_frame() { den_guides = false; frame_serial++; }   // the guides and `current` are the ended frame's
     uint64_t level_peak[MAX_GENERATIONS] = {};   // the widest level g of a pass since a progressive frame's sample 0 began (shoot_numbers)
     // the radiance queries' own device words: made by the first radiance call of a context (shoot_words_reserve)
     bool shoot_words_made() const { return swords.p && d_report.p && d_hits0.p; }
@@ -258,7 +272,7 @@ void query_progressive_reset(crt_ctx *ctx) {
     if (!ctx->query) return;
     ctx->query->prog_samples = 0;
     ctx->query->prog_active = 0;
-    ctx->query->den_guides = false;
+    ctx->query->new_frame();
 }
 
 // a radiance pass's numbers, once its last copy has arrived
@@ -1100,7 +1114,7 @@ extern "C" int crt_render_progressive(crt_ctx *ctx, const crt_options *options, 
         if (s == 0) {
             std::fill(q->level_peak, q->level_peak + MAX_GENERATIONS, 0ull);
             q->prog_is_adaptive = false;
-            q->den_guides = false;
+            q->new_frame();
             q->prog_active = pixels;   // (a uniform frame shoots every pixel in every pass)
         }
         if ((rc = launch_sample_rays(ctx, options->gi_seed, s, nullptr, pixels, q->prog_rays.p, q->prog_keys.p, ctx->stream)) ||
@@ -1239,7 +1253,7 @@ extern "C" int crt_render_adaptive(crt_ctx *ctx, const crt_options *options, con
         if (s == 0) {
             std::fill(q->level_peak, q->level_peak + MAX_GENERATIONS, 0ull);
             q->prog_is_adaptive = true;
-            q->den_guides = false;     // (a new frame: crt_render_denoised traces its guides again)
+            q->new_frame();            // (a new frame: crt_render_denoised traces its guides again)
             q->prog_adaptive = *adaptive;
             q->prog_active = pixels;
         }
@@ -1272,10 +1286,8 @@ extern "C" int crt_render_adaptive(crt_ctx *ctx, const crt_options *options, con
 // buffer of its own.  Nothing of the frame changes: the persistent colour buffer, sum, sq, counts, the lists and crt_progressive_samples
 // are only read, so the frame can be denoised after any pass and continued.
 
-extern "C" int crt_render_denoised(crt_ctx *ctx, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8) {
-    const char *what = "crt_render_denoised";
-    if (!ctx) return CRT_ERR_INVALID;
-    if (int rc = denoise_check(ctx, what, denoise)) return rc;
+// what crt_render_denoised and crt_render_accumulated ask of the context's frame
+static int adaptive_frame_check(crt_ctx *ctx, const char *what) {
     if (crt_progressive_samples(ctx) == 0) {
         ctx->error = std::string(what) + ": no adaptive frame is under way (crt_render_adaptive starts one; crt_set_camera and crt_render* end it)";
         return CRT_ERR_INVALID;
@@ -1285,20 +1297,36 @@ extern "C" int crt_render_denoised(crt_ctx *ctx, const crt_denoise *denoise, flo
                                          "with min_samples = max_samples";
         return CRT_ERR_INVALID;
     }
+    if ((uint64_t)ctx->width * ctx->height >= (1ull << 31)) { ctx->error = std::string(what) + ": width * height >= 2^31"; return CRT_ERR_INVALID; }
+    return CRT_OK;
+}
+
+// the frame's guides, traced at the frame's first call of either kind: the first hits of the camera's centre rays, as CRT_RAY_PRIMARY (the
+// rays of a pass are scratch between passes); den_hits is reserved
+static int frame_guides(crt_ctx *ctx, const uint64_t pixels) {
+    crt_query_state *q = ctx->query;
+    if (q->den_guides) return CRT_OK;
+    int rc;
+    if ((rc = crt_camera_rays_device(ctx, q->prog_rays.p, ctx->stream)) ||
+        (rc = query_run(ctx, closest_call(q->prog_rays.p, pixels, CRT_RAY_PRIMARY, q->den_hits.p), ctx->stream, true)))
+        return rc;
+    q->den_guides = true;
+    return CRT_OK;
+}
+
+extern "C" int crt_render_denoised(crt_ctx *ctx, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8) {
+    const char *what = "crt_render_denoised";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = denoise_check(ctx, what, denoise)) return rc;
+    if (int rc = adaptive_frame_check(ctx, what)) return rc;
     const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
-    if (pixels >= (1ull << 31)) { ctx->error = std::string(what) + ": width * height >= 2^31"; return CRT_ERR_INVALID; }
     int rc;
     if ((rc = query_begin(ctx, ctx->stream, CALL_QUERY))) return rc;
     crt_query_state *q = ctx->query;
     if ((rc = reserve_all(ctx, q->den_hits, pixels, q->den_mean, 3 * pixels, q->den_var, pixels, q->den_out, 3 * pixels, q->den_work,
-                          (crt_denoise_work_bytes(ctx->width, ctx->height) + sizeof(float4) - 1) / sizeof(float4), q->den_q8, 3 * pixels)))
+                          (crt_denoise_work_bytes(ctx->width, ctx->height) + sizeof(float4) - 1) / sizeof(float4), q->den_q8, 3 * pixels)) ||
+        (rc = frame_guides(ctx, pixels)))
         return rc;
-    if (!q->den_guides) {   // the first hits of the camera's centre rays, as CRT_RAY_PRIMARY: the rays of a pass are scratch between passes
-        if ((rc = crt_camera_rays_device(ctx, q->prog_rays.p, ctx->stream)) ||
-            (rc = query_run(ctx, closest_call(q->prog_rays.p, pixels, CRT_RAY_PRIMARY, q->den_hits.p), ctx->stream, true)))
-            return rc;
-        q->den_guides = true;
-    }
     if ((rc = denoise_launch_variance(ctx, q->prog_sum.p, q->prog_sq.p, q->prog_counts.p, pixels, q->den_mean.p, q->den_var.p, ctx->stream)) ||
         (rc = denoise_launch(ctx, denoise, ctx->width, ctx->height, q->den_mean.p, q->den_var.p, q->den_hits.p, q->den_out.p, nullptr, q->den_work.p,
                              ctx->stream)))
@@ -1311,3 +1339,68 @@ extern "C" int crt_render_denoised(crt_ctx *ctx, const crt_denoise *denoise, flo
     CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return CRT_OK;
 }
+
+// ---- temporal accumulation (crt_temporal.hip, csrc/kernel_temporal.h, csrc/temporal_rule.h): the adaptive frame's state merged with the
+// last frame's history, into buffers of its own.  The frame is only read, as crt_render_denoised reads it.  `previous` changes only when a
+// call finds a new frame's serial, so every call on one frame merges the same history.
+
+extern "C" int crt_render_accumulated(crt_ctx *ctx, const crt_temporal *temporal, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8,
+                                      uint8_t *out_valid) {
+    const char *what = "crt_render_accumulated";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = temporal_check(ctx, what, temporal)) return rc;
+    if (denoise)
+        if (int rc = denoise_check(ctx, what, denoise)) return rc;
+    if (int rc = adaptive_frame_check(ctx, what)) return rc;
+    const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
+    int rc;
+    if ((rc = query_begin(ctx, ctx->stream, CALL_QUERY))) return rc;
+    crt_query_state *q = ctx->query;
+    if ((rc = reserve_all(ctx, q->den_hits, pixels, q->hist[0], pixels, q->hist[1], pixels, q->acc_rgb, 3 * pixels, q->acc_var, pixels, q->acc_valid,
+                          pixels, q->den_q8, 3 * pixels)) ||
+        (denoise && (rc = reserve_all(ctx, q->den_out, 3 * pixels, q->den_work,
+                                      (crt_denoise_work_bytes(ctx->width, ctx->height) + sizeof(float4) - 1) / sizeof(float4)))) ||
+        (rc = frame_guides(ctx, pixels)))
+        return rc;
+    if (q->hist_has_cur && q->hist_serial != q->frame_serial) {   // `current` is an ended frame's: it is the previous history from here on
+        q->hist_cur ^= 1;
+        q->hist_has_prev = true;
+        q->hist_has_cur = false;
+    }
+    const int cur = q->hist_cur;
+    if ((rc = temporal_launch(ctx, temporal, ctx->width, ctx->height, &q->hist_pose[cur ^ 1], q->hist_has_prev ? q->hist[cur ^ 1].p : nullptr,
+                              q->prog_sum.p, q->prog_sq.p, q->prog_counts.p, q->den_hits.p, q->hist[cur].p, q->acc_rgb.p, q->acc_var.p, q->acc_valid.p,
+                              ctx->stream)))
+        return rc;
+    if (!q->hist_has_cur) q->hist_frames++;   // once a frame
+    q->hist_has_cur = true;
+    q->hist_serial = q->frame_serial;
+    memcpy(q->hist_pose[cur].position, ctx->frame.cam_pos, sizeof(q->hist_pose[cur].position));
+    memcpy(q->hist_pose[cur].matrix, ctx->frame.cam, sizeof(q->hist_pose[cur].matrix));
+    const float *result = q->acc_rgb.p;
+    if (denoise) {
+        if ((rc = denoise_launch(ctx, denoise, ctx->width, ctx->height, q->acc_rgb.p, q->acc_var.p, q->den_hits.p, q->den_out.p, nullptr, q->den_work.p,
+                                 ctx->stream)))
+            return rc;
+        result = q->den_out.p;
+    }
+    if (out_rgb) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, result, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (out_rgb8) {
+        if ((rc = crt_quantize_device(ctx, result, 3 * pixels, q->den_q8.p, ctx->stream))) return rc;
+        CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb8, q->den_q8.p, 3 * pixels, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (out_valid) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_valid, q->acc_valid.p, pixels, hipMemcpyDeviceToHost, ctx->stream));
+    CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return CRT_OK;
+}
+
+extern "C" int crt_history_reset(crt_ctx *ctx) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (crt_query_state *q = ctx->query) {   // (the slots stay allocated: nothing reads them until a call has written one again)
+        q->hist_has_cur = q->hist_has_prev = false;
+        q->hist_frames = 0;
+    }
+    return CRT_OK;
+}
+
+extern "C" uint32_t crt_history_frames(const crt_ctx *ctx) { return ctx && ctx->query ? ctx->query->hist_frames : 0u; }

@@ -432,6 +432,44 @@ std::vector<std::vector<Color>> RayTracer::renderDenoised(const std::string &pat
   return colorBuffer;
 }
 
+std::vector<std::vector<Color>> RayTracer::renderAccumulated(const std::string &pathToImage, const crt_temporal &temporal, const crt_denoise *denoise,
+                                                             double *validShare) {
+  if (multi) throw std::runtime_error("renderAccumulated: not available on a multi-device tracer");
+  const unsigned int W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
+  std::vector<float> merged((size_t)W * H * 3, 0.0f);
+  std::vector<uint8_t> q(pathToImage.empty() ? 0 : (size_t)W * H * 3);
+  std::vector<uint8_t> valid(validShare ? (size_t)W * H : 0);
+  const int rc = crt_render_accumulated(ctx, &temporal, denoise, merged.data(), pathToImage.empty() ? nullptr : q.data(), validShare ? valid.data() : nullptr);
+  if (rc != CRT_OK) throw std::runtime_error(std::string("renderAccumulated failed: ") + crt_last_error(ctx));
+  if (validShare) {  // over the hit pixels: the first hits of the camera's rays, which are the call's own guides
+    std::vector<crt_hit> hits((size_t)W * H);
+    crt_ray *rays = static_cast<crt_ray *>(crt_alloc_pinned((hits.size() ? hits.size() : 1) * sizeof(crt_ray)));
+    if (!rays) throw std::runtime_error("out of pinned host memory");
+    int qc = crt_camera_rays_device(ctx, rays, nullptr);  // (the context's camera is the frame's: no crt_set_camera, which would end the frame)
+    if (qc == CRT_OK) qc = crt_synchronize(ctx);
+    if (qc == CRT_OK) qc = crt_trace_rays(ctx, rays, hits.size(), CRT_RAY_PRIMARY, hits.data());
+    crt_free_pinned(rays);
+    if (qc != CRT_OK) throw std::runtime_error(std::string("renderAccumulated failed: ") + crt_last_error(ctx));
+    size_t hit = 0, kept = 0;
+    for (size_t i = 0; i < hits.size(); i++)
+      if (hits[i].hit) { hit++; kept += valid[i] != 0; }
+    *validShare = hit ? (double)kept / (double)hit : 0.0;
+  }
+  if (!pathToImage.empty()) writePPMQuantized(pathToImage, q.data(), W, H);
+  std::vector<std::vector<Color>> colorBuffer(H, std::vector<Color>(W));
+  for (unsigned int y = 0; y < H; y++)
+    for (unsigned int x = 0; x < W; x++) {
+      const float *p = &merged[((size_t)y * W + x) * 3];
+      colorBuffer[y][x] = Color(p[0], p[1], p[2]);
+    }
+  return colorBuffer;
+}
+
+void RayTracer::resetHistory() {
+  if (multi) throw std::runtime_error("resetHistory: not available on a multi-device tracer");
+  if (crt_history_reset(ctx) != CRT_OK) throw std::runtime_error("resetHistory failed");
+}
+
 void RayTracer::exportPPM(const std::string &pathToImage, const std::vector<std::vector<Color>> &colorBuffer) {
   const unsigned int W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
   std::vector<float> flatRGB((size_t)W * H * 3, 0.0f);

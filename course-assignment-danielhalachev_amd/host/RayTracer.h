@@ -136,6 +136,15 @@ class RayTracer {
   // Single-device tracers only.
   std::vector<std::vector<Color>> renderDenoised(const std::string &pathToImage, const crt_denoise &denoise);
 
+  // ---- temporal accumulation (crt_hip.h: crt_render_accumulated): the adaptive frame renderAdaptive left, merged with the history of the
+  // frames accumulated before it -- reprojected through the camera each of them had -- and then, with `denoise`, through the a-trous
+  // filter (nullptr: no spatial filter).  The frame itself is left as it was; the history survives setCamera().  Give consecutive frames
+  // different gi seeds.  validShare, if given, receives the share of the hit pixels with at least one valid history tap.  The PPM, if
+  // a path is given, is the result quantised by the PPMColor rule.  Single-device tracers only.
+  std::vector<std::vector<Color>> renderAccumulated(const std::string &pathToImage, const crt_temporal &temporal, const crt_denoise *denoise = nullptr,
+                                                    double *validShare = nullptr);
+  void resetHistory();
+
   // flat access for callers that do not want the vector-of-vectors copy
   int renderFlat(const std::string &pathToImage, const RenderOptions &renderOptions, float *outRGB, unsigned int counters = 0);
   crt_ctx *context() const { return multi ? crt_multi_context(multi, 0) : ctx; }

@@ -713,6 +713,126 @@ int crt_denoise_device(crt_ctx *ctx, const crt_denoise *denoise, uint32_t width,
                        const crt_hit *d_hits, float *d_out_rgb, float *d_out_var, void *d_work, void *stream);
 int crt_render_denoised(crt_ctx *ctx, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8);
 
+/* ---- Temporal accumulation: SVGF's temporal half for a camera that moves through a static scene.  A pixel's first hit is projected into
+ * the previous frame's camera, the previous frame's accumulated moments are fetched there with a bilinear tap whose four corners are
+ * tested against the pixel's own guide (mesh, normal, plane), and what survives is merged with this frame's moments by sample count.  It
+ * uses what the calls above compute: the adaptive fold's sum[3], sq and count, and the first hit of every pixel.  Kernel:
+ * csrc/kernel_temporal.h; the rule, one header for host and device: csrc/temporal_rule.h.  It is additive: no frame, query, radiance,
+ * progressive, adaptive or denoise kernel is involved.  Single-device contexts only.
+ *
+ * The rule.  Every line is one float32 operation with one rounding, in the order written; there is no exp, pow or sqrt, and floorf is exact.
+ * Records.  A history pixel is 64 bytes, aligned 16: {n[3], t, x[3], mesh, c[3], m2, weight, pad[3]}.  n[3], t, x[3], mesh is the guide of
+ *   the frame that wrote it (the denoiser's guide; mesh = 0xFFFFFFFF is a miss), c[3] the accumulated mean colour, m2 the
+ *   accumulated mean of r*r + g*g + b*b, weight the number of samples the record stands for, as a float; pad is written as 0.  A tap reads it
+ *   with four 16-byte loads from one 64-byte half line.  A pose is {position[3], matrix[9]}, what crt_set_camera takes: (o, m) below.
+ *   finite(x) is (x - x) == 0.0f.
+ * Pixel p = (y, x) of a width x height frame, with the guide G_p = {n_p, t_p, x_p, mesh_p} of the pixel's crt_hit, the fold's state sum[3],
+ *   sq, count, the previous pose (o, m) and the previous history array:
+ *   current:
+ *     n_c = (float)count
+ *     count == 0: C_c = 0, q_c = 0
+ *     else: inv = 1.0f / n_c; C_c = sum_c * inv; q_c = sq * inv
+ *   reproject:
+ *     no history array, or mesh_p is a miss: no history (n_h = 0, valid = 0)
+ *     w_j = x_p.j - o.j, j = 0..2
+ *     v_i = (w_0*m[3i] + w_1*m[3i+1]) + w_2*m[3i+2], i = 0..2
+ *     depth = 0.0f - v_2
+ *     skip unless depth > 0                          // a NaN skips
+ *     sx = v_0 / depth; sy = v_1 / depth
+ *     aspect = (float)width / (float)height
+ *     sx = sx / aspect
+ *     fx = ((sx + 1.0f) * 0.5f) * (float)width - 0.5f
+ *     fy = ((1.0f - sy) * 0.5f) * (float)height - 0.5f
+ *     skip unless fx > -1.0f && fx < (float)width && fy > -1.0f && fy < (float)height
+ *     x0 = floorf(fx); y0 = floorf(fy)
+ *     ax = fx - x0; ay = fy - y0
+ *     bx = 1.0f - ax; by = 1.0f - ay
+ *     tol = sigma_plane * t_p
+ *     acc = {0,0,0}; accq = 0; accn = 0; wsum = 0; valid = 0
+ *     taps q in the order (y0,x0) (y0,x0+1) (y0+1,x0) (y0+1,x0+1) with b = by*bx, by*ax, ay*bx, ay*ax:
+ *         skip q outside the frame                   // integer comparison, before any address is formed
+ *         skip unless weight_q > 0 and c_q[0..2], m2_q, weight_q are all finite
+ *         skip unless mesh_q == mesh_p
+ *         d = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z
+ *         skip unless d >= normal_min
+ *         e = (n_p.x*(x_q.x - x_p.x) + n_p.y*(x_q.y - x_p.y)) + n_p.z*(x_q.z - x_p.z)
+ *         skip unless fabsf(e) <= tol
+ *         wsum = wsum + b
+ *         acc_c = acc_c + b * c_q,c
+ *         accq = accq + b * m2_q
+ *         accn = accn + b * weight_q
+ *         valid = valid + 1
+ *     wsum > 0: inv = 1.0f / wsum; C_h,c = acc_c * inv; q_h = accq * inv; n_h = accn * inv
+ *     else: n_h = 0
+ *   merge:
+ *     n_h = n_h < max_history ? n_h : max_history
+ *     n_h == 0: C = C_c, q = q_c, n = n_c            // exactly: a pixel without history is the denoiser's own input
+ *     else: n = n_h + n_c; inv = 1.0f / n; a_h = n_h * inv; a_c = n_c * inv
+ *           C_c' = a_h * C_h,c + a_c * C_c,c
+ *           q = a_h * q_h + a_c * q_c
+ *     n == 0: C = 0, q = 0, V = 0
+ *     else: mm = (C_r*C_r + C_g*C_g) + C_b*C_b
+ *           var = q - mm
+ *           V = (var > 0 ? var : 0) * (1.0f / n)
+ *   write:
+ *     next[p] = {G_p, C, q, n}; out_rgb[p] = C; out_var[p] = V; out_valid[p] = valid (0..4)
+ *   The matrix product is the transpose of getRay's row-vector product: the reference's camera matrices are products of rotations, whose
+ *   inverse is the transpose.  A non-finite current sample gives a non-finite record; the next frame skips such a record as a tap, so a NaN
+ *   lives for one frame.
+ * Known limits.  A miss pixel keeps no history.  A matrix that is not a rotation reprojects wrongly.  The geometry tests reject most of
+ *   those taps, but not a slide within one plane.  Reflections are reprojected as if painted on the mirror.  The history holds the
+ *   unfiltered moments: the filtered colour is not fed back.
+ * crt_temporal: size must be sizeof(crt_temporal) = 16, max_history > 0 and finite, normal_min finite, sigma_plane >= 0 and finite:
+ *   anything else is CRT_ERR_INVALID, with nothing enqueued.  crt_temporal_defaults: 64.0f, 0.9f, 0.02f.
+ * crt_temporal_device: the rule for every pixel of a width x height image of the caller's: d_sum (3 floats a pixel), d_sq and d_counts --
+ *   the arrays crt_adaptive_step_device keeps --, d_hits (one crt_hit a pixel, row-major; e.g. what crt_trace_rays_device wrote for
+ *   crt_camera_rays_device's rays), the previous frame's records d_prev and its pose prev_pose (host memory, read before the call returns),
+ *   into d_next, d_out_rgb (3 floats a pixel), d_out_var (one float) and d_out_valid (one byte).  d_prev may be NULL, which means no
+ *   history; prev_pose is then ignored and may be NULL.  d_out_var and d_out_valid may be NULL.  d_next must not be d_prev; no output may
+ *   overlap an input or another output.  CRT_ERR_INVALID, with nothing enqueued: an invalid crt_temporal (above), width * height >= 2^31,
+ *   a NULL required array, d_prev without prev_pose, d_next == d_prev, d_next or d_prev not aligned to 16 bytes.  width * height of 0
+ *   with non-NULL arrays is CRT_OK and touches nothing.  It only ENQUEUES on `stream` (a hipStream_t, NULL = default): one launch, no wait,
+ *   no allocation, no readback.  It composes with crt_adaptive_step_device, crt_trace_rays_device and crt_denoise_device on one stream:
+ *   frame k's d_next is frame k+1's d_prev.
+ * crt_render_accumulated acts on the ADAPTIVE frame under way or finished and refuses exactly what crt_render_denoised refuses, beside an
+ *   invalid crt_temporal and, where `denoise` is not NULL, an invalid crt_denoise.  The guides are crt_render_denoised's guides: traced once
+ *   a frame and shared between the two calls.  The context owns two history slots, allocated on first use and freed by crt_destroy:
+ *   `previous`, the last FRAME's records and that frame's pose, and `current`, what calls on this frame write.  A frame is identified by
+ *   a serial number that advances wherever the guides are dropped: crt_set_camera, crt_render*, a new first pass.  When a call finds that
+ *   the serial has changed since `current` was written, `current` becomes `previous` first.  So every call on one frame merges the SAME
+ *   previous history with the frame's state as it stands: two calls on an unchanged frame give the same bits, and a call after pass 3 and
+ *   another after pass 8 do not count the frame twice.  After the merge, denoise != NULL runs crt_denoise_device's launches on the merged
+ *   colour and variance (NULL: no spatial filter).  The result goes to out_rgb (height * width * 3 floats), out_rgb8 (crt_quantize_device's
+ *   rule) and out_valid (the valid taps per pixel, height * width bytes); host memory, any of the three may be NULL; the call returns when
+ *   they are there.  It leaves alone everything crt_render_denoised leaves alone, so a frame can be accumulated after any pass and
+ *   continued, and crt_render_denoised's own result is unchanged by it.  The history survives crt_set_camera, which is its purpose;
+ *   crt_history_reset drops it (the next frame is a first frame again), and crt_history_frames counts the frames merged since the last
+ *   reset.  Giving consecutive frames different gi_seed values is the CALLER'S job: the same seed and camera give the same samples again,
+ *   and merging a frame with its own copy adds nothing. */
+typedef struct crt_temporal {
+    uint32_t size;       /* sizeof(crt_temporal) = 16 */
+    float max_history;   /* > 0, finite: a record stands for at most this many samples when it is merged */
+    float normal_min;    /* finite: a tap's normal must have at least this cosine with the pixel's */
+    float sigma_plane;   /* >= 0, finite: a tap may lie sigma_plane x t off the pixel's tangent plane */
+} crt_temporal;
+typedef struct crt_history_pixel {
+    float n[3], t, x[3];
+    uint32_t mesh;
+    float c[3], m2, weight, pad[3];
+} crt_history_pixel;     /* 64 bytes; arrays of it must be aligned to 16 bytes */
+typedef struct crt_camera_pose {
+    float position[3];
+    float matrix[9];
+} crt_camera_pose;
+void crt_temporal_defaults(crt_temporal *t);   /* 64.0f, 0.9f, 0.02f */
+int crt_temporal_device(crt_ctx *ctx, const crt_temporal *temporal, uint32_t width, uint32_t height, const crt_camera_pose *prev_pose,
+                        const crt_history_pixel *d_prev, const float *d_sum, const float *d_sq, const uint32_t *d_counts, const crt_hit *d_hits,
+                        crt_history_pixel *d_next, float *d_out_rgb, float *d_out_var, uint8_t *d_out_valid, void *stream);
+int crt_render_accumulated(crt_ctx *ctx, const crt_temporal *temporal, const crt_denoise *denoise /* NULL: no spatial filter */, float *out_rgb,
+                           uint8_t *out_rgb8, uint8_t *out_valid);
+int crt_history_reset(crt_ctx *ctx);
+uint32_t crt_history_frames(const crt_ctx *ctx);
+
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
  * stream per listed device (a device may be listed more than once); the covered 8x8 tiles are dealt round-robin, every
