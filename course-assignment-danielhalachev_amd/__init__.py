@@ -252,6 +252,8 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_st
                   "crt_adaptive_defaults", "crt_adaptive_work_bytes", "crt_adaptive_step_device", "crt_render_adaptive", "crt_progressive_active",
                   "crt_denoise_defaults", "crt_denoise_work_bytes", "crt_sample_variance_device", "crt_denoise_device", "crt_render_denoised",
                   "crt_temporal_defaults", "crt_temporal_device", "crt_render_accumulated", "crt_history_reset", "crt_history_frames",
+                  "crt_shoot_rays_gi_split", "crt_shoot_rays_gi_split_device", "crt_split_fold_device", "crt_split_recombine_device",
+                  "crt_render_adaptive_split", "crt_read_split_state", "crt_render_denoised_split", "crt_render_accumulated_split", "crt_history_frames_split",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -344,6 +346,16 @@ def lib():
     L.crt_history_reset.argtypes = [vp]
     L.crt_history_frames.argtypes = [vp]
     L.crt_history_frames.restype = u32
+    L.crt_shoot_rays_gi_split.argtypes = [vp, vp, vp, C.c_uint64, u32, C.POINTER(Options), vp, vp]
+    L.crt_shoot_rays_gi_split_device.argtypes = [vp, vp, vp, C.c_uint64, u32, C.POINTER(Options), vp, vp, vp]
+    L.crt_split_fold_device.argtypes = [vp, vp, vp, vp, C.c_uint64, u32, vp, vp, vp, vp]
+    L.crt_split_recombine_device.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp]
+    L.crt_render_adaptive_split.argtypes = [vp, C.POINTER(Options), C.POINTER(Adaptive), u32, u32, vp, vp]
+    L.crt_render_denoised_split.argtypes = [vp, C.POINTER(Denoise), vp, vp]
+    L.crt_read_split_state.argtypes = [vp, vp, vp, vp]
+    L.crt_render_accumulated_split.argtypes = [vp, C.POINTER(Temporal), C.POINTER(Denoise), vp, vp, vp]
+    L.crt_history_frames_split.argtypes = [vp]
+    L.crt_history_frames_split.restype = u32
     L.crt_host_shoot_stats_layout.argtypes = [C.POINTER(u32), u32]
     L.crt_host_shoot_stats_layout.restype = u32
     L.crt_get_kernel_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -791,8 +803,11 @@ class Tracer:
     def shoot_rays_gi(self, rays, keys=None, ray_type=RAY_REFLECTION, options=None, **option_fields):
         """The colour shootRay of the GI build returns for each ray: rays float32 [n, 6], keys uint32 [n] (the key of each ray's shootRay
         invocation, csrc/gi_random.h) or None for the keys of a frame's pixels 0 .. n - 1, sample 0, under options.gi_seed -> float32
-        [n, 3].  options: an Options with use_gi set, or make_options' fields by name (max_depth, gi_sample_size, gi_seed, ...)."""
+        [n, 3].  options: an Options with use_gi set, or make_options' fields by name (max_depth, gi_sample_size, gi_seed, ...).
+        split=True (by name, beside the option fields; the default is False): -> (rgb, direct), the same colours and each one's direct
+        part float32 [n, 3] (include/crt_hip.h: "Split GI frames")."""
         self._single("shoot_rays_gi")
+        split = bool(option_fields.pop("split", False))
         rays = self._rays_array(rays)
         if keys is not None:
             keys = np.ascontiguousarray(keys, dtype=np.uint32)
@@ -800,14 +815,25 @@ class Tracer:
                 raise ValueError("keys: expected shape [%d], got %r" % (len(rays), keys.shape))
         rgb = np.zeros((len(rays), 3), dtype=np.float32)
         o = self._gi_options(options, option_fields)
+        if split:
+            direct = np.zeros((len(rays), 3), dtype=np.float32)
+            self._check(lib().crt_shoot_rays_gi_split(self.ctx, _p(rays), _p(keys) if keys is not None else None, len(rays), ray_type, C.byref(o),
+                                                      _p(rgb), _p(direct)))
+            return rgb, direct
         self._check(lib().crt_shoot_rays_gi(self.ctx, _p(rays), _p(keys) if keys is not None else None, len(rays), ray_type, C.byref(o), _p(rgb)))
         return rgb
 
-    def shoot_rays_gi_device(self, d_rays_ptr, n, d_rgb_ptr, d_keys_ptr=None, ray_type=RAY_REFLECTION, options=None, stream_ptr=None, **option_fields):
+    def shoot_rays_gi_device(self, d_rays_ptr, n, d_rgb_ptr, d_keys_ptr=None, ray_type=RAY_REFLECTION, options=None, stream_ptr=None,
+                             d_direct_ptr=None, **option_fields):
         """The same on device memory (data_ptr() of: rays float32 [n, 6], rgb float32 [n, 3], keys uint32 [n] or None) on the stream; the
-        call waits for the stream once per recursion level, so it cannot be captured into a graph."""
+        call waits for the stream once per recursion level, so it cannot be captured into a graph.  d_direct_ptr (float32 [n, 3]): the
+        split call, which also writes each colour's direct part."""
         self._single("shoot_rays_gi_device")
         o = self._gi_options(options, option_fields)
+        if d_direct_ptr is not None:
+            self._check(lib().crt_shoot_rays_gi_split_device(self.ctx, C.c_void_p(d_rays_ptr), C.c_void_p(d_keys_ptr or 0), n, ray_type, C.byref(o),
+                                                             C.c_void_p(d_rgb_ptr), C.c_void_p(d_direct_ptr), C.c_void_p(stream_ptr or 0)))
+            return
         self._check(lib().crt_shoot_rays_gi_device(self.ctx, C.c_void_p(d_rays_ptr), C.c_void_p(d_keys_ptr or 0), n, ray_type, C.byref(o),
                                                    C.c_void_p(d_rgb_ptr), C.c_void_p(stream_ptr or 0)))
 
@@ -921,12 +947,14 @@ class Tracer:
         self._single("progressive_active")
         return int(lib().crt_progressive_active(self.ctx))
 
-    def render_adaptive(self, options, adaptive, per_call=1, on_pass=None):
+    def render_adaptive(self, options, adaptive, per_call=1, on_pass=None, split=False):
         """The GI frame of `options` (use_gi set; rays_per_pixel is not read) sampled adaptively: every pixel is shot until the rule of
         `adaptive` (make_adaptive) stops it, at most adaptive.max_samples times, per_call passes a call.  on_pass(passes_done, mean, counts)
         is called after every call and may return False to stop.  Returns (rgb float32 [H, W, 3], counts uint32 [H, W]): a pixel with
-        count k holds the one-shot frame of rays_per_pixel = k."""
+        count k holds the one-shot frame of rays_per_pixel = k.  split: the same frame, bit for bit, that also keeps every sample's
+        direct part, for render_denoised(split=True) and render_accumulated(split=True)."""
         self._single("render_adaptive")
+        call = lib().crt_render_adaptive_split if split else lib().crt_render_adaptive
         if per_call < 1:
             raise ValueError("per_call: at least one pass a call")
         rgb = np.zeros((self.height, self.width, 3), dtype=np.float32)
@@ -934,7 +962,7 @@ class Tracer:
         done = 0
         while done == 0 or (done < adaptive.max_samples and self.progressive_active()):
             k = min(int(per_call), adaptive.max_samples - done)
-            self._check(lib().crt_render_adaptive(self.ctx, C.byref(options), C.byref(adaptive), done, k, _p(rgb), _p(counts)))
+            self._check(call(self.ctx, C.byref(options), C.byref(adaptive), done, k, _p(rgb), _p(counts)))
             done += k
             if on_pass is not None and on_pass(done, rgb.copy(), counts.copy()) is False:
                 break
@@ -963,15 +991,17 @@ class Tracer:
                                              C.c_void_p(d_hits_ptr), C.c_void_p(d_out_rgb_ptr), C.c_void_p(d_out_var_ptr or 0),
                                              C.c_void_p(d_work_ptr), C.c_void_p(stream_ptr or 0)))
 
-    def render_denoised(self, denoise=None, rgb8=False):
+    def render_denoised(self, denoise=None, rgb8=False, split=False):
         """The context's adaptive frame, under way or finished (render_adaptive), denoised with `denoise` (make_denoise; None: the
         defaults) -> rgb float32 [H, W, 3]; with rgb8 also the PPMColor quantisation, (rgb, uint8 [H, W, 3]).  The frame itself is left
-        exactly as it was and can be continued."""
+        exactly as it was and can be continued.  split (a frame of render_adaptive(split=True)): only the indirect light is filtered, and
+        the direct light, which carries the texels, is added back untouched."""
         self._single("render_denoised")
         d = denoise if denoise is not None else make_denoise()
         rgb = np.zeros((self.height, self.width, 3), dtype=np.float32)
         q8 = np.zeros((self.height, self.width, 3), dtype=np.uint8) if rgb8 else None
-        self._check(lib().crt_render_denoised(self.ctx, C.byref(d), _p(rgb), _p(q8) if rgb8 else None))
+        call = lib().crt_render_denoised_split if split else lib().crt_render_denoised
+        self._check(call(self.ctx, C.byref(d), _p(rgb), _p(q8) if rgb8 else None))
         return (rgb, q8) if rgb8 else rgb
 
     # ---- temporal accumulation (include/crt_hip.h: crt_temporal_device, crt_render_accumulated, crt_history_reset, crt_history_frames)
@@ -987,19 +1017,21 @@ class Tracer:
                                               C.c_void_p(d_hits_ptr), C.c_void_p(d_next_ptr), C.c_void_p(d_out_rgb_ptr), C.c_void_p(d_out_var_ptr or 0),
                                               C.c_void_p(d_out_valid_ptr or 0), C.c_void_p(stream_ptr or 0)))
 
-    def render_accumulated(self, temporal=None, denoise=None, rgb8=False, valid=False):
+    def render_accumulated(self, temporal=None, denoise=None, rgb8=False, valid=False, split=False):
         """The context's adaptive frame, under way or finished (render_adaptive), merged with the last frame's history with `temporal`
         (make_temporal; None: the defaults) and then filtered with `denoise` (make_denoise; None: no spatial filter) -> rgb float32
         [H, W, 3]; with rgb8 also the PPMColor quantisation uint8 [H, W, 3], with valid also the valid taps per pixel uint8 [H, W], as a
         tuple in that order.  The frame itself is left exactly as it was and can be continued; the history survives set_camera.  Give
-        consecutive frames different gi_seed values."""
+        consecutive frames different gi_seed values.  split (a frame of render_adaptive(split=True)): only the indirect light is merged and
+        filtered, in a history of its own (history_frames(split=True))."""
         self._single("render_accumulated")
+        call = lib().crt_render_accumulated_split if split else lib().crt_render_accumulated
         t = temporal if temporal is not None else make_temporal()
         rgb = np.zeros((self.height, self.width, 3), dtype=np.float32)
         q8 = np.zeros((self.height, self.width, 3), dtype=np.uint8) if rgb8 else None
         taps = np.zeros((self.height, self.width), dtype=np.uint8) if valid else None
-        self._check(lib().crt_render_accumulated(self.ctx, C.byref(t), C.byref(denoise) if denoise is not None else None, _p(rgb),
-                                                 _p(q8) if rgb8 else None, _p(taps) if valid else None))
+        self._check(call(self.ctx, C.byref(t), C.byref(denoise) if denoise is not None else None, _p(rgb), _p(q8) if rgb8 else None,
+                         _p(taps) if valid else None))
         out = (rgb,) + ((q8,) if rgb8 else ()) + ((taps,) if valid else ())
         return out if len(out) > 1 else rgb
 
@@ -1008,10 +1040,36 @@ class Tracer:
         self._single("history_reset")
         self._check(lib().crt_history_reset(self.ctx))
 
-    def history_frames(self) -> int:
-        """The frames merged into the history since the last history_reset."""
+    def history_frames(self, split=False) -> int:
+        """The frames merged into the history (split: into the split calls' history) since the last history_reset."""
         self._single("history_frames")
-        return int(lib().crt_history_frames(self.ctx))
+        return int((lib().crt_history_frames_split if split else lib().crt_history_frames)(self.ctx))
+
+    # ---- split GI frames (include/crt_hip.h: crt_split_fold_device, crt_split_recombine_device)
+    def split_fold_device(self, d_rgb_ptr, d_direct_ptr, sample, d_dsum_ptr, d_rsum_ptr, d_rsq_ptr, n=None, d_pixels_ptr=None, stream_ptr=None):
+        """One step of the split's fold for the listed pixels (distinct!) or all of them: rgb and direct float32 [n, 3] (shoot_rays_gi_device
+        with d_direct_ptr) into dsum and rsum float32 [H * W * 3] and rsq float32 [H * W], device arrays of the caller's.  Enqueues and
+        returns."""
+        self._single("split_fold_device")
+        n = self.width * self.height if n is None else n
+        self._check(lib().crt_split_fold_device(self.ctx, C.c_void_p(d_rgb_ptr), C.c_void_p(d_direct_ptr), C.c_void_p(d_pixels_ptr or 0), n, int(sample),
+                                                C.c_void_p(d_dsum_ptr), C.c_void_p(d_rsum_ptr), C.c_void_p(d_rsq_ptr), C.c_void_p(stream_ptr or 0)))
+
+    def read_split_state(self):
+        """The split frame under way or finished: (dsum float32 [H, W, 3], rsum float32 [H, W, 3], rsq float32 [H, W]) -- the sums of the
+        samples' direct parts and the first and second moment of the rest; dsum / counts is the frame's direct-light layer."""
+        self._single("read_split_state")
+        dsum, rsum = (np.zeros((self.height, self.width, 3), dtype=np.float32) for _ in range(2))
+        rsq = np.zeros((self.height, self.width), dtype=np.float32)
+        self._check(lib().crt_read_split_state(self.ctx, _p(dsum), _p(rsum), _p(rsq)))
+        return dsum, rsum, rsq
+
+    def split_recombine_device(self, d_filtered_ptr, d_dsum_ptr, d_counts_ptr, n_pixels, d_out_ptr, stream_ptr=None):
+        """out = filtered + dsum / count (count 0: filtered) for n_pixels pixels: filtered, dsum and out float32 [n * 3], counts uint32 [n],
+        device arrays of the caller's; out may be filtered.  Enqueues and returns."""
+        self._single("split_recombine_device")
+        self._check(lib().crt_split_recombine_device(self.ctx, C.c_void_p(d_filtered_ptr), C.c_void_p(d_dsum_ptr), C.c_void_p(d_counts_ptr),
+                                                     int(n_pixels), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
 
     def shoot_stats(self) -> ShootStats:
         """rays / levels / level_rays / shadow_records / rerouted / kernel_ms of the last radiance query (waits for it)."""

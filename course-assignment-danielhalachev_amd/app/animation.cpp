@@ -7,7 +7,7 @@
 // time than the frame takes to render -- are formatted by a few writer threads while the next frames render.
 // --gi SAMPLE_SIZE --adaptive T MIN MAX renders the same orbit as GI frames, one at a time on the one context, each with renderAdaptive to
 // completion and the seed base + frame index; --denoise [K] writes each frame through the a-trous filter, and --temporal [MAX_HISTORY]
-// merges each frame with the history of the frames before it first (renderAccumulated).
+// merges each frame with the history of the frames before it first (renderAccumulated); --split makes both act on the indirect light only.
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -71,9 +71,10 @@ int main(int argc, char **argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s scene.crtscene out_prefix [--folder DIR] [--depth N] [--fps F] [--seconds S] [--radius R] [--device D] "
                          "[--in-flight K] [--writers N] [--no-ppm]\n"
-                         "       [--gi SAMPLE_SIZE --adaptive THRESHOLD MIN MAX [--seed S] [--denoise [ITERATIONS]] [--temporal [MAX_HISTORY]]]   (GI frames, one at a\n"
+                         "       [--gi SAMPLE_SIZE --adaptive THRESHOLD MIN MAX [--seed S] [--denoise [ITERATIONS]] [--temporal [MAX_HISTORY]] [--split]]   (GI frames, one at a\n"
                          "        time: every pixel is shot MIN .. MAX times; --denoise: through crt_hip.h's crt_denoise; --temporal: merged with the\n"
-                         "        history of the frames before it, crt_hip.h's crt_temporal, then through the filter if --denoise is given)\n", argv[0]);
+                         "        history of the frames before it, crt_hip.h's crt_temporal, then through the filter if --denoise is given;\n"
+                         "        --split: both act on the indirect light only, crt_hip.h's \"Split GI frames\")\n", argv[0]);
     return 2;
   }
   std::string scenePath = argv[1], prefix = argv[2], folder;
@@ -83,7 +84,7 @@ int main(int argc, char **argv) {
   int device = 0;
   unsigned inFlight = 2, nWriters = 4;
   bool writeFiles = true;
-  bool useGI = false, adaptive = false, denoise = false, temporal = false;
+  bool useGI = false, adaptive = false, denoise = false, temporal = false, split = false;
   unsigned giSamples = 2, adaptiveMin = 0, adaptiveMax = 0, seed = 0;
   float adaptiveThreshold = 0.0f, maxHistory = -1.0f;  // (-1: crt_temporal_defaults')
   int denoiseIterations = -1;                          // (-1: crt_denoise_defaults')
@@ -104,11 +105,12 @@ int main(int argc, char **argv) {
       adaptive = true; adaptiveThreshold = (float)atof(argv[++i]); adaptiveMin = (unsigned)atoi(argv[++i]); adaptiveMax = (unsigned)atoi(argv[++i]);
     }
     else if (!strcmp(argv[i], "--denoise")) { denoise = true; if (number(i + 1)) denoiseIterations = atoi(argv[++i]); }
+    else if (!strcmp(argv[i], "--split")) split = true;
     else if (!strcmp(argv[i], "--temporal")) { temporal = true; if (number(i + 1)) maxHistory = (float)atof(argv[++i]); }
   }
-  if (useGI != adaptive || ((denoise || temporal) && !useGI)) {
-    std::fprintf(stderr, "error: --gi needs --adaptive and --adaptive needs --gi; --denoise and --temporal need both\n"
-                         "usage: %s scene.crtscene out_prefix --gi SAMPLE_SIZE --adaptive THRESHOLD MIN MAX [--denoise [ITERATIONS]] [--temporal [MAX_HISTORY]]\n", argv[0]);
+  if (useGI != adaptive || ((denoise || temporal || split) && !useGI)) {
+    std::fprintf(stderr, "error: --gi needs --adaptive and --adaptive needs --gi; --denoise, --temporal and --split need both\n"
+                         "usage: %s scene.crtscene out_prefix --gi SAMPLE_SIZE --adaptive THRESHOLD MIN MAX [--denoise [ITERATIONS]] [--temporal [MAX_HISTORY]] [--split]\n", argv[0]);
     return 2;
   }
   try {
@@ -150,16 +152,16 @@ int main(int argc, char **argv) {
         crt_denoise d;
         crt_denoise_defaults(&d);
         if (denoiseIterations >= 0) d.iterations = (uint32_t)denoiseIterations;
-        tracer.renderAdaptive(denoise || temporal ? std::string() : path, options, a);
+        tracer.renderAdaptive(denoise || temporal ? std::string() : path, options, a, 1, nullptr, split);
         if (temporal) {
           crt_temporal h;
           crt_temporal_defaults(&h);
           if (maxHistory >= 0.0f) h.max_history = maxHistory;
           double share = 0.0;
-          tracer.renderAccumulated(path, h, denoise ? &d : nullptr, &share);
+          tracer.renderAccumulated(path, h, denoise ? &d : nullptr, &share, split);
           shareSum += share;
         }
-        else if (denoise) tracer.renderDenoised(path, d);
+        else if (denoise) tracer.renderDenoised(path, d, split);
         frames++;
         degrees += DEG_CHANGE;
         continue;

@@ -22,8 +22,9 @@ int main(int argc, char **argv) {
                  "        --progressive: the same frame K samples a call, in memory that does not depend on RAYS_PER_PIXEL)\n"
                  "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL --adaptive THRESHOLD MIN MAX [--counts FILE]]   (every pixel is shot until the rule of\n"
                  "        crt_hip.h's crt_adaptive stops it, MIN .. MAX times; RAYS_PER_PIXEL is not read; --counts: the samples per pixel as a P2 PGM)\n"
-                 "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL --adaptive THRESHOLD MIN MAX --denoise [ITERATIONS]]   (out.ppm is that frame through the\n"
-                 "        variance-guided a-trous filter of crt_hip.h's crt_denoise, its defaults but for ITERATIONS, 0..8)\n"
+                 "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL --adaptive THRESHOLD MIN MAX --denoise [ITERATIONS] [--split]]   (out.ppm is that frame through\n"
+                 "        the variance-guided a-trous filter of crt_hip.h's crt_denoise, its defaults but for ITERATIONS, 0..8; --split: the filter acts\n"
+                 "        on the indirect light only and the direct light is added back, crt_hip.h's \"Split GI frames\"; it needs --adaptive)\n"
                  "       [--probe ROW COL]   (no render: the closest hit of that pixel's camera ray; out.ppm is not written)\n",
                  argv[0]);
     return 2;
@@ -40,6 +41,7 @@ int main(int argc, char **argv) {
   std::string countsPath;
   bool denoise = false;
   int denoiseIterations = -1;  // (-1: crt_denoise_defaults')
+  bool split = false;
   bool probe = false;
   unsigned probeRow = 0, probeCol = 0;
   for (int i = 3; i < argc; i++) {
@@ -71,6 +73,7 @@ int main(int argc, char **argv) {
       denoise = true;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoiseIterations = atoi(argv[++i]);
     }
+    else if (!strcmp(argv[i], "--split")) split = true;
     else if (!strcmp(argv[i], "--probe") && i + 2 < argc) { probe = true; probeRow = (unsigned)atoi(argv[++i]); probeCol = (unsigned)atoi(argv[++i]); }
   }
   if (progressive && (!useGI || devices.size() > 0)) {
@@ -87,6 +90,11 @@ int main(int argc, char **argv) {
   }
   if (denoise && !adaptive) {
     std::fprintf(stderr, "error: --denoise needs --adaptive\nusage: %s scene.crtscene out.ppm --gi GI_SAMPLE_SIZE RAYS_PER_PIXEL --adaptive THRESHOLD MIN MAX --denoise [ITERATIONS]\n",
+                 argv[0]);
+    return 2;
+  }
+  if (split && !adaptive) {
+    std::fprintf(stderr, "error: --split needs --adaptive\nusage: %s scene.crtscene out.ppm --gi GI_SAMPLE_SIZE RAYS_PER_PIXEL --adaptive THRESHOLD MIN MAX --denoise [ITERATIONS] --split\n",
                  argv[0]);
     return 2;
   }
@@ -119,12 +127,12 @@ int main(int argc, char **argv) {
         crt_adaptive_defaults(&a);
         a.threshold = adaptiveThreshold; a.min_samples = adaptiveMin; a.max_samples = adaptiveMax;
         std::vector<uint32_t> counts;
-        tracer.renderAdaptive(r + 1 == repeat && !denoise ? outPath : std::string(), options, a, 1, &counts);
+        tracer.renderAdaptive(r + 1 == repeat && !denoise ? outPath : std::string(), options, a, 1, &counts, split);
         if (denoise) {  // the PPM is the denoised frame; the frame itself stays what it was
           crt_denoise d;
           crt_denoise_defaults(&d);
           if (denoiseIterations >= 0) d.iterations = (uint32_t)denoiseIterations;
-          tracer.renderDenoised(r + 1 == repeat ? outPath : std::string(), d);
+          tracer.renderDenoised(r + 1 == repeat ? outPath : std::string(), d, split);
         }
         if (r + 1 == repeat && !countsPath.empty()) {
           const unsigned W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;

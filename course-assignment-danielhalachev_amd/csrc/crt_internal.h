@@ -8,6 +8,7 @@
 //                     direct lighting of hit records and points, radiance queries; their scratch and statistics
 //   crt_denoise.hip   the denoiser's primitives: the variance of the fold's state, the a-trous filter on first-hit guides
 //   crt_temporal.hip  the temporal accumulation's primitive: the last frame's history reprojected and merged with the fold's state
+//   crt_split.hip     the split GI frames' primitives: a sample's direct light kept, the fold of the two parts, putting them back together
 //   crt_testhooks.hip unit-test hooks (libcrt_hip_test.so only)
 #pragma once
 
@@ -167,6 +168,7 @@ CRT_INTERNAL int fetch_counters(crt_ctx *ctx, const crt_options *o, uint64_t pix
 // ---- crt_query.hip
 CRT_INTERNAL void query_destroy(crt_ctx *ctx);
 CRT_INTERNAL void query_progressive_reset(crt_ctx *ctx);   // crt_set_camera, crt_render*: crt_progressive_samples is 0 again
+CRT_INTERNAL int progressive_check(crt_ctx *ctx, const char *what, const uint32_t *d_pixels, uint64_t n);   // what the fold's primitives ask of (d_pixels, n)
 // ---- crt_denoise.hip: the denoiser's settings check and launches, for crt_render_denoised (crt_query.hip)
 CRT_INTERNAL int denoise_check(crt_ctx *ctx, const char *what, const crt_denoise *d);
 CRT_INTERNAL int denoise_launch_variance(crt_ctx *ctx, const float *d_sum, const float *d_sq, const uint32_t *d_counts, uint64_t n, float *d_mean,
@@ -178,6 +180,13 @@ CRT_INTERNAL int temporal_check(crt_ctx *ctx, const char *what, const crt_tempor
 CRT_INTERNAL int temporal_launch(crt_ctx *ctx, const crt_temporal *t, uint32_t width, uint32_t height, const crt_camera_pose *prev_pose,
                                  const crt_history_pixel *d_prev, const float *d_sum, const float *d_sq, const uint32_t *d_counts, const crt_hit *d_hits,
                                  crt_history_pixel *d_next, float *d_out_rgb, float *d_out_var, uint8_t *d_out_valid, hipStream_t stream);
+// ---- crt_split.hip: the split GI frames' launches, for the radiance passes and the *_split frame calls (crt_query.hip)
+CRT_INTERNAL int split_launch_keep_direct(crt_ctx *ctx, const uint8_t *d_status, const float *d_rgb, uint32_t n, uint32_t gi_sample_size, float *d_direct,
+                                          hipStream_t stream);
+CRT_INTERNAL int split_launch_fold(crt_ctx *ctx, const float *d_rgb, const float *d_direct, const uint32_t *d_pixels, uint64_t n, uint32_t sample,
+                                   float *d_dsum, float *d_rsum, float *d_rsq, hipStream_t stream);
+CRT_INTERNAL int split_launch_recombine(crt_ctx *ctx, const float *d_filtered, const float *d_dsum, const uint32_t *d_counts, uint64_t n_pixels,
+                                        float *d_out, hipStream_t stream);
 // ---- crt_abi.hip
 CRT_INTERNAL uint64_t coverage_items(uint32_t width, uint32_t height, const crt_rect *rects, uint32_t n_rects, std::vector<WorkItem> &items);
 CRT_INTERNAL void launch_unpack_items(const float *packed, const WorkItem *items, uint32_t n_items, float *frame, uint32_t width, uint32_t height,

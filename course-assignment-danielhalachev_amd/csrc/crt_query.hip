@@ -25,6 +25,9 @@
 //                     the first hits of the camera's rays; it changes nothing of the frame
 //   an accumulated frame  crt_render_accumulated: that state merged with the last frame's history through the temporal primitive
 //                     (crt_temporal.hip), then through the denoiser's launches; the context's two history slots
+//   a split frame     crt_render_adaptive_split, crt_render_denoised_split, crt_render_accumulated_split: the three calls above with every
+//                     sample cut into its direct light and the rest (crt_split.hip, csrc/split_rule.h) -- the rest is what is filtered and
+//                     reprojected, the direct part is added back untouched; one body each for the split and the unsplit call
 #include "crt_internal.h"
 #include "glibc_powf.h"
 #include "gi_random.h"
@@ -208,6 +211,7 @@ struct crt_query_state {
     ShootLevel lv[MAX_GENERATIONS];
     DeviceArray<crt_ray> shoot_in;    // the host variant's device copy of the caller's rays
     DeviceArray<uint32_t> shoot_keys; // ... and of the caller's keys (crt_shoot_rays_gi)
+    DeviceArray<float> shoot_direct;  // ... and the device copy of the direct parts it gets back (crt_shoot_rays_gi_split)
     DeviceArray<uint32_t> swords;     // SW_*
     crt_shoot_stats shoot{};          // of the last radiance call
     // crt_shoot_rays*_enqueue
@@ -226,6 +230,10 @@ struct crt_query_state {
     DeviceArray<uint32_t> prog_counts, prog_list[2], prog_next_n;
     DeviceArray<unsigned long long> prog_work;
     bool prog_is_adaptive = false;
+    // crt_render_adaptive_split: the adaptive frame is a SPLIT one (latched at pass 0) -- beside the fold's state the sums of the samples'
+    // direct parts and the first and second moment of the rest (csrc/split_rule.h), and one pass's direct parts beside prog_rgb
+    bool prog_is_split = false;
+    DeviceArray<float> split_direct, split_dsum, split_rsum, split_rsq;
     crt_adaptive prog_adaptive{};
     uint64_t prog_active = 0;   // entries of prog_list[prog_cur]; pass 0 has no list (every pixel)
     int prog_cur = 0;
@@ -236,15 +244,20 @@ struct crt_query_state {
     DeviceArray<float4> den_work;
     DeviceArray<uint8_t> den_q8;
     bool den_guides = false;
-    // crt_render_accumulated: the frame's serial number (it advances wherever den_guides is dropped), the two history slots with the pose
-    // of the frame that wrote each -- hist[hist_cur] is `current`, the other one `previous` --, the serial `current` was written at, the
-    // frames merged since crt_history_reset, and the merged colour, variance and valid-tap counts
-    uint64_t frame_serial = 0, hist_serial = 0;
-    DeviceArray<crt_history_pixel> hist[2];
-    crt_camera_pose hist_pose[2] = {};
-    int hist_cur = 0;
-    bool hist_has_cur = false, hist_has_prev = false;
-    uint32_t hist_frames = 0;
+    // crt_render_accumulated*: the frame's serial number (it advances wherever den_guides is dropped); a History -- two slots with the pose
+    // of the frame that wrote each: slot[cur] is `current`, slot[cur ^ 1] `previous`; the serial `current` was written at; the frames
+    // merged since crt_history_reset --; and the merged colour, variance and valid-tap counts.  There are two histories: hist[0] holds the
+    // moments of whole colours (crt_render_accumulated), hist[1] those of the rest (crt_render_accumulated_split), which must never meet
+    uint64_t frame_serial = 0;
+    struct History {
+        uint64_t serial = 0;
+        DeviceArray<crt_history_pixel> slot[2];
+        crt_camera_pose pose[2] = {};
+        int cur = 0;
+        bool has_cur = false, has_prev = false;
+        uint32_t frames = 0;
+        void reset() { has_cur = has_prev = false; frames = 0; }   // (the slots stay allocated: nothing reads them until a call has written one again)
+    } hist[2];
     DeviceArray<float> acc_rgb, acc_var;
     DeviceArray<uint8_t> acc_valid;
     void new_frame() { den_guides = false; frame_serial++; }   // the guides and `current` are the ended frame's
@@ -653,6 +666,7 @@ extern "C" int crt_get_shoot_report(crt_ctx *ctx, crt_shoot_report *out) { retur
 struct ShootGi {
     const uint32_t *d_keys;   // the pass's keys on the device, or null: those of a frame's pixels key_first ..., sample 0
     uint32_t key_first;       // the index in the call of the pass's first ray
+    float *d_direct;          // crt_shoot_rays_gi_split*: the pass's slice of the direct parts, or null: nothing more is launched
 };
 
 // room for `cap` rays at level g (`own_rgb`: with colours of its own; level 0 writes the caller's array; `keys`: a GI call)
@@ -789,6 +803,9 @@ static int shoot_down(crt_ctx *ctx, ShootPass &P) {
         trace.kernels_only = light.kernels_only = P.kernels_only;
         int rc = query_launches(ctx, trace, P.stream, g == 0);
         if (rc || (g == 0 && (rc = shoot_numbers(ctx, P, true))) || (rc = query_launches(ctx, light, P.stream, false))) return rc;
+        // a split call: level 0's colours are its records' direct light now, and the up-sweep overwrites them (csrc/split_rule.h)
+        if (g == 0 && gi && P.gi->d_direct && (rc = split_launch_keep_direct(ctx, L.status.p, rgb, S.n, o->gi_sample_size, P.gi->d_direct, P.stream)))
+            return rc;
         G.child_count = d_count + g + 1;
         G.spawn = g + 1 <= o->max_depth ? 1u : 0u;   // a child enters shootRay with depth g + 1 (RayTracer.cpp:427)
         if ((rc = shoot_children(ctx, P, g, G))) return rc;
@@ -845,7 +862,11 @@ static int shoot_run(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t r
         }
         const uint32_t m = (uint32_t)std::min(n - done, pass);
         ShootGi part{};
-        if (gi) { part.d_keys = gi->d_keys ? gi->d_keys + done : nullptr; part.key_first = gi->key_first + (uint32_t)done; }
+        if (gi) {
+            part.d_keys = gi->d_keys ? gi->d_keys + done : nullptr;
+            part.key_first = gi->key_first + (uint32_t)done;
+            part.d_direct = gi->d_direct ? gi->d_direct + 3 * done : nullptr;
+        }
         ShootPass P{d_rays + done, m, ray_type, options, d_rgb + 3 * done, stream, gi ? &part : nullptr, nullptr};
         if ((rc = query_list_reserve(ctx, m)) || (rc = shoot_level_reserve(ctx, 0, m, false, gi != nullptr)) || (rc = shoot_pass(ctx, P))) return rc;
     }
@@ -920,22 +941,24 @@ static int shoot_enqueue(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32
 
 // the host variants: copy in, run, copy out, `pass` rays at a time; the colours' device copy is level 0's own colour array
 static int shoot_host(crt_ctx *ctx, const crt_ray *rays, const uint32_t *keys, uint64_t n, uint32_t ray_type, const crt_options *options, float *out_rgb,
-                      const uint64_t pass, const bool gi) {
+                      const uint64_t pass, const bool gi, float *out_direct = nullptr) {
     const uint64_t m = std::min(n, pass);
     int rc = query_begin(ctx, ctx->stream, CALL_RADIANCE);
     if (rc) return rc;
     crt_query_state *q = ctx->query;
-    if ((rc = shoot_level_reserve(ctx, 0, m, true, gi)) || (rc = reserve_all(ctx, q->shoot_in, m, q->shoot_keys, keys ? m : 0))) return rc;
+    if ((rc = shoot_level_reserve(ctx, 0, m, true, gi)) || (rc = reserve_all(ctx, q->shoot_in, m, q->shoot_keys, keys ? m : 0, q->shoot_direct, out_direct ? 3 * m : 0)))
+        return rc;
     crt_shoot_stats total{};
     crt_query_stats qtotal{};
     for (uint64_t done = 0; done < n; done += pass) {
         const uint64_t k = std::min(n - done, pass);
         CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->shoot_in.p, rays + done, k * sizeof(crt_ray), hipMemcpyHostToDevice, ctx->stream));
         if (keys) CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->shoot_keys.p, keys + done, k * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        const ShootGi part{keys ? q->shoot_keys.p : nullptr, (uint32_t)done};
+        const ShootGi part{keys ? q->shoot_keys.p : nullptr, (uint32_t)done, out_direct ? q->shoot_direct.p : nullptr};
         rc = shoot_run(ctx, q->shoot_in.p, k, ray_type, options, q->lv[0].rgb.p, ctx->stream, pass, gi ? &part : nullptr);
         if (rc) return rc;
         CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb + 3 * done, q->lv[0].rgb.p, k * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        if (out_direct) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_direct + 3 * done, q->shoot_direct.p, k * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
         CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         rc = query_harvest(ctx);
         if (rc) return rc;
@@ -981,6 +1004,32 @@ extern "C" int crt_shoot_rays_gi(crt_ctx *ctx, const crt_ray *rays, const uint32
                        [&] { return shoot_host(ctx, rays, keys, n, ray_type, options, out_rgb, pass, true); });
 }
 
+// the split calls (csrc/split_rule.h): the same passes, and radiance_keep_direct behind level 0's lighting in each
+static int split_direct_check(crt_ctx *ctx, const char *what, const void *direct, const uint64_t n) {
+    if (!ctx || n == 0 || direct) return CRT_OK;   // (no context, no rays: query_entry's business)
+    ctx->error = std::string(what) + ": d_direct is NULL with n > 0 (crt_shoot_rays_gi* is the call without it)";
+    return CRT_ERR_INVALID;
+}
+
+extern "C" int crt_shoot_rays_gi_split_device(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t *d_keys, uint64_t n, uint32_t ray_type,
+                                              const crt_options *options, float *d_rgb, float *d_direct, void *stream) {
+    const char *what = "crt_shoot_rays_gi_split_device";
+    if (int rc = split_direct_check(ctx, what, d_direct, n)) return rc;
+    uint64_t pass = 0;
+    const ShootGi gi{d_keys, 0u, d_direct};
+    return query_entry(ctx, n, shoot_needs(what, d_rays, options, d_rgb, ray_type, true, &pass),
+                       [&] { return shoot_run(ctx, d_rays, n, ray_type, options, d_rgb, (hipStream_t)stream, pass, &gi); });
+}
+
+extern "C" int crt_shoot_rays_gi_split(crt_ctx *ctx, const crt_ray *rays, const uint32_t *keys, uint64_t n, uint32_t ray_type, const crt_options *options,
+                                       float *out_rgb, float *out_direct) {
+    const char *what = "crt_shoot_rays_gi_split";
+    if (int rc = split_direct_check(ctx, what, out_direct, n)) return rc;
+    uint64_t pass = 0;
+    return query_entry(ctx, n, shoot_needs(what, rays, options, out_rgb, ray_type, true, &pass),
+                       [&] { return shoot_host(ctx, rays, keys, n, ray_type, options, out_rgb, pass, true, out_direct); });
+}
+
 extern "C" int crt_shoot_rays_enqueue(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, float *d_rgb,
                                       const uint32_t *level_cap, crt_shoot_report *d_report, void *stream) {
     const char *what = "crt_shoot_rays_enqueue";
@@ -1012,7 +1061,7 @@ static QueryCamera camera_of(const crt_ctx *ctx) {
 }
 
 // what the two primitives ask of (d_pixels, n): without a list the call is for the whole frame; one thread per entry must fit a grid
-static int progressive_check(crt_ctx *ctx, const char *what, const uint32_t *d_pixels, const uint64_t n) {
+int progressive_check(crt_ctx *ctx, const char *what, const uint32_t *d_pixels, const uint64_t n) {
     const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
     if (!d_pixels && n != pixels) {
         ctx->error = std::string(what) + ": d_pixels is NULL, so n must be width * height = " + std::to_string(pixels) + ", not " + std::to_string(n);
@@ -1113,7 +1162,7 @@ extern "C" int crt_render_progressive(crt_ctx *ctx, const crt_options *options, 
     for (uint32_t s = first_sample; s - first_sample < n_samples; s++) {   // one at a time and in order: the fold's order is the frame's
         if (s == 0) {
             std::fill(q->level_peak, q->level_peak + MAX_GENERATIONS, 0ull);
-            q->prog_is_adaptive = false;
+            q->prog_is_adaptive = q->prog_is_split = false;
             q->new_frame();
             q->prog_active = pixels;   // (a uniform frame shoots every pixel in every pass)
         }
@@ -1217,9 +1266,10 @@ static bool same_adaptive(const crt_adaptive &a, const crt_adaptive &b) {
     return a.min_samples == b.min_samples && a.max_samples == b.max_samples && a.threshold == b.threshold && a.floor == b.floor;
 }
 
-extern "C" int crt_render_adaptive(crt_ctx *ctx, const crt_options *options, const crt_adaptive *adaptive, uint32_t first_pass, uint32_t n_passes,
-                                   float *out_rgb, uint32_t *out_counts) {
-    const char *what = "crt_render_adaptive";
+// crt_render_adaptive and, `split`, crt_render_adaptive_split: the same loop with the split shoot and, behind a pass's step, split_fold on
+// the same list and sample.  What the unsplit call produces is untouched by it.
+static int render_adaptive(crt_ctx *ctx, const char *what, const bool split, const crt_options *options, const crt_adaptive *adaptive, uint32_t first_pass,
+                           uint32_t n_passes, float *out_rgb, uint32_t *out_counts) {
     if (!ctx) return CRT_ERR_INVALID;
     if (n_passes == 0) return CRT_OK;
     uint64_t pass = 0;
@@ -1234,6 +1284,11 @@ extern "C" int crt_render_adaptive(crt_ctx *ctx, const crt_options *options, con
         ctx->error = std::string(what) + ": the frame under way is a UNIFORM progressive frame (crt_render_progressive continues it; first_pass 0 starts a new frame)";
         return CRT_ERR_INVALID;
     }
+    if (first_pass != 0 && ctx->query->prog_is_split != split) {
+        ctx->error = std::string(what) + (split ? ": the frame under way is an UNSPLIT adaptive frame (crt_render_adaptive continues it; first_pass 0 starts a new frame)"
+                                                : ": the frame under way is a SPLIT adaptive frame (crt_render_adaptive_split continues it; first_pass 0 starts a new frame)");
+        return CRT_ERR_INVALID;
+    }
     if (first_pass != 0 && !same_adaptive(*adaptive, ctx->query->prog_adaptive)) {
         ctx->error = std::string(what) + ": adaptive differs from the settings latched by the frame's pass 0";
         return CRT_ERR_INVALID;
@@ -1246,13 +1301,15 @@ extern "C" int crt_render_adaptive(crt_ctx *ctx, const crt_options *options, con
     crt_query_state *q = ctx->query;
     if ((rc = reserve_all(ctx, q->prog_sum, 3 * pixels, q->prog_rgb, 3 * pixels, q->prog_rays, pixels, q->prog_keys, pixels, q->prog_sq, pixels,
                           q->prog_counts, pixels, q->prog_list[0], pixels, q->prog_list[1], pixels, q->prog_next_n, 1, q->prog_work,
-                          (crt_adaptive_work_bytes(pixels) + 7) / 8)))
+                          (crt_adaptive_work_bytes(pixels) + 7) / 8)) ||
+        (split && (rc = reserve_all(ctx, q->split_direct, 3 * pixels, q->split_dsum, 3 * pixels, q->split_rsum, 3 * pixels, q->split_rsq, pixels))))
         return rc;
-    const ShootGi gi{q->prog_keys.p, 0u};
+    const ShootGi gi{q->prog_keys.p, 0u, split ? q->split_direct.p : nullptr};
     for (uint32_t s = first_pass; s - first_pass < n_passes; s++) {   // one at a time and in order: the fold's order is the frame's
         if (s == 0) {
             std::fill(q->level_peak, q->level_peak + MAX_GENERATIONS, 0ull);
             q->prog_is_adaptive = true;
+            q->prog_is_split = split;
             q->new_frame();            // (a new frame: crt_render_denoised traces its guides again)
             q->prog_adaptive = *adaptive;
             q->prog_active = pixels;
@@ -1264,7 +1321,9 @@ extern "C" int crt_render_adaptive(crt_ctx *ctx, const crt_options *options, con
             if ((rc = launch_sample_rays(ctx, options->gi_seed, s, list, n, q->prog_rays.p, q->prog_keys.p, ctx->stream)) ||
                 (rc = shoot_run(ctx, q->prog_rays.p, n, CRT_RAY_PRIMARY, options, q->prog_rgb.p, ctx->stream, pass, &gi)) ||
                 (rc = launch_adaptive(ctx, q->prog_rgb.p, list, n, s, adaptive, q->prog_sum.p, q->prog_sq.p, ctx->d_frame, q->prog_counts.p, next,
-                                      q->prog_next_n.p, q->prog_work.p, ctx->stream)))
+                                      q->prog_next_n.p, q->prog_work.p, ctx->stream)) ||
+                (split && (rc = split_launch_fold(ctx, q->prog_rgb.p, q->split_direct.p, list, n, s, q->split_dsum.p, q->split_rsum.p, q->split_rsq.p,
+                                                  ctx->stream))))
                 return rc;
             // the next list's length: 4 bytes through pinned memory, once a pass
             CRT_HIP_CHECK(ctx, hipMemcpyAsync(&q->pin->adaptive_n, q->prog_next_n.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -1282,12 +1341,39 @@ extern "C" int crt_render_adaptive(crt_ctx *ctx, const crt_options *options, con
     return CRT_OK;
 }
 
+extern "C" int crt_render_adaptive(crt_ctx *ctx, const crt_options *options, const crt_adaptive *adaptive, uint32_t first_pass, uint32_t n_passes,
+                                   float *out_rgb, uint32_t *out_counts) {
+    return render_adaptive(ctx, "crt_render_adaptive", false, options, adaptive, first_pass, n_passes, out_rgb, out_counts);
+}
+
+extern "C" int crt_render_adaptive_split(crt_ctx *ctx, const crt_options *options, const crt_adaptive *adaptive, uint32_t first_pass, uint32_t n_passes,
+                                         float *out_rgb, uint32_t *out_counts) {
+    return render_adaptive(ctx, "crt_render_adaptive_split", true, options, adaptive, first_pass, n_passes, out_rgb, out_counts);
+}
+
+extern "C" int crt_read_split_state(crt_ctx *ctx, float *out_dsum, float *out_rsum, float *out_rsq) {
+    const char *what = "crt_read_split_state";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (crt_progressive_samples(ctx) == 0 || !ctx->query->prog_is_adaptive || !ctx->query->prog_is_split) {
+        ctx->error = std::string(what) + ": no split adaptive frame is under way (crt_render_adaptive_split starts one; crt_set_camera and crt_render* end it)";
+        return CRT_ERR_INVALID;
+    }
+    const crt_query_state *q = ctx->query;
+    const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (out_dsum) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_dsum, q->split_dsum.p, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (out_rsum) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rsum, q->split_rsum.p, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (out_rsq) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rsq, q->split_rsq.p, pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return CRT_OK;
+}
+
 // ---- denoising (crt_denoise.hip, csrc/kernel_denoise.h, csrc/denoise_rule.h): the adaptive frame under way or finished, filtered into a
 // buffer of its own.  Nothing of the frame changes: the persistent colour buffer, sum, sq, counts, the lists and crt_progressive_samples
 // are only read, so the frame can be denoised after any pass and continued.
 
 // what crt_render_denoised and crt_render_accumulated ask of the context's frame
-static int adaptive_frame_check(crt_ctx *ctx, const char *what) {
+static int adaptive_frame_check(crt_ctx *ctx, const char *what, const bool split) {
     if (crt_progressive_samples(ctx) == 0) {
         ctx->error = std::string(what) + ": no adaptive frame is under way (crt_render_adaptive starts one; crt_set_camera and crt_render* end it)";
         return CRT_ERR_INVALID;
@@ -1297,8 +1383,18 @@ static int adaptive_frame_check(crt_ctx *ctx, const char *what) {
                                          "with min_samples = max_samples";
         return CRT_ERR_INVALID;
     }
+    if (split && !ctx->query->prog_is_split) {
+        ctx->error = std::string(what) + ": the frame under way is an UNSPLIT adaptive frame, which keeps no direct part: crt_render_adaptive_split makes a split one";
+        return CRT_ERR_INVALID;
+    }
     if ((uint64_t)ctx->width * ctx->height >= (1ull << 31)) { ctx->error = std::string(what) + ": width * height >= 2^31"; return CRT_ERR_INVALID; }
     return CRT_OK;
+}
+
+// the fold's state the two frame calls below filter: the whole colour's, or -- `split` -- the rest's (csrc/split_rule.h)
+struct FoldState { const float *sum, *sq; };
+static FoldState fold_state(const crt_query_state *q, const bool split) {
+    return split ? FoldState{q->split_rsum.p, q->split_rsq.p} : FoldState{q->prog_sum.p, q->prog_sq.p};
 }
 
 // the frame's guides, traced at the frame's first call of either kind: the first hits of the camera's centre rays, as CRT_RAY_PRIMARY (the
@@ -1314,11 +1410,11 @@ static int frame_guides(crt_ctx *ctx, const uint64_t pixels) {
     return CRT_OK;
 }
 
-extern "C" int crt_render_denoised(crt_ctx *ctx, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8) {
-    const char *what = "crt_render_denoised";
+// crt_render_denoised and, `split`, crt_render_denoised_split: the rest is filtered and the direct part's mean added back untouched
+static int render_denoised(crt_ctx *ctx, const char *what, const bool split, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8) {
     if (!ctx) return CRT_ERR_INVALID;
     if (int rc = denoise_check(ctx, what, denoise)) return rc;
-    if (int rc = adaptive_frame_check(ctx, what)) return rc;
+    if (int rc = adaptive_frame_check(ctx, what, split)) return rc;
     const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
     int rc;
     if ((rc = query_begin(ctx, ctx->stream, CALL_QUERY))) return rc;
@@ -1327,9 +1423,11 @@ extern "C" int crt_render_denoised(crt_ctx *ctx, const crt_denoise *denoise, flo
                           (crt_denoise_work_bytes(ctx->width, ctx->height) + sizeof(float4) - 1) / sizeof(float4), q->den_q8, 3 * pixels)) ||
         (rc = frame_guides(ctx, pixels)))
         return rc;
-    if ((rc = denoise_launch_variance(ctx, q->prog_sum.p, q->prog_sq.p, q->prog_counts.p, pixels, q->den_mean.p, q->den_var.p, ctx->stream)) ||
+    const FoldState state = fold_state(q, split);
+    if ((rc = denoise_launch_variance(ctx, state.sum, state.sq, q->prog_counts.p, pixels, q->den_mean.p, q->den_var.p, ctx->stream)) ||
         (rc = denoise_launch(ctx, denoise, ctx->width, ctx->height, q->den_mean.p, q->den_var.p, q->den_hits.p, q->den_out.p, nullptr, q->den_work.p,
-                             ctx->stream)))
+                             ctx->stream)) ||
+        (split && (rc = split_launch_recombine(ctx, q->den_out.p, q->split_dsum.p, q->prog_counts.p, pixels, q->den_out.p, ctx->stream))))
         return rc;
     if (out_rgb) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, q->den_out.p, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (out_rgb8) {
@@ -1340,50 +1438,61 @@ extern "C" int crt_render_denoised(crt_ctx *ctx, const crt_denoise *denoise, flo
     return CRT_OK;
 }
 
+extern "C" int crt_render_denoised(crt_ctx *ctx, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8) {
+    return render_denoised(ctx, "crt_render_denoised", false, denoise, out_rgb, out_rgb8);
+}
+
+extern "C" int crt_render_denoised_split(crt_ctx *ctx, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8) {
+    return render_denoised(ctx, "crt_render_denoised_split", true, denoise, out_rgb, out_rgb8);
+}
+
 // ---- temporal accumulation (crt_temporal.hip, csrc/kernel_temporal.h, csrc/temporal_rule.h): the adaptive frame's state merged with the
 // last frame's history, into buffers of its own.  The frame is only read, as crt_render_denoised reads it.  `previous` changes only when a
 // call finds a new frame's serial, so every call on one frame merges the same history.
 
-extern "C" int crt_render_accumulated(crt_ctx *ctx, const crt_temporal *temporal, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8,
-                                      uint8_t *out_valid) {
-    const char *what = "crt_render_accumulated";
+// crt_render_accumulated and, `split`, crt_render_accumulated_split: the history pair hist[split] holds the moments of what the call
+// merges -- whole colours, or the rest --, and the direct part's mean is this frame's own, added back behind the optional filter
+static int render_accumulated(crt_ctx *ctx, const char *what, const bool split, const crt_temporal *temporal, const crt_denoise *denoise, float *out_rgb,
+                              uint8_t *out_rgb8, uint8_t *out_valid) {
     if (!ctx) return CRT_ERR_INVALID;
     if (int rc = temporal_check(ctx, what, temporal)) return rc;
     if (denoise)
         if (int rc = denoise_check(ctx, what, denoise)) return rc;
-    if (int rc = adaptive_frame_check(ctx, what)) return rc;
+    if (int rc = adaptive_frame_check(ctx, what, split)) return rc;
     const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
     int rc;
     if ((rc = query_begin(ctx, ctx->stream, CALL_QUERY))) return rc;
     crt_query_state *q = ctx->query;
-    if ((rc = reserve_all(ctx, q->den_hits, pixels, q->hist[0], pixels, q->hist[1], pixels, q->acc_rgb, 3 * pixels, q->acc_var, pixels, q->acc_valid,
+    crt_query_state::History &hist = q->hist[split ? 1 : 0];
+    if ((rc = reserve_all(ctx, q->den_hits, pixels, hist.slot[0], pixels, hist.slot[1], pixels, q->acc_rgb, 3 * pixels, q->acc_var, pixels, q->acc_valid,
                           pixels, q->den_q8, 3 * pixels)) ||
         (denoise && (rc = reserve_all(ctx, q->den_out, 3 * pixels, q->den_work,
                                       (crt_denoise_work_bytes(ctx->width, ctx->height) + sizeof(float4) - 1) / sizeof(float4)))) ||
         (rc = frame_guides(ctx, pixels)))
         return rc;
-    if (q->hist_has_cur && q->hist_serial != q->frame_serial) {   // `current` is an ended frame's: it is the previous history from here on
-        q->hist_cur ^= 1;
-        q->hist_has_prev = true;
-        q->hist_has_cur = false;
+    if (hist.has_cur && hist.serial != q->frame_serial) {   // `current` is an ended frame's: it is the previous history from here on
+        hist.cur ^= 1;
+        hist.has_prev = true;
+        hist.has_cur = false;
     }
-    const int cur = q->hist_cur;
-    if ((rc = temporal_launch(ctx, temporal, ctx->width, ctx->height, &q->hist_pose[cur ^ 1], q->hist_has_prev ? q->hist[cur ^ 1].p : nullptr,
-                              q->prog_sum.p, q->prog_sq.p, q->prog_counts.p, q->den_hits.p, q->hist[cur].p, q->acc_rgb.p, q->acc_var.p, q->acc_valid.p,
-                              ctx->stream)))
+    const int cur = hist.cur;
+    const FoldState state = fold_state(q, split);
+    if ((rc = temporal_launch(ctx, temporal, ctx->width, ctx->height, &hist.pose[cur ^ 1], hist.has_prev ? hist.slot[cur ^ 1].p : nullptr, state.sum,
+                              state.sq, q->prog_counts.p, q->den_hits.p, hist.slot[cur].p, q->acc_rgb.p, q->acc_var.p, q->acc_valid.p, ctx->stream)))
         return rc;
-    if (!q->hist_has_cur) q->hist_frames++;   // once a frame
-    q->hist_has_cur = true;
-    q->hist_serial = q->frame_serial;
-    memcpy(q->hist_pose[cur].position, ctx->frame.cam_pos, sizeof(q->hist_pose[cur].position));
-    memcpy(q->hist_pose[cur].matrix, ctx->frame.cam, sizeof(q->hist_pose[cur].matrix));
-    const float *result = q->acc_rgb.p;
+    if (!hist.has_cur) hist.frames++;   // once a frame
+    hist.has_cur = true;
+    hist.serial = q->frame_serial;
+    memcpy(hist.pose[cur].position, ctx->frame.cam_pos, sizeof(hist.pose[cur].position));
+    memcpy(hist.pose[cur].matrix, ctx->frame.cam, sizeof(hist.pose[cur].matrix));
+    float *result = q->acc_rgb.p;
     if (denoise) {
         if ((rc = denoise_launch(ctx, denoise, ctx->width, ctx->height, q->acc_rgb.p, q->acc_var.p, q->den_hits.p, q->den_out.p, nullptr, q->den_work.p,
                                  ctx->stream)))
             return rc;
         result = q->den_out.p;
     }
+    if (split && (rc = split_launch_recombine(ctx, result, q->split_dsum.p, q->prog_counts.p, pixels, result, ctx->stream))) return rc;
     if (out_rgb) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, result, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (out_rgb8) {
         if ((rc = crt_quantize_device(ctx, result, 3 * pixels, q->den_q8.p, ctx->stream))) return rc;
@@ -1394,13 +1503,24 @@ extern "C" int crt_render_accumulated(crt_ctx *ctx, const crt_temporal *temporal
     return CRT_OK;
 }
 
+extern "C" int crt_render_accumulated(crt_ctx *ctx, const crt_temporal *temporal, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8,
+                                      uint8_t *out_valid) {
+    return render_accumulated(ctx, "crt_render_accumulated", false, temporal, denoise, out_rgb, out_rgb8, out_valid);
+}
+
+extern "C" int crt_render_accumulated_split(crt_ctx *ctx, const crt_temporal *temporal, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8,
+                                            uint8_t *out_valid) {
+    return render_accumulated(ctx, "crt_render_accumulated_split", true, temporal, denoise, out_rgb, out_rgb8, out_valid);
+}
+
 extern "C" int crt_history_reset(crt_ctx *ctx) {
     if (!ctx) return CRT_ERR_INVALID;
-    if (crt_query_state *q = ctx->query) {   // (the slots stay allocated: nothing reads them until a call has written one again)
-        q->hist_has_cur = q->hist_has_prev = false;
-        q->hist_frames = 0;
+    if (crt_query_state *q = ctx->query) {
+        q->hist[0].reset();
+        q->hist[1].reset();
     }
     return CRT_OK;
 }
 
-extern "C" uint32_t crt_history_frames(const crt_ctx *ctx) { return ctx && ctx->query ? ctx->query->hist_frames : 0u; }
+extern "C" uint32_t crt_history_frames(const crt_ctx *ctx) { return ctx && ctx->query ? ctx->query->hist[0].frames : 0u; }
+extern "C" uint32_t crt_history_frames_split(const crt_ctx *ctx) { return ctx && ctx->query ? ctx->query->hist[1].frames : 0u; }

@@ -61,7 +61,8 @@
 //
 // Known limits.
 //   * There is no albedo demodulation, because the library has no albedo query.  Texture detail inside one mesh is protected by the colour
-//     weight alone.
+//     weight alone.  The split frames (csrc/split_rule.h) feed this rule the indirect light only and add the direct light, which carries
+//     the texels, back untouched.
 //   * Reflections in a flat mirror are guided by the mirror's own plane.
 //   * With count == 1 every variance is 0, so the filter hardly smooths.  Use at least 2 samples.
 #pragma once

@@ -377,7 +377,7 @@ std::vector<std::vector<Color>> RayTracer::renderProgressive(const std::string &
 }
 
 std::vector<std::vector<Color>> RayTracer::renderAdaptive(const std::string &pathToImage, RenderOptions ro, const crt_adaptive &adaptive,
-                                                          unsigned int passesPerCall, std::vector<uint32_t> *counts) {
+                                                          unsigned int passesPerCall, std::vector<uint32_t> *counts, bool split) {
   if (multi) throw std::runtime_error("renderAdaptive: not available on a multi-device tracer");
   const unsigned int W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
   crt_options o{};
@@ -396,7 +396,7 @@ std::vector<std::vector<Color>> RayTracer::renderAdaptive(const std::string &pat
   int rc = crt_set_camera(ctx, pos, &m.m[0][0]);  // (starts a new frame)
   for (unsigned int done = 0; rc == CRT_OK && (done == 0 || (done < adaptive.max_samples && crt_progressive_active(ctx)));) {
     const unsigned int k = std::min(passesPerCall, std::max(adaptive.max_samples, 1u) - done);
-    rc = crt_render_adaptive(ctx, &o, &adaptive, done, k, frame.data(), held.data());
+    rc = (split ? crt_render_adaptive_split : crt_render_adaptive)(ctx, &o, &adaptive, done, k, frame.data(), held.data());
     done += k;
   }
   if (rc == CRT_OK && !pathToImage.empty()) {
@@ -415,12 +415,12 @@ std::vector<std::vector<Color>> RayTracer::renderAdaptive(const std::string &pat
   return colorBuffer;
 }
 
-std::vector<std::vector<Color>> RayTracer::renderDenoised(const std::string &pathToImage, const crt_denoise &denoise) {
+std::vector<std::vector<Color>> RayTracer::renderDenoised(const std::string &pathToImage, const crt_denoise &denoise, bool split) {
   if (multi) throw std::runtime_error("renderDenoised: not available on a multi-device tracer");
   const unsigned int W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
   std::vector<float> denoised((size_t)W * H * 3, 0.0f);
   std::vector<uint8_t> q(pathToImage.empty() ? 0 : (size_t)W * H * 3);
-  const int rc = crt_render_denoised(ctx, &denoise, denoised.data(), pathToImage.empty() ? nullptr : q.data());
+  const int rc = (split ? crt_render_denoised_split : crt_render_denoised)(ctx, &denoise, denoised.data(), pathToImage.empty() ? nullptr : q.data());
   if (rc != CRT_OK) throw std::runtime_error(std::string("renderDenoised failed: ") + crt_last_error(ctx));
   if (!pathToImage.empty()) writePPMQuantized(pathToImage, q.data(), W, H);
   std::vector<std::vector<Color>> colorBuffer(H, std::vector<Color>(W));
@@ -433,13 +433,14 @@ std::vector<std::vector<Color>> RayTracer::renderDenoised(const std::string &pat
 }
 
 std::vector<std::vector<Color>> RayTracer::renderAccumulated(const std::string &pathToImage, const crt_temporal &temporal, const crt_denoise *denoise,
-                                                             double *validShare) {
+                                                             double *validShare, bool split) {
   if (multi) throw std::runtime_error("renderAccumulated: not available on a multi-device tracer");
   const unsigned int W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
   std::vector<float> merged((size_t)W * H * 3, 0.0f);
   std::vector<uint8_t> q(pathToImage.empty() ? 0 : (size_t)W * H * 3);
   std::vector<uint8_t> valid(validShare ? (size_t)W * H : 0);
-  const int rc = crt_render_accumulated(ctx, &temporal, denoise, merged.data(), pathToImage.empty() ? nullptr : q.data(), validShare ? valid.data() : nullptr);
+  const int rc = (split ? crt_render_accumulated_split : crt_render_accumulated)(ctx, &temporal, denoise, merged.data(), pathToImage.empty() ? nullptr : q.data(),
+                                                                                 validShare ? valid.data() : nullptr);
   if (rc != CRT_OK) throw std::runtime_error(std::string("renderAccumulated failed: ") + crt_last_error(ctx));
   if (validShare) {  // over the hit pixels: the first hits of the camera's rays, which are the call's own guides
     std::vector<crt_hit> hits((size_t)W * H);

@@ -128,13 +128,15 @@ class RayTracer {
   // given, receives the samples each pixel holds (row-major): a pixel with k samples is render()'s pixel with RAYS_PER_PIXEL = k.
   // Single-device tracers only; USE_GI must be set.
   std::vector<std::vector<Color>> renderAdaptive(const std::string &pathToImage, RenderOptions renderOptions, const crt_adaptive &adaptive,
-                                                 unsigned int passesPerCall = 1, std::vector<uint32_t> *counts = nullptr);
+                                                 unsigned int passesPerCall = 1, std::vector<uint32_t> *counts = nullptr, bool split = false);
 
   // ---- denoising (crt_hip.h: crt_render_denoised): the adaptive frame renderAdaptive left, under way or finished, through the
   // variance-guided a-trous filter with the settings of `denoise` (crt_denoise_defaults), guided by the first hits of the camera's rays.
   // The frame itself is left as it was.  The PPM, if a path is given, is the denoised frame quantised by the PPMColor rule.
   // Single-device tracers only.
-  std::vector<std::vector<Color>> renderDenoised(const std::string &pathToImage, const crt_denoise &denoise);
+  // split (crt_hip.h: "Split GI frames"; all three calls): renderAdaptive keeps every sample's direct light beside the same frame, and
+  // renderDenoised / renderAccumulated filter and reproject the indirect light only and add the direct light -- the texels -- back.
+  std::vector<std::vector<Color>> renderDenoised(const std::string &pathToImage, const crt_denoise &denoise, bool split = false);
 
   // ---- temporal accumulation (crt_hip.h: crt_render_accumulated): the adaptive frame renderAdaptive left, merged with the history of the
   // frames accumulated before it -- reprojected through the camera each of them had -- and then, with `denoise`, through the a-trous
@@ -142,7 +144,7 @@ class RayTracer {
   // different gi seeds.  validShare, if given, receives the share of the hit pixels with at least one valid history tap.  The PPM, if
   // a path is given, is the result quantised by the PPMColor rule.  Single-device tracers only.
   std::vector<std::vector<Color>> renderAccumulated(const std::string &pathToImage, const crt_temporal &temporal, const crt_denoise *denoise = nullptr,
-                                                    double *validShare = nullptr);
+                                                    double *validShare = nullptr, bool split = false);
   void resetHistory();
 
   // flat access for callers that do not want the vector-of-vectors copy

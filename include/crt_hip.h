@@ -670,7 +670,8 @@ uint64_t crt_progressive_active(const crt_ctx *ctx);
  *         pass through
  *   iterations == 0 copies input to output.  A NaN that arises from overflow is whatever these lines give.
  * Known limits.  There is no albedo demodulation, because the library has no albedo query: texture detail inside one mesh is protected by
- *   the colour weight alone.  Reflections in a flat mirror are guided by the mirror's own plane.  With count == 1 every variance is 0, so
+ *   the colour weight alone -- in THIS call; crt_render_denoised_split ("Split GI frames", below) filters the indirect light only and
+ *   adds the direct light, which carries the texels, back untouched.  Reflections in a flat mirror are guided by the mirror's own plane.  With count == 1 every variance is 0, so
  *   the filter hardly smooths: use at least 2 samples.
  * crt_denoise: size must be sizeof(crt_denoise) = 24, iterations <= 8, normal_squarings <= 16, sigma_colour and sigma_plane >= 0 and finite,
  *   floor > 0 and finite: anything else is CRT_ERR_INVALID, with nothing enqueued.  crt_denoise_defaults: 4, 5, 2.0f, 0.02f, 1e-6f.
@@ -781,7 +782,8 @@ int crt_render_denoised(crt_ctx *ctx, const crt_denoise *denoise, float *out_rgb
  *   lives for one frame.
  * Known limits.  A miss pixel keeps no history.  A matrix that is not a rotation reprojects wrongly.  The geometry tests reject most of
  *   those taps, but not a slide within one plane.  Reflections are reprojected as if painted on the mirror.  The history holds the
- *   unfiltered moments: the filtered colour is not fed back.
+ *   unfiltered moments: the filtered colour is not fed back.  Texture detail is reprojected and filtered with the noise in this call;
+ *   crt_render_accumulated_split ("Split GI frames", below) does both to the indirect light only.
  * crt_temporal: size must be sizeof(crt_temporal) = 16, max_history > 0 and finite, normal_min finite, sigma_plane >= 0 and finite:
  *   anything else is CRT_ERR_INVALID, with nothing enqueued.  crt_temporal_defaults: 64.0f, 0.9f, 0.02f.
  * crt_temporal_device: the rule for every pixel of a width x height image of the caller's: d_sum (3 floats a pixel), d_sq and d_counts --
@@ -832,6 +834,72 @@ int crt_render_accumulated(crt_ctx *ctx, const crt_temporal *temporal, const crt
                            uint8_t *out_rgb8, uint8_t *out_valid);
 int crt_history_reset(crt_ctx *ctx);
 uint32_t crt_history_frames(const crt_ctx *ctx);
+
+/* ---- Split GI frames: denoise and accumulate the INDIRECT light only.  The reference's calculateDiffusion (RayTracer.cpp:300-356) gives a
+ * diffuse hit  colour = (sum over lights of k * base + sum of the GI sample rays' colours) * (1 / (GI_SAMPLE_SIZE + 1)):  the texture /
+ * albedo `base` multiplies the direct term alone, so dividing a pixel by its albedo would stamp the inverse texture into the indirect
+ * light.  The split that fits is ADDITIVE: a sample is cut into its direct part -- deterministic for a given ray; it carries every texel
+ * and every hard shadow edge -- and the rest, the only part with Monte-Carlo noise.  The rest is filtered and reprojected, and the direct
+ * part is added back untouched.  Kernels: csrc/kernel_split.h (radiance_keep_direct, split_fold, split_recombine); the rule, one header
+ * for host and device: csrc/split_rule.h; tests/split_sets.py restates it.  Every line below is one float32 operation
+ * (-ffp-contract=off).  Single-device contexts only.
+ * crt_shoot_rays_gi_split / crt_shoot_rays_gi_split_device: crt_shoot_rays_gi / crt_shoot_rays_gi_device with one more output, direct
+ *   (3 floats a ray); rgb is bit for bit what the unsplit call writes.  direct[i] depends on the level-0 status of ray i (after shootRay's
+ *   entry normalisation), read behind level 0's lighting and before the up-sweep, when the level's colour array holds L, a DIFFUSE
+ *   record's direct light:
+ *     CRT_SHADE_DIFFUSE                       direct_c = L_c * gi_inv, gi_inv = 1.0f / (float)(gi_sample_size + 1)
+ *     CRT_SHADE_BACKGROUND                    direct_c = the ray's whole colour (a miss or a constant material: no noise but its jitter's)
+ *     CRT_SHADE_RECURSES, CRT_SHADE_INVALID   direct_c = 0: a mirror's or glass's whole colour is "rest"
+ *   A call that runs in several passes writes each pass's slice.  A NULL direct with n > 0 is CRT_ERR_INVALID, beside everything the
+ *   unsplit call refuses, with nothing enqueued.  The enqueue-only variants (crt_shoot_rays_gi_enqueue) have NO split form.
+ * crt_split_fold_device: one step of the split's fold for entry i < n, pixel p = d_pixels ? d_pixels[i] : i:
+ *     r_c      = rgb[3i+c] - direct[3i+c]
+ *     dsum_c   = (sample == 0 ? 0.0f : dsum_c) + direct[3i+c]
+ *     rsum_c   = (sample == 0 ? 0.0f : rsum_c) + r_c
+ *     rsq      = (sample == 0 ? 0.0f : rsq) + ((r_r*r_r + r_g*r_g) + r_b*r_b)
+ *   on d_dsum and d_rsum (3 floats a PIXEL) and d_rsq (one).  (d_pixels, n) follow crt_accumulate_samples_device's rules: without a list
+ *   n must be width * height, the pixels of one call must be distinct, an index outside the frame is skipped before any address is formed
+ *   from it.  d_rsum, d_rsq and the frame's counts have the shape of crt_adaptive_step_device's sum, sq and counts, so the rest goes
+ *   through crt_sample_variance_device, crt_temporal_device and crt_denoise_device as they are.
+ * crt_split_recombine_device: for i < n_pixels
+ *     count == 0: out_c = filtered_c
+ *     else:       inv = 1.0f / (float)count; out_c = filtered_c + dsum_c * inv
+ *   d_out may be d_filtered.  Both device calls only ENQUEUE on `stream`: one launch, no wait, no allocation, no readback; a NULL array
+ *   with n > 0 is CRT_ERR_INVALID, n == 0 is CRT_OK and touches nothing.
+ * crt_render_adaptive_split is crt_render_adaptive's loop with the split shoot and, behind a pass's step, the fold above on the same list
+ *   and sample.  Everything crt_render_adaptive produces is that call's bit for bit -- the colour buffer, sum, sq, counts, the lists,
+ *   out_rgb, out_counts, crt_progressive_active --, and the stopping rule still sees the whole colour.  The frame is latched as split at
+ *   pass 0: continuing a split frame with crt_render_adaptive, or an unsplit one with this call, is CRT_ERR_INVALID.  The three arrays
+ *   of the split's state are the context's, allocated on first use and freed by crt_destroy; crt_read_split_state copies them to host
+ *   memory (height * width * 3 floats of dsum and of rsum, height * width of rsq; any may be NULL) while a split frame is under way --
+ *   dsum times 1 / count is the frame's direct-light layer.
+ * crt_render_denoised_split refuses what crt_render_denoised refuses, and a frame that is not split.  crt_sample_variance_device's lines on
+ *   (rsum, rsq, counts), the a-trous filter on that mean and variance with the frame's shared guides, the recombine, then out_rgb and
+ *   out_rgb8 as crt_render_denoised's.
+ * crt_render_accumulated_split is crt_render_accumulated on (rsum, rsq, counts), with the recombine behind the optional filter.  The
+ *   direct part's mean is this frame's own and is not accumulated: it has no noise to average.  The history holds the moments of the
+ *   REST, which must never meet crt_render_accumulated's records of whole colours: this call owns a second pair of history slots and
+ *   poses, under the same serial rule.  The two calls do not disturb each other's history.  crt_history_reset drops both pairs;
+ *   crt_history_frames_split counts this pair's frames, crt_history_frames the other's, as before.
+ * All three leave the frame readable, as their unsplit siblings do: a frame can be denoised after any pass and continued.
+ * Known limits.  Mirrors and glass are all "rest" and are filtered as before.  A sample with an infinite channel gives inf - inf = NaN in
+ *   the rest, and such a pixel passes through the filter as NaN pixels do.  The output is filtered + dmean by the rule: with 0 iterations
+ *   it is not bit-equal to the unsplit mean. */
+int crt_shoot_rays_gi_split(crt_ctx *ctx, const crt_ray *rays, const uint32_t *keys, uint64_t n, uint32_t ray_type,
+                            const crt_options *options, float *out_rgb, float *out_direct);
+int crt_shoot_rays_gi_split_device(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t *d_keys, uint64_t n, uint32_t ray_type,
+                                   const crt_options *options, float *d_rgb, float *d_direct, void *stream);
+int crt_split_fold_device(crt_ctx *ctx, const float *d_rgb, const float *d_direct, const uint32_t *d_pixels, uint64_t n, uint32_t sample,
+                          float *d_dsum, float *d_rsum, float *d_rsq, void *stream);
+int crt_split_recombine_device(crt_ctx *ctx, const float *d_filtered, const float *d_dsum, const uint32_t *d_counts, uint64_t n_pixels,
+                               float *d_out, void *stream);
+int crt_render_adaptive_split(crt_ctx *ctx, const crt_options *options, const crt_adaptive *adaptive, uint32_t first_pass, uint32_t n_passes,
+                              float *out_rgb, uint32_t *out_counts);
+int crt_read_split_state(crt_ctx *ctx, float *out_dsum, float *out_rsum, float *out_rsq);
+int crt_render_denoised_split(crt_ctx *ctx, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8);
+int crt_render_accumulated_split(crt_ctx *ctx, const crt_temporal *temporal, const crt_denoise *denoise /* NULL: no spatial filter */,
+                                 float *out_rgb, uint8_t *out_rgb8, uint8_t *out_valid);
+uint32_t crt_history_frames_split(const crt_ctx *ctx);
 
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
