@@ -254,6 +254,7 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_st
                   "crt_temporal_defaults", "crt_temporal_device", "crt_render_accumulated", "crt_history_reset", "crt_history_frames",
                   "crt_shoot_rays_gi_split", "crt_shoot_rays_gi_split_device", "crt_split_fold_device", "crt_split_recombine_device",
                   "crt_render_adaptive_split", "crt_read_split_state", "crt_render_denoised_split", "crt_render_accumulated_split", "crt_history_frames_split",
+                  "crt_guide_work_bytes", "crt_guide_rays", "crt_guide_rays_device", "crt_set_guide_bounces", "crt_guide_bounces",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -355,6 +356,13 @@ def lib():
     L.crt_read_split_state.argtypes = [vp, vp, vp, vp]
     L.crt_render_accumulated_split.argtypes = [vp, C.POINTER(Temporal), C.POINTER(Denoise), vp, vp, vp]
     L.crt_history_frames_split.argtypes = [vp]
+    L.crt_guide_work_bytes.restype = C.c_size_t
+    L.crt_guide_work_bytes.argtypes = [C.c_uint64]
+    L.crt_guide_rays.argtypes = [vp, vp, C.c_uint64, u32, C.POINTER(Options), u32, vp, vp, vp]
+    L.crt_guide_rays_device.argtypes = [vp, vp, C.c_uint64, u32, C.POINTER(Options), u32, vp, vp, vp, vp, vp]
+    L.crt_set_guide_bounces.argtypes = [vp, u32]
+    L.crt_guide_bounces.restype = u32
+    L.crt_guide_bounces.argtypes = [vp]
     L.crt_history_frames_split.restype = u32
     L.crt_host_shoot_stats_layout.argtypes = [C.POINTER(u32), u32]
     L.crt_host_shoot_stats_layout.restype = u32
@@ -1044,6 +1052,42 @@ class Tracer:
         """The frames merged into the history (split: into the split calls' history) since the last history_reset."""
         self._single("history_frames")
         return int((lib().crt_history_frames_split if split else lib().crt_history_frames)(self.ctx))
+
+    # ---- chain guides (include/crt_hip.h: crt_guide_rays*, crt_set_guide_bounces): filter guides that follow mirrors and glass
+    def guide_work_bytes(self, n) -> int:
+        return int(lib().crt_guide_work_bytes(int(n)))
+
+    def guide_rays(self, rays, ray_type=RAY_PRIMARY, max_bounces=4, reflection_bias=1e-4, refraction_bias=1e-4):
+        """The chain guide of each ray: the record of the first diffuse or constant surface it reaches through mirrors and glass, with
+        the path length as t and a tagged mesh; rays float32 [n, 6] (used as given) -> (records HIT_DTYPE [n], status uint8 [n]: bits 0-5
+        the bounces, bit 7 cut at max_bounces, last_rays float32 [n, 6]: the terminal segment's ray)."""
+        self._single("guide_rays")
+        rays = self._rays_array(rays)
+        hits = np.zeros(len(rays), dtype=HIT_DTYPE)
+        status = np.zeros(len(rays), dtype=np.uint8)
+        last = np.zeros((len(rays), 6), dtype=np.float32)
+        o = make_options(0, 1e-4, reflection_bias, refraction_bias)
+        self._check(lib().crt_guide_rays(self.ctx, _p(rays), len(rays), ray_type, C.byref(o), int(max_bounces), _p(hits), _p(status), _p(last)))
+        return hits, status, last
+
+    def guide_rays_device(self, d_rays_ptr, n, ray_type, max_bounces, d_hits_ptr, d_work_ptr, d_status_ptr=None, d_last_rays_ptr=None,
+                          reflection_bias=1e-4, refraction_bias=1e-4, stream_ptr=None):
+        """The same on device memory (rays float32 [n, 6], hits uint8 [n, 48], status uint8 [n] or None, last_rays float32 [n, 6] or None,
+        work guide_work_bytes(n) bytes, 16-byte aligned).  Enqueues and returns."""
+        self._single("guide_rays_device")
+        o = make_options(0, 1e-4, reflection_bias, refraction_bias)
+        self._check(lib().crt_guide_rays_device(self.ctx, C.c_void_p(d_rays_ptr), int(n), ray_type, C.byref(o), int(max_bounces), C.c_void_p(d_hits_ptr),
+                                                C.c_void_p(d_status_ptr or 0), C.c_void_p(d_last_rays_ptr or 0), C.c_void_p(d_work_ptr),
+                                                C.c_void_p(stream_ptr or 0)))
+
+    def set_guide_bounces(self, max_bounces):
+        """0 (the default): the frame calls filter under first-hit guides.  Above 0: render_denoised's and render_accumulated's spatial
+        filter runs under the chain guides of the camera's centre rays; the temporal stage keeps the first hits."""
+        self._single("set_guide_bounces")
+        self._check(lib().crt_set_guide_bounces(self.ctx, int(max_bounces)))
+
+    def guide_bounces(self) -> int:
+        return int(lib().crt_guide_bounces(self.ctx))
 
     # ---- split GI frames (include/crt_hip.h: crt_split_fold_device, crt_split_recombine_device)
     def split_fold_device(self, d_rgb_ptr, d_direct_ptr, sample, d_dsum_ptr, d_rsum_ptr, d_rsq_ptr, n=None, d_pixels_ptr=None, stream_ptr=None):

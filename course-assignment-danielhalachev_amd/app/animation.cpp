@@ -71,10 +71,11 @@ int main(int argc, char **argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s scene.crtscene out_prefix [--folder DIR] [--depth N] [--fps F] [--seconds S] [--radius R] [--device D] "
                          "[--in-flight K] [--writers N] [--no-ppm]\n"
-                         "       [--gi SAMPLE_SIZE --adaptive THRESHOLD MIN MAX [--seed S] [--denoise [ITERATIONS]] [--temporal [MAX_HISTORY]] [--split]]   (GI frames, one at a\n"
+                         "       [--gi SAMPLE_SIZE --adaptive THRESHOLD MIN MAX [--seed S] [--denoise [ITERATIONS]] [--temporal [MAX_HISTORY]] [--split] [--guide-bounces B]]   (GI frames, one at a\n"
                          "        time: every pixel is shot MIN .. MAX times; --denoise: through crt_hip.h's crt_denoise; --temporal: merged with the\n"
                          "        history of the frames before it, crt_hip.h's crt_temporal, then through the filter if --denoise is given;\n"
-                         "        --split: both act on the indirect light only, crt_hip.h's \"Split GI frames\")\n", argv[0]);
+                         "        --split: both act on the indirect light only, crt_hip.h's \"Split GI frames\";\n"
+                         "        --guide-bounces B, 0..63: the filter of --denoise runs under guides that follow mirrors and glass, crt_hip.h's \"Chain guides\")\n", argv[0]);
     return 2;
   }
   std::string scenePath = argv[1], prefix = argv[2], folder;
@@ -88,6 +89,7 @@ int main(int argc, char **argv) {
   unsigned giSamples = 2, adaptiveMin = 0, adaptiveMax = 0, seed = 0;
   float adaptiveThreshold = 0.0f, maxHistory = -1.0f;  // (-1: crt_temporal_defaults')
   int denoiseIterations = -1;                          // (-1: crt_denoise_defaults')
+  int guideBounces = -1;                               // (-1: not given)
   auto number = [&](int i) { return i < argc && ((argv[i][0] >= '0' && argv[i][0] <= '9') || argv[i][0] == '.'); };
   for (int i = 3; i < argc; i++) {
     if (!strcmp(argv[i], "--folder") && i + 1 < argc) folder = argv[++i];
@@ -106,11 +108,17 @@ int main(int argc, char **argv) {
     }
     else if (!strcmp(argv[i], "--denoise")) { denoise = true; if (number(i + 1)) denoiseIterations = atoi(argv[++i]); }
     else if (!strcmp(argv[i], "--split")) split = true;
+    else if (!strcmp(argv[i], "--guide-bounces") && i + 1 < argc) guideBounces = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--temporal")) { temporal = true; if (number(i + 1)) maxHistory = (float)atof(argv[++i]); }
   }
   if (useGI != adaptive || ((denoise || temporal || split) && !useGI)) {
     std::fprintf(stderr, "error: --gi needs --adaptive and --adaptive needs --gi; --denoise, --temporal and --split need both\n"
                          "usage: %s scene.crtscene out_prefix --gi SAMPLE_SIZE --adaptive THRESHOLD MIN MAX [--denoise [ITERATIONS]] [--temporal [MAX_HISTORY]] [--split]\n", argv[0]);
+    return 2;
+  }
+  if (guideBounces >= 0 && (!denoise || guideBounces > 63)) {
+    std::fprintf(stderr, "error: --guide-bounces needs --denoise and a value of 0..63\n"
+                         "usage: %s scene.crtscene out_prefix --gi SAMPLE_SIZE --adaptive THRESHOLD MIN MAX --denoise [ITERATIONS] [--temporal [MAX_HISTORY]] --guide-bounces B\n", argv[0]);
     return 2;
   }
   try {
@@ -120,6 +128,7 @@ int main(int argc, char **argv) {
     tracer.setFramesInFlight(inFlight ? inFlight : 1);
     const unsigned W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
     crt::RenderOptions options(crt::BVHBucketsThreadPool, depth, useGI, giSamples, 1);
+    if (guideBounces > 0) tracer.setGuideBounces((unsigned)guideBounces);
     if (useGI) tracer.setGISeed(seed);  // frame k uses seed + k: renderAdaptive takes the next one
     Writers writers(writeFiles ? (nWriters ? nWriters : 1) : 0, W, H);
     const float DEG_CHANGE = 360.0f / (FPS * SECONDS);

@@ -22,9 +22,11 @@ int main(int argc, char **argv) {
                  "        --progressive: the same frame K samples a call, in memory that does not depend on RAYS_PER_PIXEL)\n"
                  "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL --adaptive THRESHOLD MIN MAX [--counts FILE]]   (every pixel is shot until the rule of\n"
                  "        crt_hip.h's crt_adaptive stops it, MIN .. MAX times; RAYS_PER_PIXEL is not read; --counts: the samples per pixel as a P2 PGM)\n"
-                 "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL --adaptive THRESHOLD MIN MAX --denoise [ITERATIONS] [--split]]   (out.ppm is that frame through\n"
+                 "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL --adaptive THRESHOLD MIN MAX --denoise [ITERATIONS] [--split] [--guide-bounces B]]   (out.ppm is that frame through\n"
                  "        the variance-guided a-trous filter of crt_hip.h's crt_denoise, its defaults but for ITERATIONS, 0..8; --split: the filter acts\n"
-                 "        on the indirect light only and the direct light is added back, crt_hip.h's \"Split GI frames\"; it needs --adaptive)\n"
+                 "        on the indirect light only and the direct light is added back, crt_hip.h's \"Split GI frames\"; it needs --adaptive;\n"
+                 "        --guide-bounces B, 0..63: the filter runs under guides that follow mirrors and glass for up to B bounces, crt_hip.h's \"Chain guides\";\n"
+                 "        it needs --denoise)\n"
                  "       [--probe ROW COL]   (no render: the closest hit of that pixel's camera ray; out.ppm is not written)\n",
                  argv[0]);
     return 2;
@@ -42,6 +44,7 @@ int main(int argc, char **argv) {
   bool denoise = false;
   int denoiseIterations = -1;  // (-1: crt_denoise_defaults')
   bool split = false;
+  int guideBounces = -1;  // (-1: not given)
   bool probe = false;
   unsigned probeRow = 0, probeCol = 0;
   for (int i = 3; i < argc; i++) {
@@ -74,6 +77,7 @@ int main(int argc, char **argv) {
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoiseIterations = atoi(argv[++i]);
     }
     else if (!strcmp(argv[i], "--split")) split = true;
+    else if (!strcmp(argv[i], "--guide-bounces") && i + 1 < argc) guideBounces = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--probe") && i + 2 < argc) { probe = true; probeRow = (unsigned)atoi(argv[++i]); probeCol = (unsigned)atoi(argv[++i]); }
   }
   if (progressive && (!useGI || devices.size() > 0)) {
@@ -98,6 +102,11 @@ int main(int argc, char **argv) {
                  argv[0]);
     return 2;
   }
+  if (guideBounces >= 0 && (!denoise || guideBounces > 63)) {
+    std::fprintf(stderr, "error: --guide-bounces needs --denoise and a value of 0..63\nusage: %s scene.crtscene out.ppm --gi GI_SAMPLE_SIZE RAYS_PER_PIXEL --adaptive THRESHOLD MIN MAX --denoise [ITERATIONS] --guide-bounces B\n",
+                 argv[0]);
+    return 2;
+  }
   try {
     crt::SceneParser parser;
     crt::Scene scene = parser.parseScene(scenePath, folder);
@@ -118,6 +127,7 @@ int main(int argc, char **argv) {
       return 0;
     }
     crt::RenderOptions options((crt::RenderOptimization)mode, depth, useGI, giSamples, raysPerPixel);
+    if (guideBounces > 0) tracer.setGuideBounces((unsigned)guideBounces);
     tracer.setGISeed(seed);  // frame r of this run uses seed + r (the reference's GI frames all differ: clock() ^ thread id)
     double best = 1e30;
     for (int r = 0; r < repeat; r++) {

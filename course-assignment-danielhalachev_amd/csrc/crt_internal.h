@@ -9,6 +9,7 @@
 //   crt_denoise.hip   the denoiser's primitives: the variance of the fold's state, the a-trous filter on first-hit guides
 //   crt_temporal.hip  the temporal accumulation's primitive: the last frame's history reprojected and merged with the fold's state
 //   crt_split.hip     the split GI frames' primitives: a sample's direct light kept, the fold of the two parts, putting them back together
+//   crt_guides.hip    the chain guides' kernel launch and work-area layout: filter guides that follow mirrors and glass
 //   crt_testhooks.hip unit-test hooks (libcrt_hip_test.so only)
 #pragma once
 
@@ -130,6 +131,7 @@ struct crt_ctx {
     crt_stats stats{};
     int num_cus = 0;
     struct crt_query_state *query = nullptr;   // crt_query.hip: the ray queries' scratch and statistics, created by the first query
+    uint32_t guide_bounces = 0;                // crt_set_guide_bounces: > 0, the frame calls' spatial filter runs under chain guides
     uint64_t query_host_rays = QUERY_HOST_RAYS, query_launch_rays = QUERY_LAUNCH_RAYS, shoot_pass_rays = SHOOT_PASS_RAYS;   // ... and its chunk sizes
 };
 
@@ -187,6 +189,20 @@ CRT_INTERNAL int split_launch_fold(crt_ctx *ctx, const float *d_rgb, const float
                                    float *d_dsum, float *d_rsum, float *d_rsq, hipStream_t stream);
 CRT_INTERNAL int split_launch_recombine(crt_ctx *ctx, const float *d_filtered, const float *d_dsum, const uint32_t *d_counts, uint64_t n_pixels,
                                         float *d_out, hipStream_t stream);
+// ---- crt_guides.hip: the chain guides' work area and the launch behind a level's trace, for crt_guide_rays* (crt_query.hip)
+constexpr uint32_t GUIDE_COUNT_WORDS = 128;   // the head of the work area: entries appended to level k at [k]
+struct GuideWork {
+    uint32_t *count;
+    crt_hit *hits;          // the level's closest hits, by list position
+    crt_ray *rays[2];       // two lists: level k reads list k & 1 and appends to the other
+    uint32_t *pixel[2];
+    float *tsum[2];
+    uint32_t *mesh0[2];
+};
+CRT_INTERNAL GuideWork guides_work(void *d_work, uint64_t n);
+CRT_INTERNAL int guides_launch_step(crt_ctx *ctx, const GuideWork &W, const crt_ray *d_rays, uint32_t n, uint32_t level, uint32_t max_bounces,
+                                    float reflection_bias, float refraction_bias, crt_hit *d_out_hits, uint8_t *d_out_status, crt_ray *d_out_last_rays,
+                                    hipStream_t stream);
 // ---- crt_abi.hip
 CRT_INTERNAL uint64_t coverage_items(uint32_t width, uint32_t height, const crt_rect *rects, uint32_t n_rects, std::vector<WorkItem> &items);
 CRT_INTERNAL void launch_unpack_items(const float *packed, const WorkItem *items, uint32_t n_items, float *frame, uint32_t width, uint32_t height,

@@ -244,6 +244,15 @@ struct crt_query_state {
     DeviceArray<float4> den_work;
     DeviceArray<uint8_t> den_q8;
     bool den_guides = false;
+    // crt_set_guide_bounces > 0: beside them the chain guides of the same rays (crt_guide_rays_device's records), which the spatial filter
+    // then runs under, and that call's work area; traced and dropped with den_hits.  The biases are those of the frame's pass 0
+    DeviceArray<crt_hit> den_chain;
+    DeviceArray<float4> guide_work;
+    float prog_reflection_bias = 0, prog_refraction_bias = 0;
+    // crt_guide_rays: the host variant's device copies of the status bytes and terminal rays, and its work area
+    DeviceArray<uint8_t> g_status;
+    DeviceArray<crt_ray> g_last;
+    DeviceArray<float4> g_work;
     // crt_render_accumulated*: the frame's serial number (it advances wherever den_guides is dropped); a History -- two slots with the pose
     // of the frame that wrote each: slot[cur] is `current`, slot[cur ^ 1] `previous`; the serial `current` was written at; the frames
     // merged since crt_history_reset --; and the merged colour, variance and valid-tap counts.  There are two histories: hist[0] holds the
@@ -1050,6 +1059,112 @@ extern "C" int crt_shoot_rays_gi_enqueue(crt_ctx *ctx, const crt_ray *d_rays, co
 
 extern "C" uint64_t crt_query_scratch_generation(const crt_ctx *ctx) { return ctx && ctx->query ? ctx->query->generation : 0; }
 
+// ---- chain guides (crt_guides.hip, csrc/kernel_guides.h): a pixel's chain of closest-hit walks through mirrors and glass.  For level
+// k = 0 .. max_bounces: one trace of the live chains (query_launches; behind level 0 the DEVN build, sized for n and reading the list's
+// length from the work area's word k), then guide_step, which finalises a pixel or appends its next segment.  Like shoot_enqueue the call
+// waits for nothing: a level that ran dry costs empty launches.
+
+// what every guide call asks beyond query_entry's check (NULL arrays, ray_type); nothing is enqueued on a refusal
+static int guide_check(crt_ctx *ctx, const char *what, const uint64_t n, const uint32_t max_bounces) {
+    const auto refuse = [&](const std::string &why) {
+        ctx->error = std::string(what) + ": " + why;
+        return (int)CRT_ERR_INVALID;
+    };
+    if (max_bounces > 63u) return refuse("max_bounces is " + std::to_string(max_bounces) + ", at most 63 (the status byte's bits 0-5)");
+    if (n > SHOOT_LEVEL_RAYS) return refuse("n = " + std::to_string(n) + " > 2^30 rays; split the rays over several calls");
+    const uint64_t meshes = ctx->scene.n_meshes;
+    if (meshes * (meshes + 1) >= 0xFFFFFFFFull) return refuse("n_meshes * (n_meshes + 1) >= 2^32 - 1: the mesh tag does not fit 32 bits");
+    return CRT_OK;
+}
+
+// One call's launches on `stream`; d_work holds crt_guide_work_bytes(n) bytes.  What waits, allocates or records an event happens before
+// the first launch and never inside a capture, which is refused what it would need of that (shoot_enqueue's rule).
+static int guide_enqueue(crt_ctx *ctx, const crt_ray *d_rays, const uint64_t n, const uint32_t ray_type, const float reflection_bias,
+                         const float refraction_bias, const uint32_t max_bounces, crt_hit *d_out_hits, uint8_t *d_out_status, crt_ray *d_out_last_rays,
+                         void *d_work, hipStream_t stream, const char *what, const bool first = true) {
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    CRT_HIP_CHECK(ctx, hipStreamIsCapturing(stream, &capture));
+    const bool capturing = capture != hipStreamCaptureStatusNone;
+    const auto refuse = [&](const char *why) {
+        ctx->error = std::string(what) + ": the stream is being captured and " + why;
+        return CRT_ERR_INVALID;
+    };
+    int rc;
+    if (capturing) {
+        if (capture != hipStreamCaptureStatusActive) return refuse("the capture is invalidated");
+        if (ctx->pending) return refuse("a crt_render_async frame is pending: the call would have to wait for it (crt_wait before the capture)");
+        if (!ctx->query || !ctx->query->pin) return refuse("the query scratch would have to be made (the context has none yet): make the same call once before the capture");
+        if (ctx->query->call.open) return refuse("an open call would have to be harvested, which waits (crt_get_query_stats before the capture)");
+        if (uses_filter(ctx) && ctx->query->list.cap < std::min(n, ctx->query_launch_rays))
+            return refuse("the query scratch would have to grow for these rays: make the same call once before the capture");
+    } else if ((rc = query_begin(ctx, stream, CALL_QUERY)) || (rc = query_list_reserve(ctx, n))) return rc;
+    crt_query_state *q = ctx->query;
+    const GuideWork W = guides_work(d_work, n);
+    // every word starts at zero: the queries' cursors and totals, and the levels' counts in the work area (`first` false, a later round
+    // trip of the host variant: the totals stay and the call's statistics add up, as query_run's do)
+    if ((rc = first ? clear_words(ctx, q->words.p, QW_WORDS, W.count, GUIDE_COUNT_WORDS, true, stream)
+                    : clear_words(ctx, W.count, GUIDE_COUNT_WORDS, nullptr, 0, true, stream)))
+        return rc;
+    if (!capturing && (rc = call_open(ctx, CALL_QUERY, n, stream, first))) return rc;
+    for (uint32_t g = 0; g <= max_bounces; g++) {
+        // children are REFLECTION or REFRACTION rays, which walk alike: only the caller's own ray can be PRIMARY (Ray.cpp:13)
+        QueryCall trace = closest_call(g == 0 ? d_rays : W.rays[g & 1u], n, g == 0 ? ray_type : (uint32_t)CRT_RAY_REFLECTION, W.hits);
+        trace.d_count = g == 0 ? nullptr : W.count + g;
+        trace.kernels_only = true;
+        if ((rc = query_launches(ctx, trace, stream, g == 0 && first)) ||
+            (rc = guides_launch_step(ctx, W, d_rays, (uint32_t)n, g, max_bounces, reflection_bias, refraction_bias, d_out_hits, d_out_status,
+                                     d_out_last_rays, stream)))
+            return rc;
+    }
+    if (capturing) return CRT_OK;   // (a captured call opens and closes nothing)
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->pin->words, q->words.p, QW_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    return call_close(ctx, CALL_QUERY, stream);
+}
+
+extern "C" int crt_guide_rays_device(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, uint32_t max_bounces,
+                                     crt_hit *d_out_hits, uint8_t *d_out_status, crt_ray *d_out_last_rays, void *d_work, void *stream) {
+    const char *what = "crt_guide_rays_device";
+    // (options are not handed to the check: use_gi may be left set, nothing of the GI build is involved)
+    return query_entry(ctx, n, {what, {d_rays, options, d_out_hits}, ray_type}, [&] {
+        if (int rc = guide_check(ctx, what, n, max_bounces)) return rc;
+        if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15u)) {
+            ctx->error = std::string(what) + ": d_work is NULL or not aligned to 16 bytes";
+            return (int)CRT_ERR_INVALID;
+        }
+        return guide_enqueue(ctx, d_rays, n, ray_type, options->reflection_bias, options->refraction_bias, max_bounces, d_out_hits, d_out_status,
+                             d_out_last_rays, d_work, (hipStream_t)stream, what);
+    });
+}
+
+// the host variant: copy in, run, copy out, query_host_rays at a time, through device copies that are kept for the next call
+extern "C" int crt_guide_rays(crt_ctx *ctx, const crt_ray *rays, uint64_t n, uint32_t ray_type, const crt_options *options, uint32_t max_bounces,
+                              crt_hit *out_hits, uint8_t *out_status, crt_ray *out_last_rays) {
+    const char *what = "crt_guide_rays";
+    return query_entry(ctx, n, {what, {rays, options, out_hits}, ray_type}, [&]() -> int {
+        int rc;
+        if ((rc = guide_check(ctx, what, n, max_bounces)) || (rc = query_begin(ctx, ctx->stream, CALL_QUERY))) return rc;
+        crt_query_state *q = ctx->query;
+        const uint64_t cap = std::min(n, ctx->query_host_rays);
+        if ((rc = reserve_all(ctx, q->s_rays, cap, q->s_hits, cap, q->g_status, cap, q->g_last, cap, q->g_work,
+                              (crt_guide_work_bytes(cap) + sizeof(float4) - 1) / sizeof(float4))))
+            return rc;
+        for (uint64_t done = 0; done < n; done += ctx->query_host_rays) {
+            const uint64_t m = std::min(n - done, ctx->query_host_rays);
+            CRT_HIP_CHECK(ctx, hipMemcpyAsync(q->s_rays.p, rays + done, m * sizeof(crt_ray), hipMemcpyHostToDevice, ctx->stream));
+            if ((rc = guide_enqueue(ctx, q->s_rays.p, m, ray_type, options->reflection_bias, options->refraction_bias, max_bounces, q->s_hits.p,
+                                    q->g_status.p, q->g_last.p, q->g_work.p, ctx->stream, what, done == 0)))
+                return rc;
+            CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_hits + done, q->s_hits.p, m * sizeof(crt_hit), hipMemcpyDeviceToHost, ctx->stream));
+            if (out_status) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_status + done, q->g_status.p, m, hipMemcpyDeviceToHost, ctx->stream));
+            if (out_last_rays) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_last_rays + done, q->g_last.p, m * sizeof(crt_ray), hipMemcpyDeviceToHost, ctx->stream));
+            CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+            if ((rc = query_harvest(ctx))) return rc;
+        }
+        return (int)CRT_OK;
+    });
+}
+
 // ---- progressive GI frames (csrc/kernel_progressive.h): the frame's left fold over a pixel's samples, cut into sample passes.
 
 static QueryCamera camera_of(const crt_ctx *ctx) {
@@ -1312,6 +1427,8 @@ static int render_adaptive(crt_ctx *ctx, const char *what, const bool split, con
             q->prog_is_split = split;
             q->new_frame();            // (a new frame: crt_render_denoised traces its guides again)
             q->prog_adaptive = *adaptive;
+            q->prog_reflection_bias = options->reflection_bias;
+            q->prog_refraction_bias = options->refraction_bias;
             q->prog_active = pixels;
         }
         const uint64_t n = q->prog_active;
@@ -1399,6 +1516,8 @@ static FoldState fold_state(const crt_query_state *q, const bool split) {
 
 // the frame's guides, traced at the frame's first call of either kind: the first hits of the camera's centre rays, as CRT_RAY_PRIMARY (the
 // rays of a pass are scratch between passes); den_hits is reserved
+// crt_set_guide_bounces > 0: and, behind them, the chain guides of the same rays, for the spatial filter alone (the temporal stage keeps the
+// first hits: with a still camera "as if painted" is exact)
 static int frame_guides(crt_ctx *ctx, const uint64_t pixels) {
     crt_query_state *q = ctx->query;
     if (q->den_guides) return CRT_OK;
@@ -1406,9 +1525,29 @@ static int frame_guides(crt_ctx *ctx, const uint64_t pixels) {
     if ((rc = crt_camera_rays_device(ctx, q->prog_rays.p, ctx->stream)) ||
         (rc = query_run(ctx, closest_call(q->prog_rays.p, pixels, CRT_RAY_PRIMARY, q->den_hits.p), ctx->stream, true)))
         return rc;
+    if (ctx->guide_bounces) {
+        const char *what = "crt_set_guide_bounces";
+        if ((rc = guide_check(ctx, what, pixels, ctx->guide_bounces)) ||
+            (rc = reserve_all(ctx, q->den_chain, pixels, q->guide_work, (crt_guide_work_bytes(pixels) + sizeof(float4) - 1) / sizeof(float4))) ||
+            (rc = guide_enqueue(ctx, q->prog_rays.p, pixels, CRT_RAY_PRIMARY, q->prog_reflection_bias, q->prog_refraction_bias, ctx->guide_bounces,
+                                q->den_chain.p, nullptr, nullptr, q->guide_work.p, ctx->stream, what)))
+            return rc;
+    }
     q->den_guides = true;
     return CRT_OK;
 }
+// the guides of the spatial filter stage
+static const crt_hit *filter_guides(const crt_ctx *ctx) { return ctx->guide_bounces ? ctx->query->den_chain.p : ctx->query->den_hits.p; }
+
+extern "C" int crt_set_guide_bounces(crt_ctx *ctx, uint32_t max_bounces) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = guide_check(ctx, "crt_set_guide_bounces", 0, max_bounces)) return rc;
+    if (max_bounces == ctx->guide_bounces) return CRT_OK;
+    ctx->guide_bounces = max_bounces;
+    if (ctx->query) ctx->query->den_guides = false;   // the kept guides alone: the history and the frame's serial stay
+    return CRT_OK;
+}
+extern "C" uint32_t crt_guide_bounces(const crt_ctx *ctx) { return ctx ? ctx->guide_bounces : 0u; }
 
 // crt_render_denoised and, `split`, crt_render_denoised_split: the rest is filtered and the direct part's mean added back untouched
 static int render_denoised(crt_ctx *ctx, const char *what, const bool split, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8) {
@@ -1425,7 +1564,7 @@ static int render_denoised(crt_ctx *ctx, const char *what, const bool split, con
         return rc;
     const FoldState state = fold_state(q, split);
     if ((rc = denoise_launch_variance(ctx, state.sum, state.sq, q->prog_counts.p, pixels, q->den_mean.p, q->den_var.p, ctx->stream)) ||
-        (rc = denoise_launch(ctx, denoise, ctx->width, ctx->height, q->den_mean.p, q->den_var.p, q->den_hits.p, q->den_out.p, nullptr, q->den_work.p,
+        (rc = denoise_launch(ctx, denoise, ctx->width, ctx->height, q->den_mean.p, q->den_var.p, filter_guides(ctx), q->den_out.p, nullptr, q->den_work.p,
                              ctx->stream)) ||
         (split && (rc = split_launch_recombine(ctx, q->den_out.p, q->split_dsum.p, q->prog_counts.p, pixels, q->den_out.p, ctx->stream))))
         return rc;
@@ -1487,7 +1626,7 @@ static int render_accumulated(crt_ctx *ctx, const char *what, const bool split, 
     memcpy(hist.pose[cur].matrix, ctx->frame.cam, sizeof(hist.pose[cur].matrix));
     float *result = q->acc_rgb.p;
     if (denoise) {
-        if ((rc = denoise_launch(ctx, denoise, ctx->width, ctx->height, q->acc_rgb.p, q->acc_var.p, q->den_hits.p, q->den_out.p, nullptr, q->den_work.p,
+        if ((rc = denoise_launch(ctx, denoise, ctx->width, ctx->height, q->acc_rgb.p, q->acc_var.p, filter_guides(ctx), q->den_out.p, nullptr, q->den_work.p,
                                  ctx->stream)))
             return rc;
         result = q->den_out.p;

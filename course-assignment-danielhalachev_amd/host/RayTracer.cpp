@@ -195,6 +195,28 @@ std::vector<crt_hit> RayTracer::traceRays(const std::vector<crt_ray> &rays, unsi
   return hits;
 }
 
+std::vector<crt_hit> RayTracer::guideRays(const std::vector<crt_ray> &rays, const RenderOptions &renderOptions, unsigned int maxBounces, unsigned int rayType,
+                                          std::vector<unsigned char> *status, std::vector<crt_ray> *lastRays) {
+  if (multi) throw std::runtime_error("guideRays: not available on a multi-device tracer");
+  std::vector<crt_hit> hits(rays.size());
+  if (status) status->assign(rays.size(), 0);
+  if (lastRays) lastRays->assign(rays.size(), crt_ray{});
+  crt_options options{};
+  options.reflection_bias = renderOptions.REFLECTION_BIAS;
+  options.refraction_bias = renderOptions.REFRACTION_BIAS;
+  if (crt_guide_rays(ctx, rays.data(), rays.size(), rayType, &options, maxBounces, hits.data(), status ? status->data() : nullptr,
+                     lastRays ? lastRays->data() : nullptr) != CRT_OK)
+    throw std::runtime_error(std::string("guideRays failed: ") + crt_last_error(ctx));
+  return hits;
+}
+
+void RayTracer::setGuideBounces(unsigned int maxBounces) {
+  if (multi) throw std::runtime_error("setGuideBounces: not available on a multi-device tracer");
+  if (crt_set_guide_bounces(ctx, maxBounces) != CRT_OK) throw std::runtime_error(std::string("setGuideBounces failed: ") + crt_last_error(ctx));
+}
+
+unsigned int RayTracer::guideBounces() const { return multi ? 0u : crt_guide_bounces(ctx); }
+
 std::vector<unsigned char> RayTracer::occludedRays(const std::vector<crt_ray> &rays, const std::vector<float> &maxDistance) {
   if (multi) throw std::runtime_error("occludedRays: not available on a multi-device tracer");
   if (maxDistance.size() != rays.size()) throw std::runtime_error("occludedRays: one max distance per ray");

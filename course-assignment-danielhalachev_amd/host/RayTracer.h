@@ -117,6 +117,18 @@ class RayTracer {
   std::vector<float> shootRaysGI(const std::vector<crt_ray> &rays, const std::vector<uint32_t> &keys, const RenderOptions &renderOptions,
                                  unsigned int rayType = CRT_RAY_REFLECTION, crt_shoot_stats *stats = nullptr);
 
+  // ---- chain guides (crt_hip.h: "Chain guides", crt_guide_rays): for every ray the guide record of the surface it shows -- the chain of
+  // closest hits through reflective and refractive meshes to the first diffuse or constant surface, a miss or maxBounces (<= 63) --, with
+  // the path length as t and a tagged mesh; the biases come from renderOptions.  *status: a byte a ray (bits 0-5 the bounces, bit 7 cut),
+  // *lastRays: the terminal segment's ray, when they are given.  Single-device tracers only.
+  std::vector<crt_hit> guideRays(const std::vector<crt_ray> &rays, const RenderOptions &renderOptions, unsigned int maxBounces,
+                                 unsigned int rayType = CRT_RAY_PRIMARY, std::vector<unsigned char> *status = nullptr,
+                                 std::vector<crt_ray> *lastRays = nullptr);
+  // 0 (the default): renderDenoised and renderAccumulated filter under first-hit guides; above 0: under the chain guides of the camera's
+  // centre rays (crt_set_guide_bounces); the temporal stage keeps the first hits
+  void setGuideBounces(unsigned int maxBounces);
+  unsigned int guideBounces() const;
+
   // ---- progressive GI frames (crt_hip.h: crt_render_progressive): render()'s USE_GI frame with renderOptions.RAYS_PER_PIXEL rays per
   // pixel, samplesPerCall samples a call, in memory that does not depend on RAYS_PER_PIXEL; the frame's seed is taken as render() takes
   // it.  EVERY pixel of the frame is rendered: where render()'s bucket grid covers the frame (RayTracer.cpp:141-152 can leave edge rows

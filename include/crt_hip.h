@@ -671,7 +671,8 @@ uint64_t crt_progressive_active(const crt_ctx *ctx);
  *   iterations == 0 copies input to output.  A NaN that arises from overflow is whatever these lines give.
  * Known limits.  There is no albedo demodulation, because the library has no albedo query: texture detail inside one mesh is protected by
  *   the colour weight alone -- in THIS call; crt_render_denoised_split ("Split GI frames", below) filters the indirect light only and
- *   adds the direct light, which carries the texels, back untouched.  Reflections in a flat mirror are guided by the mirror's own plane.  With count == 1 every variance is 0, so
+ *   adds the direct light, which carries the texels, back untouched.  Reflections in a flat mirror are guided by the mirror's own plane
+ *   while crt_guide_bounces(ctx) is 0, the default: "Chain guides", below, gives such pixels the guide of the surface they show.  With count == 1 every variance is 0, so
  *   the filter hardly smooths: use at least 2 samples.
  * crt_denoise: size must be sizeof(crt_denoise) = 24, iterations <= 8, normal_squarings <= 16, sigma_colour and sigma_plane >= 0 and finite,
  *   floor > 0 and finite: anything else is CRT_ERR_INVALID, with nothing enqueued.  crt_denoise_defaults: 4, 5, 2.0f, 0.02f, 1e-6f.
@@ -781,7 +782,7 @@ int crt_render_denoised(crt_ctx *ctx, const crt_denoise *denoise, float *out_rgb
  *   inverse is the transpose.  A non-finite current sample gives a non-finite record; the next frame skips such a record as a tap, so a NaN
  *   lives for one frame.
  * Known limits.  A miss pixel keeps no history.  A matrix that is not a rotation reprojects wrongly.  The geometry tests reject most of
- *   those taps, but not a slide within one plane.  Reflections are reprojected as if painted on the mirror.  The history holds the
+ *   those taps, but not a slide within one plane.  Reflections are reprojected as if painted on the mirror, with or without chain guides (below).  The history holds the
  *   unfiltered moments: the filtered colour is not fed back.  Texture detail is reprojected and filtered with the noise in this call;
  *   crt_render_accumulated_split ("Split GI frames", below) does both to the indirect light only.
  * crt_temporal: size must be sizeof(crt_temporal) = 16, max_history > 0 and finite, normal_min finite, sigma_plane >= 0 and finite:
@@ -882,7 +883,8 @@ uint32_t crt_history_frames(const crt_ctx *ctx);
  *   poses, under the same serial rule.  The two calls do not disturb each other's history.  crt_history_reset drops both pairs;
  *   crt_history_frames_split counts this pair's frames, crt_history_frames the other's, as before.
  * All three leave the frame readable, as their unsplit siblings do: a frame can be denoised after any pass and continued.
- * Known limits.  Mirrors and glass are all "rest" and are filtered as before.  A sample with an infinite channel gives inf - inf = NaN in
+ * Known limits.  Mirrors and glass are all "rest" and are filtered as before -- under first-hit guides, or under chain guides (below) with
+ *   crt_set_guide_bounces.  A sample with an infinite channel gives inf - inf = NaN in
  *   the rest, and such a pixel passes through the filter as NaN pixels do.  The output is filtered + dmean by the rule: with 0 iterations
  *   it is not bit-equal to the unsplit mean. */
 int crt_shoot_rays_gi_split(crt_ctx *ctx, const crt_ray *rays, const uint32_t *keys, uint64_t n, uint32_t ray_type,
@@ -900,6 +902,72 @@ int crt_render_denoised_split(crt_ctx *ctx, const crt_denoise *denoise, float *o
 int crt_render_accumulated_split(crt_ctx *ctx, const crt_temporal *temporal, const crt_denoise *denoise /* NULL: no spatial filter */,
                                  float *out_rgb, uint8_t *out_rgb8, uint8_t *out_valid);
 uint32_t crt_history_frames_split(const crt_ctx *ctx);
+
+/* ---- Chain guides: filter guides that follow mirrors and glass to the surface they show.  The a-trous filter takes its edge-stopping
+ * guides from a crt_hit per pixel.  The first hit of a mirror or glass pixel is the wrong guide: every pixel of a flat mirror has the same
+ * mesh, normal and plane, so only the colour weight separates the surfaces the mirror shows.  A chain guide is the record of the first
+ * diffuse (or constant) surface the pixel's ray reaches through reflective and refractive meshes.  It is additive: a new way to produce
+ * guide records; crt_denoise_device and crt_temporal_device take them as they take any crt_hit array.  Kernel: csrc/kernel_guides.h
+ * (guide_step), launched by csrc/crt_guides.hip behind the ray queries' walks; tests/guide_sets.py restates the rule.  Single-device
+ * contexts only.  No frame, radiance, denoise or temporal kernel is involved.
+ *
+ * The rule.  Every float operation is float32 with one rounding.
+ * Segments.  A pixel's chain starts with the caller's ray, AS GIVEN (crt_trace_rays*' rule: nothing is normalised), traced as the caller's
+ *   ray_type: segment 0.  After segment k with closest hit h_k the hit's material decides:
+ *     a REFLECTIVE mesh continues with the ray calculateReflection shoots (RayTracer.cpp:366-367);
+ *     a REFRACTIVE mesh continues with the transmission ray calculateRefraction shoots, and under total internal reflection with the
+ *       reflection ray instead.
+ *   These are the children crt_shoot_rays* shoots -- one device function computes them for both, mirror_glass_children of
+ *   csrc/kernel_common.h, from segment k's direction as it was traced, h_k's point and normal, options->reflection_bias and
+ *   options->refraction_bias --, normalised once more as the child's shootRay entry normalises them (RayTracer.cpp:420).  Reflection
+ *   children are CRT_RAY_REFLECTION rays, transmission children CRT_RAY_REFRACTION rays.  Only CRT_RAY_PRIMARY differs in a walk (Ray.cpp:13), so
+ *   one launch traces a level's children of both kinds, as CRT_RAY_REFLECTION -- as the levels of crt_shoot_rays* are traced: the same bits.  For a caller's ray that
+ *   normalisation leaves as it is, segment k is therefore the ray shootRay traces at depth k along that branch.
+ * Termination.  The chain ends at a miss, at a diffuse or constant material, or when k == max_bounces.
+ * Guide record, a crt_hit.  point, normal, u, v, triangle and hit are the terminal hit's.  t is the PATH LENGTH ((t_0 + t_1) + ...) + t_k,
+ *   one float32 add per segment in that order, so that the filter's tol = sigma_plane * t scales with the whole path.  mesh is TAGGED: with
+ *   0 bounces it is the terminal mesh, otherwise terminal_mesh + n_meshes * (1 + mesh of h_0).  The tag keeps a wall seen in a mirror from
+ *   being averaged with the same wall seen directly, or seen in another mirror; equality is all the filter asks of mesh (the tag is below
+ *   0xFFFFFFFF, the filter's own mark of a miss).  A miss is all-zero with hit == 0, as crt_trace_rays* writes it, after any number of bounces.
+ * Status byte, one per ray.  Bits 0-5: the number of bounces k.  Bit 7: the chain was cut at max_bounces on a reflective or refractive
+ *   hit; the record is then that hit's.  max_bounces == 0 gives crt_trace_rays_device's records bit for bit.
+ * Known limits.  The Fresnel reflection on glass is guided by what lies BEHIND the glass: one guide a pixel follows one branch.  Temporal
+ *   reprojection is unchanged: crt_render_accumulated* reprojects first hits, mirrors as if painted (below).  A curved mirror spreads a
+ *   surface's taps thinly: neighbouring pixels end on different meshes or far-apart points, and few taps pass the mesh and plane tests.
+ * crt_guide_rays_device: the rule for d_rays[0 .. n) into d_out_hits (one crt_hit a ray), d_out_status (one byte; may be NULL) and
+ *   d_out_last_rays (the terminal segment's crt_ray, as it was traced; may be NULL).  d_work is the caller's, at least
+ *   crt_guide_work_bytes(n) bytes (512 + 120 a ray: the levels' counts, a level's hit records, two compact lists of ray, pixel, path
+ *   length and first mesh), aligned to 16 bytes; nothing may overlap it.  Of `options` reflection_bias and refraction_bias are read;
+ *   use_gi may be left set and is ignored.  CRT_ERR_INVALID, with nothing enqueued: max_bounces > 63, a NULL d_rays, options or d_out_hits,
+ *   a NULL or misaligned d_work, an unknown ray_type, n > 2^30, a scene with n_meshes * (n_meshes + 1) >= 0xFFFFFFFF.  n == 0 is CRT_OK
+ *   and touches nothing.
+ *   It only ENQUEUES on `stream` (a hipStream_t, NULL = default): no host wait, no allocation once the context's query scratch has seen a
+ *   call of this size, no readback the host waits for.  Each bounce is one trace of the live chains -- crt_trace_rays_device's launches,
+ *   sized for n and reading the list's length from a device word, as crt_shoot_rays_enqueue's levels do -- and one guide_step launch
+ *   behind it, which finalises a pixel's record or appends the chain's next segment to the next level's compact list (one ballot and one
+ *   atomic per wave; the capacity of every level is n, so nothing can overflow).  The order in a list may vary from run to run; no pixel's
+ *   result does.  4 (max_bounces + 1) launches; a level that ran dry costs empty launches, nothing else.
+ *   Inside a stream capture the call follows crt_shoot_rays_enqueue's rule: it makes no HIP call that synchronises, allocates or records an
+ *   event, and returns CRT_ERR_INVALID before it enqueues anything if it would need one (a pending crt_render_async frame, an open call, a
+ *   reroute list that would have to grow: make the same call once before the capture).  Outside a capture it is an open call like
+ *   crt_trace_rays_device: crt_get_query_stats gives rays = n and hits = the segments with a hit, over all levels.
+ * crt_guide_rays: the host variant; copies in, runs, copies out and returns when the results are there.  out_status and out_last_rays may
+ *   be NULL.
+ * crt_set_guide_bounces / crt_guide_bounces: the frame calls' setting, 0 by default; at 0 every call gives the bits it gave before.  With
+ *   a value above 0 the SPATIAL FILTER STAGE of crt_render_denoised, crt_render_accumulated and their _split forms runs under the chain
+ *   guides of the camera's centre rays (crt_camera_rays_device's rays as CRT_RAY_PRIMARY, with the biases of the frame's pass 0), traced
+ *   once a frame and kept beside the first-hit guides.  THE TEMPORAL STAGE KEEPS THE FIRST-HIT GUIDES: with a still camera "as if painted"
+ *   is exact, and a terminal point projected into the last camera would lose that.  Setting another value drops the frame's kept guides
+ *   (they are traced again by the next call); it does not drop the history and does not advance the frame's serial.  A value above 63 is
+ *   CRT_ERR_INVALID, and so is a scene whose mesh tag does not fit. */
+size_t crt_guide_work_bytes(uint64_t n);
+int crt_guide_rays(crt_ctx *ctx, const crt_ray *rays, uint64_t n, uint32_t ray_type, const crt_options *options, uint32_t max_bounces,
+                   crt_hit *out_hits, uint8_t *out_status /* may be NULL */, crt_ray *out_last_rays /* may be NULL */);
+int crt_guide_rays_device(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, uint32_t max_bounces,
+                          crt_hit *d_out_hits, uint8_t *d_out_status /* may be NULL */,
+                          crt_ray *d_out_last_rays /* may be NULL: the terminal segment's crt_ray */, void *d_work, void *stream);
+int crt_set_guide_bounces(crt_ctx *ctx, uint32_t max_bounces);
+uint32_t crt_guide_bounces(const crt_ctx *ctx);
 
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
