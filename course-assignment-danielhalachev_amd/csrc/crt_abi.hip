@@ -83,7 +83,7 @@ static int render_enqueue(crt_ctx *ctx, const crt_options *o, const crt_rect *re
     if (rc) return rc;
     if (n_rects && !rects) { ctx->error = "rects is NULL"; return CRT_ERR_INVALID; }
     CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    query_progressive_reset(ctx);   // the colour buffer is this frame's from here on
+    giframe_reset(ctx);   // the colour buffer is this frame's from here on
     // coverage: the union of the clamped rectangles (RayTracer.cpp:84-85), as 8x8 tiles with lane masks
     bool same = !ctx->cached_is_partition && ctx->cached_rects.size() == n_rects && n_rects > 0 &&
                 memcmp(ctx->cached_rects.data(), rects, n_rects * sizeof(crt_rect)) == 0;
@@ -181,7 +181,7 @@ extern "C" int crt_render_tiles_device(crt_ctx *ctx, const crt_options *o, uint3
     if (rc) return rc;
     if (stride == 0 || !d_packed) { ctx->error = "bad tile partition"; return CRT_ERR_INVALID; }
     CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    query_progressive_reset(ctx);
+    giframe_reset(ctx);
     const uint32_t n = crt_packed_tile_count(ctx, first, stride);
     crt_rect key{first, stride, 0u, 0u};
     bool same = ctx->cached_is_partition && ctx->cached_rects.size() == 1 && memcmp(ctx->cached_rects.data(), &key, sizeof(key)) == 0;

@@ -1,5 +1,5 @@
 // crt_denoise.hip -- the denoiser's primitives (include/crt_hip.h: "Denoising"): crt_denoise_defaults, crt_denoise_work_bytes,
-// crt_sample_variance_device and crt_denoise_device, and their launches for crt_render_denoised (crt_query.hip, which owns the frame's
+// crt_sample_variance_device and crt_denoise_device, and their launches for crt_render_denoised (crt_giframe.hip, which owns the frame's
 // state).  Kernels: csrc/kernel_denoise.h; the rule: csrc/denoise_rule.h.  Both device calls only enqueue: no wait, no allocation, no
 // readback.
 #include "crt_internal.h"

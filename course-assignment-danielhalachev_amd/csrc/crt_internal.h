@@ -5,7 +5,9 @@
 //   crt_abi.hip       the render entry points, tiles, statistics
 //   crt_multi.hip     one scene on several devices behind one call
 //   crt_query.hip     the queries for what the caller supplies, behind one call path: ray queries (closest hit / occlusion, the camera's rays),
-//                     direct lighting of hit records and points, radiance queries; their scratch and statistics
+//                     direct lighting of hit records and points, radiance queries, chain guides; their scratch and statistics
+//   crt_giframe.hip   the GI frame calls: progressive, adaptive, denoised, accumulated and split frames on the context's colour buffer; the
+//                     frame's state and the histories (the rules: giframe_rule.h)
 //   crt_denoise.hip   the denoiser's primitives: the variance of the fold's state, the a-trous filter on first-hit guides
 //   crt_temporal.hip  the temporal accumulation's primitive: the last frame's history reprojected and merged with the fold's state
 //   crt_split.hip     the split GI frames' primitives: a sample's direct light kept, the fold of the two parts, putting them back together
@@ -31,6 +33,7 @@
 
 #include "../../include/crt_hip.h"
 #include "crt_bvh.h"
+#include "call_wait.h"
 #include "kernel_common.h"
 
 #define CRT_INTERNAL __attribute__((visibility("hidden")))
@@ -131,8 +134,18 @@ struct crt_ctx {
     crt_stats stats{};
     int num_cus = 0;
     struct crt_query_state *query = nullptr;   // crt_query.hip: the ray queries' scratch and statistics, created by the first query
+    struct crt_giframe_state *giframe = nullptr;   // crt_giframe.hip: the GI frame under way and the histories, created by the first frame call
+    uint64_t scratch_generation = 0;           // crt_query_scratch_generation: every growth of an array of either (device_array.h)
     uint32_t guide_bounces = 0;                // crt_set_guide_bounces: > 0, the frame calls' spatial filter runs under chain guides
     uint64_t query_host_rays = QUERY_HOST_RAYS, query_launch_rays = QUERY_LAUNCH_RAYS, shoot_pass_rays = SHOOT_PASS_RAYS;   // ... and its chunk sizes
+    // the camera of the NEXT frame: crt_set_camera's last word, as crt_camera_rays_device and the frame calls' sample rays take it
+    QueryCamera camera() const {
+        QueryCamera cam;
+        memcpy(cam.pos, frame.cam_pos, sizeof(cam.pos));
+        memcpy(cam.m, frame.cam, sizeof(cam.m));
+        cam.width = width; cam.height = height;
+        return cam;
+    }
 };
 
 // constants that round 2 carried as crt_tuning fields (DESIGN.md section 7 has the measurements)
@@ -167,22 +180,38 @@ CRT_INTERNAL int ensure_items(crt_ctx *ctx, size_t n);
 CRT_INTERNAL int launch_render(crt_ctx *ctx, const crt_options *o, uint32_t n_items, float *d_out, uint32_t packed, hipStream_t stream);
 CRT_INTERNAL void note_overflow(crt_ctx *ctx);
 CRT_INTERNAL int fetch_counters(crt_ctx *ctx, const crt_options *o, uint64_t pixels);
-// ---- crt_query.hip
+// ---- crt_query.hip: what the GI frame calls (crt_giframe.hip) run of the queries, on the queries' scratch
 CRT_INTERNAL void query_destroy(crt_ctx *ctx);
-CRT_INTERNAL void query_progressive_reset(crt_ctx *ctx);   // crt_set_camera, crt_render*: crt_progressive_samples is 0 again
+CRT_INTERNAL int query_begin(crt_ctx *ctx, hipStream_t stream, CallKind kind);   // before a call on `stream`: the waiting rule, the scratch every query needs
+// the GI radiance calls' own check for a frame's rays (PRIMARY rays, the context's arrays); *pass: the rays of one pass
+CRT_INTERNAL int query_gi_check(crt_ctx *ctx, const char *what, const crt_options *options, uint64_t *pass);
+// crt_shoot_rays_gi_device (d_direct: crt_shoot_rays_gi_split_device) for n PRIMARY rays, `pass` at a time
+CRT_INTERNAL int query_gi_run(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t *d_keys, uint64_t n, const crt_options *options, float *d_rgb,
+                              float *d_direct, uint64_t pass, hipStream_t stream);
+CRT_INTERNAL int query_closest_run(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, crt_hit *d_hits, hipStream_t stream);   // crt_trace_rays_device, unchecked
+// the widest levels of the radiance passes since this call (query_level_headroom reads them)
+CRT_INTERNAL void query_level_peaks_reset(crt_ctx *ctx);
+CRT_INTERNAL int query_level_headroom(crt_ctx *ctx, const crt_options *o, uint64_t pass_rays);   // behind a frame's sample 0: room in the level arrays for later samples
+CRT_INTERNAL int guide_check(crt_ctx *ctx, const char *what, uint64_t n, uint32_t max_bounces);   // what every guide call asks beyond its arrays
+CRT_INTERNAL int guide_enqueue(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, float reflection_bias, float refraction_bias,
+                               uint32_t max_bounces, crt_hit *d_out_hits, uint8_t *d_out_status, crt_ray *d_out_last_rays, void *d_work, hipStream_t stream,
+                               const char *what, bool first = true);
+// ---- crt_giframe.hip
+CRT_INTERNAL void giframe_destroy(crt_ctx *ctx);
+CRT_INTERNAL void giframe_reset(crt_ctx *ctx);   // crt_set_camera, crt_render*: the frame under way has ended, crt_progressive_samples is 0 again
 CRT_INTERNAL int progressive_check(crt_ctx *ctx, const char *what, const uint32_t *d_pixels, uint64_t n);   // what the fold's primitives ask of (d_pixels, n)
-// ---- crt_denoise.hip: the denoiser's settings check and launches, for crt_render_denoised (crt_query.hip)
+// ---- crt_denoise.hip: the denoiser's settings check and launches, for crt_render_denoised (crt_giframe.hip)
 CRT_INTERNAL int denoise_check(crt_ctx *ctx, const char *what, const crt_denoise *d);
 CRT_INTERNAL int denoise_launch_variance(crt_ctx *ctx, const float *d_sum, const float *d_sq, const uint32_t *d_counts, uint64_t n, float *d_mean,
                                          float *d_var, hipStream_t stream);
 CRT_INTERNAL int denoise_launch(crt_ctx *ctx, const crt_denoise *d, uint32_t width, uint32_t height, const float *d_rgb, const float *d_var,
                                 const crt_hit *d_hits, float *d_out_rgb, float *d_out_var, void *d_work, hipStream_t stream);
-// ---- crt_temporal.hip: the temporal accumulation's settings check and launch, for crt_render_accumulated (crt_query.hip)
+// ---- crt_temporal.hip: the temporal accumulation's settings check and launch, for crt_render_accumulated (crt_giframe.hip)
 CRT_INTERNAL int temporal_check(crt_ctx *ctx, const char *what, const crt_temporal *t);
 CRT_INTERNAL int temporal_launch(crt_ctx *ctx, const crt_temporal *t, uint32_t width, uint32_t height, const crt_camera_pose *prev_pose,
                                  const crt_history_pixel *d_prev, const float *d_sum, const float *d_sq, const uint32_t *d_counts, const crt_hit *d_hits,
                                  crt_history_pixel *d_next, float *d_out_rgb, float *d_out_var, uint8_t *d_out_valid, hipStream_t stream);
-// ---- crt_split.hip: the split GI frames' launches, for the radiance passes and the *_split frame calls (crt_query.hip)
+// ---- crt_split.hip: the split GI frames' launches, for the radiance passes (crt_query.hip) and the *_split frame calls (crt_giframe.hip)
 CRT_INTERNAL int split_launch_keep_direct(crt_ctx *ctx, const uint8_t *d_status, const float *d_rgb, uint32_t n, uint32_t gi_sample_size, float *d_direct,
                                           hipStream_t stream);
 CRT_INTERNAL int split_launch_fold(crt_ctx *ctx, const float *d_rgb, const float *d_direct, const uint32_t *d_pixels, uint64_t n, uint32_t sample,

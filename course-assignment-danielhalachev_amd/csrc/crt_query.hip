@@ -5,36 +5,24 @@
 //   direct lighting    crt_shade_hits*, crt_light_points*: RayTracer::calculateDiffusion (RayTracer.cpp:300-330) for the caller's hit
 //                      records and points; kernels: csrc/kernel_shade.h
 //   radiance queries   crt_shoot_rays*: RayTracer::shootRay (RayTracer.cpp:419-451), a host loop over the launches of the other two, one
-//                      recursion level behind the other, with three small kernels of its own around them (csrc/kernel_radiance.h): at
-//                      the end of this file; crt_shoot_rays_gi*: the same loop for the GI build (a key per ray, sample rays at DIFFUSE
+//                      recursion level behind the other, with three small kernels of its own around them (csrc/kernel_radiance.h): behind
+//                      them in this file; crt_shoot_rays_gi*: the same loop for the GI build (a key per ray, sample rays at DIFFUSE
 //                      records, no mesh skipped by a shadow ray)
+//   chain guides       crt_guide_rays*: a ray's chain of closest-hit walks through mirrors and glass, level behind level without a wait;
+//                      the step kernel and the work area: crt_guides.hip
 // and their statistics (crt_get_query_stats, crt_get_shoot_stats).  A query reads the context's scene and nothing of its frames: the
-// scratch below is the queries' own.  The shape of the file:
+// scratch below is the queries' own.  The GI frame calls (crt_giframe.hip) run queries through the few functions crt_internal.h lists
+// and see nothing else of this file, nor this file anything of theirs.  The shape of the file:
 //   an entry point    query_entry: the preamble and the one argument check (query_check, told what the call needs by a CallCheck)
 //   a call            query_begin (the waiting rule: call_wait.h), then its launches between call_open and call_close
 //   its launches      query_launches: the filter / reroute pair of the call's kind from one table (PAIRS); clear_words clears every word
 //   a radiance pass   shoot_pass: shoot_down (level behind level), shoot_up, shoot_numbers.  The synchronous and the enqueue form part in
 //                     shoot_children (a level's room and size), clear_words and shoot_numbers -- and in shoot_up's choice of build --,
 //                     and nowhere in the level loop
-//   a progressive frame  crt_render_progressive, at the end of this file: a GI frame sample pass by sample pass -- the rays and keys of one
-//                     sample (crt_camera_sample_rays_device), shoot_run, one step of the pixel's fold (crt_accumulate_samples_device);
-//                     kernels: csrc/kernel_progressive.h
-//   an adaptive frame  crt_render_adaptive, behind it: the same loop over a pixel list that shrinks -- the step, the rule and the
-//                     compaction of crt_adaptive_step_device; kernels: csrc/kernel_adaptive.h, the rule: csrc/adaptive_rule.h
-//   a denoised frame  crt_render_denoised, last: the adaptive frame's state through the denoiser's primitives (crt_denoise.hip), guided by
-//                     the first hits of the camera's rays; it changes nothing of the frame
-//   an accumulated frame  crt_render_accumulated: that state merged with the last frame's history through the temporal primitive
-//                     (crt_temporal.hip), then through the denoiser's launches; the context's two history slots
-//   a split frame     crt_render_adaptive_split, crt_render_denoised_split, crt_render_accumulated_split: the three calls above with every
-//                     sample cut into its direct light and the rest (crt_split.hip, csrc/split_rule.h) -- the rest is what is filtered and
-//                     reprojected, the direct part is added back untouched; one body each for the split and the unsplit call
-#include "crt_internal.h"
+#include "device_array.h"
 #include "glibc_powf.h"
 #include "gi_random.h"
 #include "shoot_caps.h"
-#include "call_wait.h"
-
-static void query_scratch_changed(crt_ctx *ctx);   // (below crt_query_state)
 
 namespace {
 
@@ -47,8 +35,6 @@ namespace {
 #include "kernel_query.h"
 #include "kernel_shade.h"
 #include "kernel_radiance.h"
-#include "kernel_progressive.h"
-#include "kernel_adaptive.h"
 #pragma clang diagnostic pop
 
 // radiance queries: what a level may hold at most is SHOOT_LEVEL_RAYS (shoot_caps.h: a level is at most twice as wide as the one above
@@ -60,38 +46,6 @@ constexpr uint64_t SHOOT_GI_DEEPEST_RAYS = 1ull << 26;
 enum : int { SW_COUNT = 0, SW_DIFFUSE = MAX_GENERATIONS + 2, SW_WORDS = MAX_GENERATIONS + 4 };
 // ... and what comes back through pinned memory (uint64 slots): a level's count, level 0's hits, the DIFFUSE records, the rerouted ones
 enum : int { SH_COUNT = 0, SH_HITS0 = 1, SH_DIFFUSE = 2, SH_REROUTED = 3, SH_SLOTS = 4 };
-
-// A device array that only grows and is kept for the next call; freed with its owner.
-template <typename T>
-struct DeviceArray {
-    T *p = nullptr;
-    uint64_t cap = 0;
-    DeviceArray() = default;
-    DeviceArray(const DeviceArray &) = delete;
-    DeviceArray &operator=(const DeviceArray &) = delete;
-    ~DeviceArray() { release(); }
-    int reserve(crt_ctx *ctx, const uint64_t n) {
-        if (n <= cap) return CRT_OK;
-        if (p) CRT_HIP_CHECK(ctx, hipDeviceSynchronize());   // nothing may still be using the old array
-        release();
-        CRT_HIP_CHECK(ctx, hipMalloc((void **)&p, n * sizeof(T)));
-        cap = n;
-        query_scratch_changed(ctx);   // a graph captured from an enqueue call holds the old pointer (crt_query_scratch_generation)
-        return CRT_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-// reserve_all(ctx, a, n, b, m, ...): room for n elements in a, m in b, ...; the first failure ends it
-int reserve_all(crt_ctx *) { return CRT_OK; }
-template <typename T, typename... More>
-int reserve_all(crt_ctx *ctx, DeviceArray<T> &a, const uint64_t n, More &&...more) {
-    if (int rc = a.reserve(ctx, n)) return rc;
-    return reserve_all(ctx, more...);
-}
 
 // one recursion level of a radiance query: rays, their records, colours (level 0 writes the caller's array), status and nodes
 struct ShootLevel {
@@ -184,7 +138,6 @@ struct QueryPinned {
     uint32_t words[QW_WORDS];   // the words of the last call, copied behind its last launch
     uint64_t shoot[SH_SLOTS];   // SH_*
     crt_shoot_report report;    // crt_query_state::d_report, copied behind the last launch of an enqueue call
-    uint32_t adaptive_n;        // crt_render_adaptive: the next pass's list length, copied behind a pass's scatter
 };
 
 }  // namespace
@@ -218,59 +171,11 @@ struct crt_query_state {
     DeviceArray<crt_shoot_report> d_report;   // what radiance_report writes for the library's own statistics (outside a capture)
     DeviceArray<unsigned long long> d_hits0;  // level 0's hits: QW_HITS as the level's trace left it (the lighting launches add to that word)
     crt_shoot_report report{};                // of the last enqueue call outside a capture
-    uint64_t generation = 0;                  // crt_query_scratch_generation
-    // crt_render_progressive: the frame's H*W*3 sums, one sample's rays, keys and colours for every pixel, the samples folded in so far
-    DeviceArray<float> prog_sum, prog_rgb;
-    DeviceArray<crt_ray> prog_rays;
-    DeviceArray<uint32_t> prog_keys;
-    uint32_t prog_samples = 0;
-    // crt_render_adaptive: the frame above with one float and one count more per pixel, two pixel lists (this pass's and the next one's),
-    // the next list's length, the compaction's work area; which kind of frame is under way, its latched settings and its list
-    DeviceArray<float> prog_sq;
-    DeviceArray<uint32_t> prog_counts, prog_list[2], prog_next_n;
-    DeviceArray<unsigned long long> prog_work;
-    bool prog_is_adaptive = false;
-    // crt_render_adaptive_split: the adaptive frame is a SPLIT one (latched at pass 0) -- beside the fold's state the sums of the samples'
-    // direct parts and the first and second moment of the rest (csrc/split_rule.h), and one pass's direct parts beside prog_rgb
-    bool prog_is_split = false;
-    DeviceArray<float> split_direct, split_dsum, split_rsum, split_rsq;
-    crt_adaptive prog_adaptive{};
-    uint64_t prog_active = 0;   // entries of prog_list[prog_cur]; pass 0 has no list (every pixel)
-    int prog_cur = 0;
-    // crt_render_denoised: the guides (the first hits of the camera's centre rays, traced at a frame's first denoise call and kept until the
-    // frame is reset), the mean and variance of the fold's state, the denoised frame, the primitive's work area, the quantised frame
-    DeviceArray<crt_hit> den_hits;
-    DeviceArray<float> den_mean, den_var, den_out;
-    DeviceArray<float4> den_work;
-    DeviceArray<uint8_t> den_q8;
-    bool den_guides = false;
-    // crt_set_guide_bounces > 0: beside them the chain guides of the same rays (crt_guide_rays_device's records), which the spatial filter
-    // then runs under, and that call's work area; traced and dropped with den_hits.  The biases are those of the frame's pass 0
-    DeviceArray<crt_hit> den_chain;
-    DeviceArray<float4> guide_work;
-    float prog_reflection_bias = 0, prog_refraction_bias = 0;
     // crt_guide_rays: the host variant's device copies of the status bytes and terminal rays, and its work area
     DeviceArray<uint8_t> g_status;
     DeviceArray<crt_ray> g_last;
     DeviceArray<float4> g_work;
-    // crt_render_accumulated*: the frame's serial number (it advances wherever den_guides is dropped); a History -- two slots with the pose
-    // of the frame that wrote each: slot[cur] is `current`, slot[cur ^ 1] `previous`; the serial `current` was written at; the frames
-    // merged since crt_history_reset --; and the merged colour, variance and valid-tap counts.  There are two histories: hist[0] holds the
-    // moments of whole colours (crt_render_accumulated), hist[1] those of the rest (crt_render_accumulated_split), which must never meet
-    uint64_t frame_serial = 0;
-    struct History {
-        uint64_t serial = 0;
-        DeviceArray<crt_history_pixel> slot[2];
-        crt_camera_pose pose[2] = {};
-        int cur = 0;
-        bool has_cur = false, has_prev = false;
-        uint32_t frames = 0;
-        void reset() { has_cur = has_prev = false; frames = 0; }   // (the slots stay allocated: nothing reads them until a call has written one again)
-    } hist[2];
-    DeviceArray<float> acc_rgb, acc_var;
-    DeviceArray<uint8_t> acc_valid;
-    void new_frame() { den_guides = false; frame_serial++; }   // the guides and `current` are the ended frame's
-    uint64_t level_peak[MAX_GENERATIONS] = {};   // the widest level g of a pass since a progressive frame's sample 0 began (shoot_numbers)
+    uint64_t level_peak[MAX_GENERATIONS] = {};   // the widest level g of a pass since query_level_peaks_reset (shoot_numbers)
     // the radiance queries' own device words: made by the first radiance call of a context (shoot_words_reserve)
     bool shoot_words_made() const { return swords.p && d_report.p && d_hits0.p; }
     ~crt_query_state() {
@@ -280,21 +185,9 @@ struct crt_query_state {
     }
 };
 
-static void query_scratch_changed(crt_ctx *ctx) {
-    if (ctx->query) ctx->query->generation++;
-}
-
 void query_destroy(crt_ctx *ctx) {
     delete ctx->query;
     ctx->query = nullptr;
-}
-
-// crt_set_camera and crt_render*: the progressive frame under way, if any, is no longer the context's frame
-void query_progressive_reset(crt_ctx *ctx) {
-    if (!ctx->query) return;
-    ctx->query->prog_samples = 0;
-    ctx->query->prog_active = 0;
-    ctx->query->new_frame();
 }
 
 // a radiance pass's numbers, once its last copy has arrived
@@ -335,7 +228,7 @@ static int query_harvest(crt_ctx *ctx) {
 static bool uses_filter(const crt_ctx *ctx) { return ctx->scene.bvh_ok && ctx->tuning.bvh; }
 
 // before a call on `stream`: the waiting rules (OpenCall), and what every query needs, allocated by the first one
-static int query_begin(crt_ctx *ctx, hipStream_t stream, const CallKind kind) {
+int query_begin(crt_ctx *ctx, hipStream_t stream, const CallKind kind) {
     if (ctx->pending) {
         int rc = crt_wait(ctx);
         if (rc) return rc;
@@ -638,13 +531,9 @@ extern "C" int crt_camera_rays_device(crt_ctx *ctx, crt_ray *d_rays, void *strea
     if (!ctx) return CRT_ERR_INVALID;
     if (!d_rays) { ctx->error = "crt_camera_rays_device: d_rays is NULL"; return CRT_ERR_INVALID; }
     CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    QueryCamera cam;
-    memcpy(cam.pos, ctx->frame.cam_pos, sizeof(cam.pos));   // the camera of the NEXT frame: crt_set_camera's last word
-    memcpy(cam.m, ctx->frame.cam, sizeof(cam.m));
-    cam.width = ctx->width; cam.height = ctx->height;
     const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
     if (pixels == 0) return CRT_OK;
-    hipLaunchKernelGGL(query_camera_rays, dim3((uint32_t)((pixels + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, cam, d_rays);
+    hipLaunchKernelGGL(query_camera_rays, dim3((uint32_t)((pixels + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, ctx->camera(), d_rays);
     CRT_HIP_CHECK(ctx, hipGetLastError());
     return CRT_OK;
 }
@@ -891,6 +780,33 @@ static uint64_t shoot_level_room(const crt_query_state *q, const uint32_t g, con
     return room;
 }
 
+// The start of a call that only enqueues (shoot_enqueue, guide_enqueue) and so may be captured.  Inside a capture nothing may wait,
+// allocate or record an event: what the call would need of that is refused, while nothing is enqueued yet, so that the capture stays
+// valid.  `made`: the scratch the call cannot do without exists -- else `no_scratch` is the refusal, and `open_call` that of a call
+// that would have to be harvested.  Outside a capture: query_begin.
+struct Capture {
+    crt_ctx *ctx;
+    const char *what;
+    bool on = false;
+    int refuse(const char *why) const {
+        ctx->error = std::string(what) + ": the stream is being captured and " + why;
+        return CRT_ERR_INVALID;
+    }
+};
+static int capture_begin(crt_ctx *ctx, hipStream_t stream, const CallKind kind, Capture &capture, const bool made, const char *no_scratch,
+                         const char *open_call) {
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    CRT_HIP_CHECK(ctx, hipStreamIsCapturing(stream, &status));
+    capture.on = status != hipStreamCaptureStatusNone;
+    if (!capture.on) return query_begin(ctx, stream, kind);
+    if (status != hipStreamCaptureStatusActive) return capture.refuse("the capture is invalidated");
+    if (ctx->pending) return capture.refuse("a crt_render_async frame is pending: the call would have to wait for it (crt_wait before the capture)");
+    if (!made) return capture.refuse(no_scratch);
+    if (ctx->query->call.open) return capture.refuse(open_call);
+    return CRT_OK;
+}
+
 // crt_shoot_rays*_enqueue: one pass whose levels' sizes stay on the device (shoot_pass with a ShootDev).  Everything that waits,
 // allocates or records an event happens HERE, before the first launch, and none of it inside a capture: what a capture would need of
 // it is refused while nothing is enqueued yet, so that the capture stays valid.
@@ -900,23 +816,14 @@ static int shoot_enqueue(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32
         ctx->error = std::string(what) + ": a call is one pass: n = " + std::to_string(n) + " > 2^22 rays; split the rays over several calls";
         return CRT_ERR_INVALID;
     }
-    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-    CRT_HIP_CHECK(ctx, hipStreamIsCapturing(stream, &capture));
-    const bool capturing = capture != hipStreamCaptureStatusNone;
-    const auto refuse = [&](const char *why) {
-        ctx->error = std::string(what) + ": the stream is being captured and " + why;
-        return CRT_ERR_INVALID;
-    };
+    Capture capture{ctx, what};
     int rc;
-    if (capturing) {
-        if (capture != hipStreamCaptureStatusActive) return refuse("the capture is invalidated");
-        if (ctx->pending) return refuse("a crt_render_async frame is pending: the call would have to wait for it (crt_wait before the capture)");
-        if (!ctx->query || !ctx->query->shoot_words_made())
-            return refuse("the query scratch would have to grow (the context has none yet): size it with a radiance call before the capture");
-        if (ctx->query->call.open)
-            return refuse("an open call would have to be harvested, which waits (crt_get_shoot_stats or crt_get_query_stats before the capture)");
-    } else if ((rc = query_begin(ctx, stream, CALL_ENQUEUE)) || (rc = shoot_words_reserve(ctx))) return rc;
+    if ((rc = capture_begin(ctx, stream, CALL_ENQUEUE, capture, ctx->query && ctx->query->shoot_words_made(),
+                            "the query scratch would have to grow (the context has none yet): size it with a radiance call before the capture",
+                            "an open call would have to be harvested, which waits (crt_get_shoot_stats or crt_get_query_stats before the capture)")) ||
+        (!capture.on && (rc = shoot_words_reserve(ctx))))
+        return rc;
+    const bool capturing = capture.on;
     crt_query_state *q = ctx->query;
     // the capacities, and room for them
     const bool keys = gi != nullptr;
@@ -933,7 +840,7 @@ static int shoot_enqueue(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32
     if (capturing) {
         // (the reroute list need not follow the widest level here: a level's launches are cut to what the list holds, query_launches)
         if (!fits || (uses_filter(ctx) && q->list.cap < std::min(n, ctx->query_launch_rays)))
-            return refuse("the query scratch would have to grow for these rays and capacities: make the same call once before the capture");
+            return capture.refuse("the query scratch would have to grow for these rays and capacities: make the same call once before the capture");
     } else {
         if ((rc = query_list_reserve(ctx, widest)) || (rc = shoot_level_reserve(ctx, 0, n, false, keys))) return rc;
         for (uint32_t g = 1; g <= o->max_depth && dev.cap[g]; g++)
@@ -1057,7 +964,42 @@ extern "C" int crt_shoot_rays_gi_enqueue(crt_ctx *ctx, const crt_ray *d_rays, co
     });
 }
 
-extern "C" uint64_t crt_query_scratch_generation(const crt_ctx *ctx) { return ctx && ctx->query ? ctx->query->generation : 0; }
+// ---- what the GI frame calls (crt_giframe.hip) run of the above: the camera's rays are PRIMARY rays, the arrays are the context's
+
+int query_gi_check(crt_ctx *ctx, const char *what, const crt_options *options, uint64_t *pass) {
+    return query_check(ctx, shoot_needs(what, ctx, options, ctx, CRT_RAY_PRIMARY, true, pass));
+}
+
+int query_gi_run(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t *d_keys, uint64_t n, const crt_options *options, float *d_rgb, float *d_direct,
+                 const uint64_t pass, hipStream_t stream) {
+    const ShootGi gi{d_keys, 0u, d_direct};
+    return shoot_run(ctx, d_rays, n, CRT_RAY_PRIMARY, options, d_rgb, stream, pass, &gi);
+}
+
+int query_closest_run(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, crt_hit *d_hits, hipStream_t stream) {
+    return query_run(ctx, closest_call(d_rays, n, ray_type, d_hits), stream, true);
+}
+
+void query_level_peaks_reset(crt_ctx *ctx) { std::fill(ctx->query->level_peak, ctx->query->level_peak + MAX_GENERATIONS, 0ull); }
+
+// Behind a frame's sample 0: room in the level arrays for later samples, whose levels differ from sample 0's by the pixels whose jittered
+// ray meets another material.  shoot_children reserves fan x a level's rays for the level below it; this reserves fan x (the widest such
+// level of sample 0's passes and a quarter more), never more than the level can hold at all (fan^g x a pass's rays).  A later sample that
+// still outgrows it grows the arrays as any radiance call does: only crt_query_scratch_generation tells.
+int query_level_headroom(crt_ctx *ctx, const crt_options *o, const uint64_t pass_rays) {
+    crt_query_state *q = ctx->query;
+    const uint64_t fan = shoot_fan(o, true);
+    uint64_t most = pass_rays, widest = 0;
+    for (uint32_t g = 0; g < o->max_depth && q->level_peak[g]; g++) {
+        most = std::min<uint64_t>(most * fan, SHOOT_LEVEL_RAYS);
+        const uint64_t want = std::min(fan * (q->level_peak[g] + q->level_peak[g] / 4 + 64), most);
+        if (int rc = shoot_level_reserve(ctx, g + 1, want, true, true)) return rc;
+        widest = std::max(widest, want);
+    }
+    return query_list_reserve(ctx, widest);
+}
+
+extern "C" uint64_t crt_query_scratch_generation(const crt_ctx *ctx) { return ctx ? ctx->scratch_generation : 0; }
 
 // ---- chain guides (crt_guides.hip, csrc/kernel_guides.h): a pixel's chain of closest-hit walks through mirrors and glass.  For level
 // k = 0 .. max_bounces: one trace of the live chains (query_launches; behind level 0 the DEVN build, sized for n and reading the list's
@@ -1065,7 +1007,7 @@ extern "C" uint64_t crt_query_scratch_generation(const crt_ctx *ctx) { return ct
 // waits for nothing: a level that ran dry costs empty launches.
 
 // what every guide call asks beyond query_entry's check (NULL arrays, ray_type); nothing is enqueued on a refusal
-static int guide_check(crt_ctx *ctx, const char *what, const uint64_t n, const uint32_t max_bounces) {
+int guide_check(crt_ctx *ctx, const char *what, const uint64_t n, const uint32_t max_bounces) {
     const auto refuse = [&](const std::string &why) {
         ctx->error = std::string(what) + ": " + why;
         return (int)CRT_ERR_INVALID;
@@ -1078,27 +1020,20 @@ static int guide_check(crt_ctx *ctx, const char *what, const uint64_t n, const u
 }
 
 // One call's launches on `stream`; d_work holds crt_guide_work_bytes(n) bytes.  What waits, allocates or records an event happens before
-// the first launch and never inside a capture, which is refused what it would need of that (shoot_enqueue's rule).
-static int guide_enqueue(crt_ctx *ctx, const crt_ray *d_rays, const uint64_t n, const uint32_t ray_type, const float reflection_bias,
-                         const float refraction_bias, const uint32_t max_bounces, crt_hit *d_out_hits, uint8_t *d_out_status, crt_ray *d_out_last_rays,
-                         void *d_work, hipStream_t stream, const char *what, const bool first = true) {
-    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-    CRT_HIP_CHECK(ctx, hipStreamIsCapturing(stream, &capture));
-    const bool capturing = capture != hipStreamCaptureStatusNone;
-    const auto refuse = [&](const char *why) {
-        ctx->error = std::string(what) + ": the stream is being captured and " + why;
-        return CRT_ERR_INVALID;
-    };
+// the first launch and never inside a capture, which is refused what it would need of that (capture_begin).
+int guide_enqueue(crt_ctx *ctx, const crt_ray *d_rays, const uint64_t n, const uint32_t ray_type, const float reflection_bias, const float refraction_bias,
+                  const uint32_t max_bounces, crt_hit *d_out_hits, uint8_t *d_out_status, crt_ray *d_out_last_rays, void *d_work, hipStream_t stream,
+                  const char *what, const bool first) {
+    Capture capture{ctx, what};
     int rc;
-    if (capturing) {
-        if (capture != hipStreamCaptureStatusActive) return refuse("the capture is invalidated");
-        if (ctx->pending) return refuse("a crt_render_async frame is pending: the call would have to wait for it (crt_wait before the capture)");
-        if (!ctx->query || !ctx->query->pin) return refuse("the query scratch would have to be made (the context has none yet): make the same call once before the capture");
-        if (ctx->query->call.open) return refuse("an open call would have to be harvested, which waits (crt_get_query_stats before the capture)");
-        if (uses_filter(ctx) && ctx->query->list.cap < std::min(n, ctx->query_launch_rays))
-            return refuse("the query scratch would have to grow for these rays: make the same call once before the capture");
-    } else if ((rc = query_begin(ctx, stream, CALL_QUERY)) || (rc = query_list_reserve(ctx, n))) return rc;
+    if ((rc = capture_begin(ctx, stream, CALL_QUERY, capture, ctx->query && ctx->query->pin,
+                            "the query scratch would have to be made (the context has none yet): make the same call once before the capture",
+                            "an open call would have to be harvested, which waits (crt_get_query_stats before the capture)")))
+        return rc;
+    const bool capturing = capture.on;
+    if (capturing && uses_filter(ctx) && ctx->query->list.cap < std::min(n, ctx->query_launch_rays))
+        return capture.refuse("the query scratch would have to grow for these rays: make the same call once before the capture");
+    if (!capturing && (rc = query_list_reserve(ctx, n))) return rc;
     crt_query_state *q = ctx->query;
     const GuideWork W = guides_work(d_work, n);
     // every word starts at zero: the queries' cursors and totals, and the levels' counts in the work area (`first` false, a later round
@@ -1147,7 +1082,7 @@ extern "C" int crt_guide_rays(crt_ctx *ctx, const crt_ray *rays, uint64_t n, uin
         crt_query_state *q = ctx->query;
         const uint64_t cap = std::min(n, ctx->query_host_rays);
         if ((rc = reserve_all(ctx, q->s_rays, cap, q->s_hits, cap, q->g_status, cap, q->g_last, cap, q->g_work,
-                              (crt_guide_work_bytes(cap) + sizeof(float4) - 1) / sizeof(float4))))
+                              float4s(crt_guide_work_bytes(cap)))))
             return rc;
         for (uint64_t done = 0; done < n; done += ctx->query_host_rays) {
             const uint64_t m = std::min(n - done, ctx->query_host_rays);
@@ -1164,502 +1099,3 @@ extern "C" int crt_guide_rays(crt_ctx *ctx, const crt_ray *rays, uint64_t n, uin
         return (int)CRT_OK;
     });
 }
-
-// ---- progressive GI frames (csrc/kernel_progressive.h): the frame's left fold over a pixel's samples, cut into sample passes.
-
-static QueryCamera camera_of(const crt_ctx *ctx) {
-    QueryCamera cam;
-    memcpy(cam.pos, ctx->frame.cam_pos, sizeof(cam.pos));   // crt_set_camera's last word, as crt_camera_rays_device takes it
-    memcpy(cam.m, ctx->frame.cam, sizeof(cam.m));
-    cam.width = ctx->width; cam.height = ctx->height;
-    return cam;
-}
-
-// what the two primitives ask of (d_pixels, n): without a list the call is for the whole frame; one thread per entry must fit a grid
-int progressive_check(crt_ctx *ctx, const char *what, const uint32_t *d_pixels, const uint64_t n) {
-    const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
-    if (!d_pixels && n != pixels) {
-        ctx->error = std::string(what) + ": d_pixels is NULL, so n must be width * height = " + std::to_string(pixels) + ", not " + std::to_string(n);
-        return CRT_ERR_INVALID;
-    }
-    if (pixels > 0xFFFFFFFFull || (n + BLOCK - 1) / BLOCK > 0x7FFFFFFFull) {
-        ctx->error = std::string(what) + ": more pixels or entries than 32-bit pixel indices and one launch hold";
-        return CRT_ERR_INVALID;
-    }
-    return CRT_OK;
-}
-
-static int launch_sample_rays(crt_ctx *ctx, uint32_t gi_seed, uint32_t sample, const uint32_t *d_pixels, uint64_t n, crt_ray *d_rays, uint32_t *d_keys,
-                              hipStream_t stream) {
-    SampleRaysArgs P{};
-    P.cam = camera_of(ctx);
-    P.seed = gi_seed; P.sample = sample; P.pixels = d_pixels; P.n = n; P.rays = d_rays; P.keys = d_keys;
-    hipLaunchKernelGGL(progressive_sample_rays, dim3((uint32_t)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, P);
-    CRT_HIP_CHECK(ctx, hipGetLastError());
-    return CRT_OK;
-}
-
-static int launch_accumulate(crt_ctx *ctx, const float *d_rgb, const uint32_t *d_pixels, uint64_t n, uint32_t sample, float *d_sum, float *d_mean,
-                             hipStream_t stream) {
-    AccumulateArgs P{};
-    P.rgb = d_rgb; P.pixels = d_pixels; P.n = n; P.frame_pixels = (uint64_t)ctx->width * ctx->height; P.sample = sample; P.sum = d_sum; P.mean = d_mean;
-    hipLaunchKernelGGL(progressive_accumulate, dim3((uint32_t)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, P);
-    CRT_HIP_CHECK(ctx, hipGetLastError());
-    return CRT_OK;
-}
-
-extern "C" int crt_camera_sample_rays_device(crt_ctx *ctx, uint32_t gi_seed, uint32_t sample, const uint32_t *d_pixels, uint64_t n, crt_ray *d_rays,
-                                             uint32_t *d_keys, void *stream) {
-    const char *what = "crt_camera_sample_rays_device";
-    if (!ctx) return CRT_ERR_INVALID;
-    if (int rc = progressive_check(ctx, what, d_pixels, n)) return rc;
-    if (n == 0) return CRT_OK;
-    if (!d_rays) { ctx->error = std::string(what) + ": d_rays is NULL"; return CRT_ERR_INVALID; }
-    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    return launch_sample_rays(ctx, gi_seed, sample, d_pixels, n, d_rays, d_keys, (hipStream_t)stream);
-}
-
-extern "C" int crt_accumulate_samples_device(crt_ctx *ctx, const float *d_rgb, const uint32_t *d_pixels, uint64_t n, uint32_t sample, float *d_sum,
-                                             float *d_mean, void *stream) {
-    const char *what = "crt_accumulate_samples_device";
-    if (!ctx) return CRT_ERR_INVALID;
-    if (int rc = progressive_check(ctx, what, d_pixels, n)) return rc;
-    if (n == 0) return CRT_OK;
-    if (!d_rgb || !d_sum) { ctx->error = std::string(what) + ": d_rgb or d_sum is NULL"; return CRT_ERR_INVALID; }
-    if (sample == 0xFFFFFFFFu) { ctx->error = std::string(what) + ": sample + 1 does not fit 32 bits"; return CRT_ERR_INVALID; }
-    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    return launch_accumulate(ctx, d_rgb, d_pixels, n, sample, d_sum, d_mean, (hipStream_t)stream);
-}
-
-extern "C" uint32_t crt_progressive_samples(const crt_ctx *ctx) { return ctx && ctx->query ? ctx->query->prog_samples : 0u; }
-
-// Behind a frame's sample 0: room in the level arrays for later samples, whose levels differ from sample 0's by the pixels whose jittered
-// ray meets another material.  shoot_children reserves fan x a level's rays for the level below it; this reserves fan x (the widest such
-// level of sample 0's passes and a quarter more), never more than the level can hold at all (fan^g x a pass's rays).  A later sample that
-// still outgrows it grows the arrays as any radiance call does: only crt_query_scratch_generation tells.
-static int progressive_headroom(crt_ctx *ctx, const crt_options *o, const uint64_t pass_rays) {
-    crt_query_state *q = ctx->query;
-    const uint64_t fan = shoot_fan(o, true);
-    uint64_t most = pass_rays, widest = 0;
-    for (uint32_t g = 0; g < o->max_depth && q->level_peak[g]; g++) {
-        most = std::min<uint64_t>(most * fan, SHOOT_LEVEL_RAYS);
-        const uint64_t want = std::min(fan * (q->level_peak[g] + q->level_peak[g] / 4 + 64), most);
-        if (int rc = shoot_level_reserve(ctx, g + 1, want, true, true)) return rc;
-        widest = std::max(widest, want);
-    }
-    return query_list_reserve(ctx, widest);
-}
-
-extern "C" int crt_render_progressive(crt_ctx *ctx, const crt_options *options, uint32_t first_sample, uint32_t n_samples, float *out_rgb) {
-    const char *what = "crt_render_progressive";
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n_samples == 0) return CRT_OK;
-    // the GI radiance calls' own check: the camera's rays are PRIMARY rays, the arrays are the context's
-    uint64_t pass = 0;
-    if (int rc = query_check(ctx, shoot_needs(what, ctx, options, ctx, CRT_RAY_PRIMARY, true, &pass))) return rc;
-    if (first_sample != 0 && first_sample != crt_progressive_samples(ctx)) {   // (0 starts a new frame, whatever the context holds)
-        ctx->error = std::string(what) + ": first_sample is " + std::to_string(first_sample) + ", but the context's frame holds " +
-                     std::to_string(crt_progressive_samples(ctx)) + " samples (crt_progressive_samples; 0 starts a new frame)";
-        return CRT_ERR_INVALID;
-    }
-    if (first_sample != 0 && ctx->query->prog_is_adaptive) {   // (first_sample == the count > 0: the context has a query state)
-        ctx->error = std::string(what) + ": the frame under way is an ADAPTIVE frame (crt_render_adaptive continues it; first_sample 0 starts a new frame)";
-        return CRT_ERR_INVALID;
-    }
-    if ((uint64_t)first_sample + n_samples > 0xFFFFFFFFull) { ctx->error = std::string(what) + ": more than 2^32 - 1 samples"; return CRT_ERR_INVALID; }
-    const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
-    if (pixels == 0) return CRT_OK;
-    int rc;
-    if ((rc = progressive_check(ctx, what, nullptr, pixels)) || (rc = query_begin(ctx, ctx->stream, CALL_RADIANCE))) return rc;
-    crt_query_state *q = ctx->query;
-    if ((rc = reserve_all(ctx, q->prog_sum, 3 * pixels, q->prog_rgb, 3 * pixels, q->prog_rays, pixels, q->prog_keys, pixels))) return rc;
-    const ShootGi gi{q->prog_keys.p, 0u};
-    for (uint32_t s = first_sample; s - first_sample < n_samples; s++) {   // one at a time and in order: the fold's order is the frame's
-        if (s == 0) {
-            std::fill(q->level_peak, q->level_peak + MAX_GENERATIONS, 0ull);
-            q->prog_is_adaptive = q->prog_is_split = false;
-            q->new_frame();
-            q->prog_active = pixels;   // (a uniform frame shoots every pixel in every pass)
-        }
-        if ((rc = launch_sample_rays(ctx, options->gi_seed, s, nullptr, pixels, q->prog_rays.p, q->prog_keys.p, ctx->stream)) ||
-            (rc = shoot_run(ctx, q->prog_rays.p, pixels, CRT_RAY_PRIMARY, options, q->prog_rgb.p, ctx->stream, pass, &gi)) ||
-            (rc = launch_accumulate(ctx, q->prog_rgb.p, nullptr, pixels, s, q->prog_sum.p, ctx->d_frame, ctx->stream)))
-            return rc;
-        q->prog_samples = s + 1;
-        if (s == 0 && (rc = progressive_headroom(ctx, options, std::min(pixels, pass)))) return rc;
-    }
-    if (out_rgb) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, ctx->d_frame, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return CRT_OK;
-}
-
-// ---- adaptive sampling (csrc/kernel_adaptive.h, csrc/adaptive_rule.h): the progressive frame's loop over a pixel list that shrinks.
-
-extern "C" void crt_adaptive_defaults(crt_adaptive *a) {
-    if (!a) return;
-    a->size = (uint32_t)sizeof(crt_adaptive);
-    a->min_samples = 4;
-    a->max_samples = 64;
-    a->threshold = 0.05f;
-    a->floor = 1e-4f;
-}
-
-static uint64_t adaptive_blocks(const uint64_t n) { return (n + BLOCK - 1) / BLOCK; }
-
-extern "C" size_t crt_adaptive_work_bytes(uint64_t n) {
-    const uint64_t blocks = adaptive_blocks(n);
-    return (size_t)(blocks * ADAPTIVE_WAVES * sizeof(unsigned long long) + 2 * blocks * sizeof(uint32_t));
-}
-
-static int adaptive_check(crt_ctx *ctx, const char *what, const crt_adaptive *a) {
-    const char *why = nullptr;
-    if (!a) why = "adaptive is NULL";
-    else if (a->size != sizeof(crt_adaptive)) why = "adaptive->size is not sizeof(crt_adaptive)";
-    else if (a->min_samples == 0) why = "min_samples is 0";
-    else if (a->max_samples < a->min_samples) why = "max_samples < min_samples";
-    else if (!(a->threshold >= 0.0f) || !std::isfinite(a->threshold)) why = "threshold is negative or not finite";
-    else if (!(a->floor >= 0.0f) || !std::isfinite(a->floor)) why = "floor is negative or not finite";
-    if (!why) return CRT_OK;
-    ctx->error = std::string(what) + ": " + why;
-    return CRT_ERR_INVALID;
-}
-
-// the step, the scan and the scatter of n > 0 entries, one behind the other on `stream`
-static int launch_adaptive(crt_ctx *ctx, const float *d_rgb, const uint32_t *d_pixels, uint64_t n, uint32_t sample, const crt_adaptive *a, float *d_sum,
-                           float *d_sq, float *d_mean, uint32_t *d_counts, uint32_t *d_next, uint32_t *d_next_n, void *d_work, hipStream_t stream) {
-    const uint32_t blocks = (uint32_t)adaptive_blocks(n);
-    AdaptiveWork work{};
-    work.masks = (unsigned long long *)d_work;
-    work.counts = (uint32_t *)(work.masks + (uint64_t)blocks * ADAPTIVE_WAVES);
-    work.offsets = work.counts + blocks;
-    AdaptiveStepArgs S{};
-    S.rgb = d_rgb; S.pixels = d_pixels; S.n = n; S.frame_pixels = (uint64_t)ctx->width * ctx->height; S.sample = sample;
-    S.rule = crt_adaptive_rule{a->min_samples, a->max_samples, a->threshold, a->floor};
-    S.sum = d_sum; S.sq = d_sq; S.mean = d_mean; S.count = d_counts; S.work = work;
-    hipLaunchKernelGGL(adaptive_step, dim3(blocks), dim3(BLOCK), 0, stream, S);
-    CRT_HIP_CHECK(ctx, hipGetLastError());
-    const AdaptiveScanArgs C{work.counts, work.offsets, d_next_n, blocks};
-    hipLaunchKernelGGL(adaptive_scan, dim3(1), dim3(BLOCK), 0, stream, C);
-    CRT_HIP_CHECK(ctx, hipGetLastError());
-    const AdaptiveScatterArgs T{d_pixels, n, work, d_next};
-    hipLaunchKernelGGL(adaptive_scatter, dim3(blocks), dim3(BLOCK), 0, stream, T);
-    CRT_HIP_CHECK(ctx, hipGetLastError());
-    return CRT_OK;
-}
-
-extern "C" int crt_adaptive_step_device(crt_ctx *ctx, const float *d_rgb, const uint32_t *d_pixels, uint64_t n, uint32_t sample, const crt_adaptive *adaptive,
-                                        float *d_sum, float *d_sq, float *d_mean, uint32_t *d_counts, uint32_t *d_next_pixels, uint32_t *d_next_n,
-                                        void *d_work, void *stream) {
-    const char *what = "crt_adaptive_step_device";
-    if (!ctx) return CRT_ERR_INVALID;
-    if (int rc = adaptive_check(ctx, what, adaptive)) return rc;
-    if (int rc = progressive_check(ctx, what, d_pixels, n)) return rc;
-    if (n > 0xFFFFFFFFull) { ctx->error = std::string(what) + ": the next list's length is one 32-bit word: n = " + std::to_string(n) + " > 2^32 - 1"; return CRT_ERR_INVALID; }
-    if (!d_next_n) { ctx->error = std::string(what) + ": d_next_n is NULL"; return CRT_ERR_INVALID; }
-    if (n != 0) {
-        if (!d_rgb || !d_sum || !d_sq || !d_counts || !d_next_pixels || !d_work) {
-            ctx->error = std::string(what) + ": d_rgb, d_sum, d_sq, d_counts, d_next_pixels or d_work is NULL";
-            return CRT_ERR_INVALID;
-        }
-        if (d_next_pixels == d_pixels) { ctx->error = std::string(what) + ": d_next_pixels must not alias d_pixels"; return CRT_ERR_INVALID; }
-        if ((uintptr_t)d_work % alignof(unsigned long long)) { ctx->error = std::string(what) + ": d_work must be aligned to 8 bytes"; return CRT_ERR_INVALID; }
-        if (sample == 0xFFFFFFFFu) { ctx->error = std::string(what) + ": sample + 1 does not fit 32 bits"; return CRT_ERR_INVALID; }
-    }
-    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (n == 0) {   // no entry: the next list is empty, and nothing else is written
-        CRT_HIP_CHECK(ctx, hipMemsetAsync(d_next_n, 0, sizeof(uint32_t), (hipStream_t)stream));
-        return CRT_OK;
-    }
-    return launch_adaptive(ctx, d_rgb, d_pixels, n, sample, adaptive, d_sum, d_sq, d_mean, d_counts, d_next_pixels, d_next_n, d_work, (hipStream_t)stream);
-}
-
-extern "C" uint64_t crt_progressive_active(const crt_ctx *ctx) {
-    return ctx && ctx->query && ctx->query->prog_samples ? ctx->query->prog_active : 0ull;
-}
-
-static bool same_adaptive(const crt_adaptive &a, const crt_adaptive &b) {
-    return a.min_samples == b.min_samples && a.max_samples == b.max_samples && a.threshold == b.threshold && a.floor == b.floor;
-}
-
-// crt_render_adaptive and, `split`, crt_render_adaptive_split: the same loop with the split shoot and, behind a pass's step, split_fold on
-// the same list and sample.  What the unsplit call produces is untouched by it.
-static int render_adaptive(crt_ctx *ctx, const char *what, const bool split, const crt_options *options, const crt_adaptive *adaptive, uint32_t first_pass,
-                           uint32_t n_passes, float *out_rgb, uint32_t *out_counts) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (n_passes == 0) return CRT_OK;
-    uint64_t pass = 0;
-    if (int rc = query_check(ctx, shoot_needs(what, ctx, options, ctx, CRT_RAY_PRIMARY, true, &pass))) return rc;
-    if (int rc = adaptive_check(ctx, what, adaptive)) return rc;
-    if (first_pass != 0 && first_pass != crt_progressive_samples(ctx)) {   // (0 starts a new frame, whatever the context holds)
-        ctx->error = std::string(what) + ": first_pass is " + std::to_string(first_pass) + ", but the context's frame holds " +
-                     std::to_string(crt_progressive_samples(ctx)) + " passes (crt_progressive_samples; 0 starts a new frame)";
-        return CRT_ERR_INVALID;
-    }
-    if (first_pass != 0 && !ctx->query->prog_is_adaptive) {
-        ctx->error = std::string(what) + ": the frame under way is a UNIFORM progressive frame (crt_render_progressive continues it; first_pass 0 starts a new frame)";
-        return CRT_ERR_INVALID;
-    }
-    if (first_pass != 0 && ctx->query->prog_is_split != split) {
-        ctx->error = std::string(what) + (split ? ": the frame under way is an UNSPLIT adaptive frame (crt_render_adaptive continues it; first_pass 0 starts a new frame)"
-                                                : ": the frame under way is a SPLIT adaptive frame (crt_render_adaptive_split continues it; first_pass 0 starts a new frame)");
-        return CRT_ERR_INVALID;
-    }
-    if (first_pass != 0 && !same_adaptive(*adaptive, ctx->query->prog_adaptive)) {
-        ctx->error = std::string(what) + ": adaptive differs from the settings latched by the frame's pass 0";
-        return CRT_ERR_INVALID;
-    }
-    if ((uint64_t)first_pass + n_passes > 0xFFFFFFFFull) { ctx->error = std::string(what) + ": more than 2^32 - 1 passes"; return CRT_ERR_INVALID; }
-    const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
-    if (pixels == 0) return CRT_OK;
-    int rc;
-    if ((rc = progressive_check(ctx, what, nullptr, pixels)) || (rc = query_begin(ctx, ctx->stream, CALL_RADIANCE))) return rc;
-    crt_query_state *q = ctx->query;
-    if ((rc = reserve_all(ctx, q->prog_sum, 3 * pixels, q->prog_rgb, 3 * pixels, q->prog_rays, pixels, q->prog_keys, pixels, q->prog_sq, pixels,
-                          q->prog_counts, pixels, q->prog_list[0], pixels, q->prog_list[1], pixels, q->prog_next_n, 1, q->prog_work,
-                          (crt_adaptive_work_bytes(pixels) + 7) / 8)) ||
-        (split && (rc = reserve_all(ctx, q->split_direct, 3 * pixels, q->split_dsum, 3 * pixels, q->split_rsum, 3 * pixels, q->split_rsq, pixels))))
-        return rc;
-    const ShootGi gi{q->prog_keys.p, 0u, split ? q->split_direct.p : nullptr};
-    for (uint32_t s = first_pass; s - first_pass < n_passes; s++) {   // one at a time and in order: the fold's order is the frame's
-        if (s == 0) {
-            std::fill(q->level_peak, q->level_peak + MAX_GENERATIONS, 0ull);
-            q->prog_is_adaptive = true;
-            q->prog_is_split = split;
-            q->new_frame();            // (a new frame: crt_render_denoised traces its guides again)
-            q->prog_adaptive = *adaptive;
-            q->prog_reflection_bias = options->reflection_bias;
-            q->prog_refraction_bias = options->refraction_bias;
-            q->prog_active = pixels;
-        }
-        const uint64_t n = q->prog_active;
-        if (n != 0) {   // (an empty list launches nothing: every pixel has stopped, or reached max_samples)
-            const uint32_t *list = s == 0 ? nullptr : q->prog_list[q->prog_cur].p;   // pass 0: every pixel
-            uint32_t *next = q->prog_list[s == 0 ? 0 : q->prog_cur ^ 1].p;
-            if ((rc = launch_sample_rays(ctx, options->gi_seed, s, list, n, q->prog_rays.p, q->prog_keys.p, ctx->stream)) ||
-                (rc = shoot_run(ctx, q->prog_rays.p, n, CRT_RAY_PRIMARY, options, q->prog_rgb.p, ctx->stream, pass, &gi)) ||
-                (rc = launch_adaptive(ctx, q->prog_rgb.p, list, n, s, adaptive, q->prog_sum.p, q->prog_sq.p, ctx->d_frame, q->prog_counts.p, next,
-                                      q->prog_next_n.p, q->prog_work.p, ctx->stream)) ||
-                (split && (rc = split_launch_fold(ctx, q->prog_rgb.p, q->split_direct.p, list, n, s, q->split_dsum.p, q->split_rsum.p, q->split_rsq.p,
-                                                  ctx->stream))))
-                return rc;
-            // the next list's length: 4 bytes through pinned memory, once a pass
-            CRT_HIP_CHECK(ctx, hipMemcpyAsync(&q->pin->adaptive_n, q->prog_next_n.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            q->prog_active = q->pin->adaptive_n;
-            if (s != 0) q->prog_cur ^= 1;
-            else q->prog_cur = 0;
-        }
-        q->prog_samples = s + 1;
-        if (s == 0 && (rc = progressive_headroom(ctx, options, std::min(pixels, pass)))) return rc;
-    }
-    if (out_rgb) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, ctx->d_frame, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (out_counts) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_counts, q->prog_counts.p, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return CRT_OK;
-}
-
-extern "C" int crt_render_adaptive(crt_ctx *ctx, const crt_options *options, const crt_adaptive *adaptive, uint32_t first_pass, uint32_t n_passes,
-                                   float *out_rgb, uint32_t *out_counts) {
-    return render_adaptive(ctx, "crt_render_adaptive", false, options, adaptive, first_pass, n_passes, out_rgb, out_counts);
-}
-
-extern "C" int crt_render_adaptive_split(crt_ctx *ctx, const crt_options *options, const crt_adaptive *adaptive, uint32_t first_pass, uint32_t n_passes,
-                                         float *out_rgb, uint32_t *out_counts) {
-    return render_adaptive(ctx, "crt_render_adaptive_split", true, options, adaptive, first_pass, n_passes, out_rgb, out_counts);
-}
-
-extern "C" int crt_read_split_state(crt_ctx *ctx, float *out_dsum, float *out_rsum, float *out_rsq) {
-    const char *what = "crt_read_split_state";
-    if (!ctx) return CRT_ERR_INVALID;
-    if (crt_progressive_samples(ctx) == 0 || !ctx->query->prog_is_adaptive || !ctx->query->prog_is_split) {
-        ctx->error = std::string(what) + ": no split adaptive frame is under way (crt_render_adaptive_split starts one; crt_set_camera and crt_render* end it)";
-        return CRT_ERR_INVALID;
-    }
-    const crt_query_state *q = ctx->query;
-    const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
-    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (out_dsum) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_dsum, q->split_dsum.p, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (out_rsum) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rsum, q->split_rsum.p, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (out_rsq) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rsq, q->split_rsq.p, pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return CRT_OK;
-}
-
-// ---- denoising (crt_denoise.hip, csrc/kernel_denoise.h, csrc/denoise_rule.h): the adaptive frame under way or finished, filtered into a
-// buffer of its own.  Nothing of the frame changes: the persistent colour buffer, sum, sq, counts, the lists and crt_progressive_samples
-// are only read, so the frame can be denoised after any pass and continued.
-
-// what crt_render_denoised and crt_render_accumulated ask of the context's frame
-static int adaptive_frame_check(crt_ctx *ctx, const char *what, const bool split) {
-    if (crt_progressive_samples(ctx) == 0) {
-        ctx->error = std::string(what) + ": no adaptive frame is under way (crt_render_adaptive starts one; crt_set_camera and crt_render* end it)";
-        return CRT_ERR_INVALID;
-    }
-    if (!ctx->query->prog_is_adaptive) {
-        ctx->error = std::string(what) + ": the frame under way is a UNIFORM progressive frame, which keeps no second moment (sq): use crt_render_adaptive "
-                                         "with min_samples = max_samples";
-        return CRT_ERR_INVALID;
-    }
-    if (split && !ctx->query->prog_is_split) {
-        ctx->error = std::string(what) + ": the frame under way is an UNSPLIT adaptive frame, which keeps no direct part: crt_render_adaptive_split makes a split one";
-        return CRT_ERR_INVALID;
-    }
-    if ((uint64_t)ctx->width * ctx->height >= (1ull << 31)) { ctx->error = std::string(what) + ": width * height >= 2^31"; return CRT_ERR_INVALID; }
-    return CRT_OK;
-}
-
-// the fold's state the two frame calls below filter: the whole colour's, or -- `split` -- the rest's (csrc/split_rule.h)
-struct FoldState { const float *sum, *sq; };
-static FoldState fold_state(const crt_query_state *q, const bool split) {
-    return split ? FoldState{q->split_rsum.p, q->split_rsq.p} : FoldState{q->prog_sum.p, q->prog_sq.p};
-}
-
-// the frame's guides, traced at the frame's first call of either kind: the first hits of the camera's centre rays, as CRT_RAY_PRIMARY (the
-// rays of a pass are scratch between passes); den_hits is reserved
-// crt_set_guide_bounces > 0: and, behind them, the chain guides of the same rays, for the spatial filter alone (the temporal stage keeps the
-// first hits: with a still camera "as if painted" is exact)
-static int frame_guides(crt_ctx *ctx, const uint64_t pixels) {
-    crt_query_state *q = ctx->query;
-    if (q->den_guides) return CRT_OK;
-    int rc;
-    if ((rc = crt_camera_rays_device(ctx, q->prog_rays.p, ctx->stream)) ||
-        (rc = query_run(ctx, closest_call(q->prog_rays.p, pixels, CRT_RAY_PRIMARY, q->den_hits.p), ctx->stream, true)))
-        return rc;
-    if (ctx->guide_bounces) {
-        const char *what = "crt_set_guide_bounces";
-        if ((rc = guide_check(ctx, what, pixels, ctx->guide_bounces)) ||
-            (rc = reserve_all(ctx, q->den_chain, pixels, q->guide_work, (crt_guide_work_bytes(pixels) + sizeof(float4) - 1) / sizeof(float4))) ||
-            (rc = guide_enqueue(ctx, q->prog_rays.p, pixels, CRT_RAY_PRIMARY, q->prog_reflection_bias, q->prog_refraction_bias, ctx->guide_bounces,
-                                q->den_chain.p, nullptr, nullptr, q->guide_work.p, ctx->stream, what)))
-            return rc;
-    }
-    q->den_guides = true;
-    return CRT_OK;
-}
-// the guides of the spatial filter stage
-static const crt_hit *filter_guides(const crt_ctx *ctx) { return ctx->guide_bounces ? ctx->query->den_chain.p : ctx->query->den_hits.p; }
-
-extern "C" int crt_set_guide_bounces(crt_ctx *ctx, uint32_t max_bounces) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (int rc = guide_check(ctx, "crt_set_guide_bounces", 0, max_bounces)) return rc;
-    if (max_bounces == ctx->guide_bounces) return CRT_OK;
-    ctx->guide_bounces = max_bounces;
-    if (ctx->query) ctx->query->den_guides = false;   // the kept guides alone: the history and the frame's serial stay
-    return CRT_OK;
-}
-extern "C" uint32_t crt_guide_bounces(const crt_ctx *ctx) { return ctx ? ctx->guide_bounces : 0u; }
-
-// crt_render_denoised and, `split`, crt_render_denoised_split: the rest is filtered and the direct part's mean added back untouched
-static int render_denoised(crt_ctx *ctx, const char *what, const bool split, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (int rc = denoise_check(ctx, what, denoise)) return rc;
-    if (int rc = adaptive_frame_check(ctx, what, split)) return rc;
-    const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
-    int rc;
-    if ((rc = query_begin(ctx, ctx->stream, CALL_QUERY))) return rc;
-    crt_query_state *q = ctx->query;
-    if ((rc = reserve_all(ctx, q->den_hits, pixels, q->den_mean, 3 * pixels, q->den_var, pixels, q->den_out, 3 * pixels, q->den_work,
-                          (crt_denoise_work_bytes(ctx->width, ctx->height) + sizeof(float4) - 1) / sizeof(float4), q->den_q8, 3 * pixels)) ||
-        (rc = frame_guides(ctx, pixels)))
-        return rc;
-    const FoldState state = fold_state(q, split);
-    if ((rc = denoise_launch_variance(ctx, state.sum, state.sq, q->prog_counts.p, pixels, q->den_mean.p, q->den_var.p, ctx->stream)) ||
-        (rc = denoise_launch(ctx, denoise, ctx->width, ctx->height, q->den_mean.p, q->den_var.p, filter_guides(ctx), q->den_out.p, nullptr, q->den_work.p,
-                             ctx->stream)) ||
-        (split && (rc = split_launch_recombine(ctx, q->den_out.p, q->split_dsum.p, q->prog_counts.p, pixels, q->den_out.p, ctx->stream))))
-        return rc;
-    if (out_rgb) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, q->den_out.p, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (out_rgb8) {
-        if ((rc = crt_quantize_device(ctx, q->den_out.p, 3 * pixels, q->den_q8.p, ctx->stream))) return rc;
-        CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb8, q->den_q8.p, 3 * pixels, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return CRT_OK;
-}
-
-extern "C" int crt_render_denoised(crt_ctx *ctx, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8) {
-    return render_denoised(ctx, "crt_render_denoised", false, denoise, out_rgb, out_rgb8);
-}
-
-extern "C" int crt_render_denoised_split(crt_ctx *ctx, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8) {
-    return render_denoised(ctx, "crt_render_denoised_split", true, denoise, out_rgb, out_rgb8);
-}
-
-// ---- temporal accumulation (crt_temporal.hip, csrc/kernel_temporal.h, csrc/temporal_rule.h): the adaptive frame's state merged with the
-// last frame's history, into buffers of its own.  The frame is only read, as crt_render_denoised reads it.  `previous` changes only when a
-// call finds a new frame's serial, so every call on one frame merges the same history.
-
-// crt_render_accumulated and, `split`, crt_render_accumulated_split: the history pair hist[split] holds the moments of what the call
-// merges -- whole colours, or the rest --, and the direct part's mean is this frame's own, added back behind the optional filter
-static int render_accumulated(crt_ctx *ctx, const char *what, const bool split, const crt_temporal *temporal, const crt_denoise *denoise, float *out_rgb,
-                              uint8_t *out_rgb8, uint8_t *out_valid) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (int rc = temporal_check(ctx, what, temporal)) return rc;
-    if (denoise)
-        if (int rc = denoise_check(ctx, what, denoise)) return rc;
-    if (int rc = adaptive_frame_check(ctx, what, split)) return rc;
-    const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
-    int rc;
-    if ((rc = query_begin(ctx, ctx->stream, CALL_QUERY))) return rc;
-    crt_query_state *q = ctx->query;
-    crt_query_state::History &hist = q->hist[split ? 1 : 0];
-    if ((rc = reserve_all(ctx, q->den_hits, pixels, hist.slot[0], pixels, hist.slot[1], pixels, q->acc_rgb, 3 * pixels, q->acc_var, pixels, q->acc_valid,
-                          pixels, q->den_q8, 3 * pixels)) ||
-        (denoise && (rc = reserve_all(ctx, q->den_out, 3 * pixels, q->den_work,
-                                      (crt_denoise_work_bytes(ctx->width, ctx->height) + sizeof(float4) - 1) / sizeof(float4)))) ||
-        (rc = frame_guides(ctx, pixels)))
-        return rc;
-    if (hist.has_cur && hist.serial != q->frame_serial) {   // `current` is an ended frame's: it is the previous history from here on
-        hist.cur ^= 1;
-        hist.has_prev = true;
-        hist.has_cur = false;
-    }
-    const int cur = hist.cur;
-    const FoldState state = fold_state(q, split);
-    if ((rc = temporal_launch(ctx, temporal, ctx->width, ctx->height, &hist.pose[cur ^ 1], hist.has_prev ? hist.slot[cur ^ 1].p : nullptr, state.sum,
-                              state.sq, q->prog_counts.p, q->den_hits.p, hist.slot[cur].p, q->acc_rgb.p, q->acc_var.p, q->acc_valid.p, ctx->stream)))
-        return rc;
-    if (!hist.has_cur) hist.frames++;   // once a frame
-    hist.has_cur = true;
-    hist.serial = q->frame_serial;
-    memcpy(hist.pose[cur].position, ctx->frame.cam_pos, sizeof(hist.pose[cur].position));
-    memcpy(hist.pose[cur].matrix, ctx->frame.cam, sizeof(hist.pose[cur].matrix));
-    float *result = q->acc_rgb.p;
-    if (denoise) {
-        if ((rc = denoise_launch(ctx, denoise, ctx->width, ctx->height, q->acc_rgb.p, q->acc_var.p, filter_guides(ctx), q->den_out.p, nullptr, q->den_work.p,
-                                 ctx->stream)))
-            return rc;
-        result = q->den_out.p;
-    }
-    if (split && (rc = split_launch_recombine(ctx, result, q->split_dsum.p, q->prog_counts.p, pixels, result, ctx->stream))) return rc;
-    if (out_rgb) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, result, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (out_rgb8) {
-        if ((rc = crt_quantize_device(ctx, result, 3 * pixels, q->den_q8.p, ctx->stream))) return rc;
-        CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb8, q->den_q8.p, 3 * pixels, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (out_valid) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_valid, q->acc_valid.p, pixels, hipMemcpyDeviceToHost, ctx->stream));
-    CRT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return CRT_OK;
-}
-
-extern "C" int crt_render_accumulated(crt_ctx *ctx, const crt_temporal *temporal, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8,
-                                      uint8_t *out_valid) {
-    return render_accumulated(ctx, "crt_render_accumulated", false, temporal, denoise, out_rgb, out_rgb8, out_valid);
-}
-
-extern "C" int crt_render_accumulated_split(crt_ctx *ctx, const crt_temporal *temporal, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8,
-                                            uint8_t *out_valid) {
-    return render_accumulated(ctx, "crt_render_accumulated_split", true, temporal, denoise, out_rgb, out_rgb8, out_valid);
-}
-
-extern "C" int crt_history_reset(crt_ctx *ctx) {
-    if (!ctx) return CRT_ERR_INVALID;
-    if (crt_query_state *q = ctx->query) {
-        q->hist[0].reset();
-        q->hist[1].reset();
-    }
-    return CRT_OK;
-}
-
-extern "C" uint32_t crt_history_frames(const crt_ctx *ctx) { return ctx && ctx->query ? ctx->query->hist[0].frames : 0u; }
-extern "C" uint32_t crt_history_frames_split(const crt_ctx *ctx) { return ctx && ctx->query ? ctx->query->hist[1].frames : 0u; }

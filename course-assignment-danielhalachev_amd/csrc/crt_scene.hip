@@ -576,6 +576,7 @@ extern "C" void crt_destroy(crt_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     for (void *p : ctx->allocs) (void)hipFree(p);
     query_destroy(ctx);
+    giframe_destroy(ctx);
     if (ctx->d_frame) (void)hipFree(ctx->d_frame);
     if (ctx->d_quant) (void)hipFree(ctx->d_quant);
     if (ctx->d_items) (void)hipFree(ctx->d_items);
@@ -629,6 +630,6 @@ extern "C" int crt_set_camera(crt_ctx *ctx, const float position[3], const float
     if (!ctx || !position || !matrix) return CRT_ERR_INVALID;
     memcpy(ctx->frame.cam_pos, position, 3 * sizeof(float));
     memcpy(ctx->frame.cam, matrix, 9 * sizeof(float));
-    query_progressive_reset(ctx);   // a progressive frame is one camera's
+    giframe_reset(ctx);   // a progressive frame is one camera's
     return CRT_OK;
 }

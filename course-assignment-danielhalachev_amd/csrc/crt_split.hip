@@ -1,5 +1,5 @@
 // crt_split.hip -- the split GI frames' primitives (include/crt_hip.h: "Split GI frames"): crt_split_fold_device and
-// crt_split_recombine_device, and the three launches for the radiance passes and the frame calls of crt_query.hip, which owns the frame's
+// crt_split_recombine_device, and the three launches for the radiance passes of crt_query.hip and the frame calls of crt_giframe.hip, which owns the frame's
 // state.  Kernels: csrc/kernel_split.h; the rule: csrc/split_rule.h.  Everything here only enqueues: one launch, no wait, no allocation,
 // no readback.
 #include "crt_internal.h"

@@ -1,5 +1,5 @@
 // crt_temporal.hip -- the temporal accumulation's primitive (include/crt_hip.h: "Temporal accumulation"): crt_temporal_defaults and
-// crt_temporal_device, and its launch for crt_render_accumulated (crt_query.hip, which owns the frame's state and the history).  Kernel:
+// crt_temporal_device, and its launch for crt_render_accumulated (crt_giframe.hip, which owns the frame's state and the history).  Kernel:
 // csrc/kernel_temporal.h; the rule: csrc/temporal_rule.h.  The device call only enqueues: one launch, no wait, no allocation, no readback.
 #include "crt_internal.h"
 

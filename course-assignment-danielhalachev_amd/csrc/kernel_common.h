@@ -226,6 +226,8 @@ __device__ __forceinline__ void normalize3(float &x, float &y, float &z) {  // V
 __device__ __forceinline__ float std_max(float a, float b) { return (a < b) ? b : a; }
 __device__ __forceinline__ float std_min(float a, float b) { return (b < a) ? b : a; }
 
+// the camera of the kernels that make rays for the caller or a frame call (query_camera_rays, progressive_sample_rays): position, matrix, frame size
+struct QueryCamera { float pos[3]; float m[9]; uint32_t width, height; };
 
 // A ray as both kernels see it: origin, direction, 1/direction (BoundingBox.h:95 recomputes it per box,
 // it only depends on the ray) and the mask of axes with |d| < FLT_EPSILON (BoundingBox.h:90).

@@ -252,7 +252,6 @@ __global__ __launch_bounds__(BLOCK) void query_reset(const ResetArgs P) {
 // RayTracer::getRay (RayTracer.cpp:61-80) at the pixel centre, one thread per pixel, row-major: the direction normalised ONCE, as
 // getRay returns it (primary_ray, kernel_common.h, is getRay FOLLOWED by shootRay's own normalisation, RayTracer.cpp:420: the ray a
 // frame walks.  A query walks the ray it is given, so a caller who wants the frame's ray normalises once more).
-struct QueryCamera { float pos[3]; float m[9]; uint32_t width, height; };
 __global__ __launch_bounds__(BLOCK) void query_camera_rays(const QueryCamera C, crt_ray *out) {
     const uint64_t gid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (gid >= (uint64_t)C.width * C.height) return;
