@@ -185,6 +185,22 @@ def make_temporal(**fields):
     return t
 
 
+class VarianceEstimate(C.Structure):
+    """crt_variance_estimate: the settings of the GI frames' variance estimate (make_variance_estimate fills it)"""
+    _fields_ = [("size", C.c_uint32), ("min_history", C.c_float), ("normal_squarings", C.c_uint32), ("sigma_plane", C.c_float)]
+
+
+def make_variance_estimate(**fields):
+    """crt_variance_estimate_defaults (4.0, 5, 0.02) with the given fields replaced, e.g. make_variance_estimate(min_history=2.0)."""
+    e = VarianceEstimate()
+    lib().crt_variance_estimate_defaults(C.byref(e))
+    for k, v in fields.items():
+        if k not in dict(VarianceEstimate._fields_) or k == "size":
+            raise KeyError("crt_variance_estimate has no field %r" % k)
+        setattr(e, k, v)
+    return e
+
+
 def make_pose(position, matrix):
     """a crt_camera_pose of 3 and 9 floats"""
     pose = CameraPose()
@@ -255,6 +271,7 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_st
                   "crt_shoot_rays_gi_split", "crt_shoot_rays_gi_split_device", "crt_split_fold_device", "crt_split_recombine_device",
                   "crt_render_adaptive_split", "crt_read_split_state", "crt_render_denoised_split", "crt_render_accumulated_split", "crt_history_frames_split",
                   "crt_guide_work_bytes", "crt_guide_rays", "crt_guide_rays_device", "crt_set_guide_bounces", "crt_guide_bounces",
+                  "crt_variance_estimate_defaults", "crt_variance_estimate_device", "crt_set_variance_estimate", "crt_get_variance_estimate",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -363,6 +380,11 @@ def lib():
     L.crt_set_guide_bounces.argtypes = [vp, u32]
     L.crt_guide_bounces.restype = u32
     L.crt_guide_bounces.argtypes = [vp]
+    L.crt_variance_estimate_defaults.argtypes = [C.POINTER(VarianceEstimate)]
+    L.crt_variance_estimate_defaults.restype = None
+    L.crt_variance_estimate_device.argtypes = [vp, C.POINTER(VarianceEstimate), u32, u32, vp, vp, vp, vp, vp]
+    L.crt_set_variance_estimate.argtypes = [vp, C.POINTER(VarianceEstimate)]
+    L.crt_get_variance_estimate.argtypes = [vp, C.POINTER(VarianceEstimate)]
     L.crt_history_frames_split.restype = u32
     L.crt_host_shoot_stats_layout.argtypes = [C.POINTER(u32), u32]
     L.crt_host_shoot_stats_layout.restype = u32
@@ -1088,6 +1110,29 @@ class Tracer:
 
     def guide_bounces(self) -> int:
         return int(lib().crt_guide_bounces(self.ctx))
+
+    # ---- variance estimate (include/crt_hip.h: crt_variance_estimate_device, crt_set_variance_estimate)
+    def variance_estimate_device(self, estimate, width, height, d_moments_ptr, d_hits_ptr, d_var_ptr, d_out_var_ptr, stream_ptr=None):
+        """Where a pixel's record stands for fewer than estimate.min_history samples, its variance of the mean is replaced by a 7x7
+        cross-bilateral estimate from its neighbours' moments: moments uint8 [H * W, 64] (crt_history_pixel records, e.g. temporal_device's
+        next; aligned to 16 bytes), hits uint8 [H * W, 48], var float32 [H * W] -> out_var float32 [H * W] (may be var); device arrays of
+        the caller's.  Enqueues and returns."""
+        self._single("variance_estimate_device")
+        self._check(lib().crt_variance_estimate_device(self.ctx, C.byref(estimate), int(width), int(height), C.c_void_p(d_moments_ptr),
+                                                       C.c_void_p(d_hits_ptr), C.c_void_p(d_var_ptr), C.c_void_p(d_out_var_ptr),
+                                                       C.c_void_p(stream_ptr or 0)))
+
+    def set_variance_estimate(self, estimate=None):
+        """None (the default): off.  A make_variance_estimate(): render_denoised and render_accumulated (with a filter) run the variance
+        estimate between the stage that produces colour and variance and the a-trous filter.  Nothing is dropped by changing it."""
+        self._single("set_variance_estimate")
+        self._check(lib().crt_set_variance_estimate(self.ctx, C.byref(estimate) if estimate is not None else None))
+
+    def variance_estimate(self):
+        """The setting: a VarianceEstimate, or None when it is off."""
+        self._single("variance_estimate")
+        e = VarianceEstimate()
+        return e if lib().crt_get_variance_estimate(self.ctx, C.byref(e)) else None
 
     # ---- split GI frames (include/crt_hip.h: crt_split_fold_device, crt_split_recombine_device)
     def split_fold_device(self, d_rgb_ptr, d_direct_ptr, sample, d_dsum_ptr, d_rsum_ptr, d_rsq_ptr, n=None, d_pixels_ptr=None, stream_ptr=None):

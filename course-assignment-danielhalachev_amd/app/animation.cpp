@@ -71,11 +71,13 @@ int main(int argc, char **argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s scene.crtscene out_prefix [--folder DIR] [--depth N] [--fps F] [--seconds S] [--radius R] [--device D] "
                          "[--in-flight K] [--writers N] [--no-ppm]\n"
-                         "       [--gi SAMPLE_SIZE --adaptive THRESHOLD MIN MAX [--seed S] [--denoise [ITERATIONS]] [--temporal [MAX_HISTORY]] [--split] [--guide-bounces B]]   (GI frames, one at a\n"
+                         "       [--gi SAMPLE_SIZE --adaptive THRESHOLD MIN MAX [--seed S] [--denoise [ITERATIONS]] [--temporal [MAX_HISTORY]] [--split] [--guide-bounces B] [--variance-estimate [MIN_HISTORY]]]   (GI frames, one at a\n"
                          "        time: every pixel is shot MIN .. MAX times; --denoise: through crt_hip.h's crt_denoise; --temporal: merged with the\n"
                          "        history of the frames before it, crt_hip.h's crt_temporal, then through the filter if --denoise is given;\n"
                          "        --split: both act on the indirect light only, crt_hip.h's \"Split GI frames\";\n"
-                         "        --guide-bounces B, 0..63: the filter of --denoise runs under guides that follow mirrors and glass, crt_hip.h's \"Chain guides\")\n", argv[0]);
+                         "        --guide-bounces B, 0..63: the filter of --denoise runs under guides that follow mirrors and glass, crt_hip.h's \"Chain guides\";\n"
+                         "        --variance-estimate [MIN_HISTORY]: before the filter of --denoise a pixel whose moments stand for fewer samples gets a 7x7\n"
+                         "        estimate of its variance, crt_hip.h's \"Variance estimate\")\n", argv[0]);
     return 2;
   }
   std::string scenePath = argv[1], prefix = argv[2], folder;
@@ -90,6 +92,8 @@ int main(int argc, char **argv) {
   float adaptiveThreshold = 0.0f, maxHistory = -1.0f;  // (-1: crt_temporal_defaults')
   int denoiseIterations = -1;                          // (-1: crt_denoise_defaults')
   int guideBounces = -1;                               // (-1: not given)
+  bool varianceEstimate = false;
+  float minHistory = -1.0f;                            // (-1: crt_variance_estimate_defaults')
   auto number = [&](int i) { return i < argc && ((argv[i][0] >= '0' && argv[i][0] <= '9') || argv[i][0] == '.'); };
   for (int i = 3; i < argc; i++) {
     if (!strcmp(argv[i], "--folder") && i + 1 < argc) folder = argv[++i];
@@ -109,6 +113,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--denoise")) { denoise = true; if (number(i + 1)) denoiseIterations = atoi(argv[++i]); }
     else if (!strcmp(argv[i], "--split")) split = true;
     else if (!strcmp(argv[i], "--guide-bounces") && i + 1 < argc) guideBounces = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--variance-estimate")) { varianceEstimate = true; if (number(i + 1)) minHistory = (float)atof(argv[++i]); }
     else if (!strcmp(argv[i], "--temporal")) { temporal = true; if (number(i + 1)) maxHistory = (float)atof(argv[++i]); }
   }
   if (useGI != adaptive || ((denoise || temporal || split) && !useGI)) {
@@ -121,6 +126,11 @@ int main(int argc, char **argv) {
                          "usage: %s scene.crtscene out_prefix --gi SAMPLE_SIZE --adaptive THRESHOLD MIN MAX --denoise [ITERATIONS] [--temporal [MAX_HISTORY]] --guide-bounces B\n", argv[0]);
     return 2;
   }
+  if (varianceEstimate && !denoise) {
+    std::fprintf(stderr, "error: --variance-estimate needs --denoise\n"
+                         "usage: %s scene.crtscene out_prefix --gi SAMPLE_SIZE --adaptive THRESHOLD MIN MAX --denoise [ITERATIONS] [--temporal [MAX_HISTORY]] --variance-estimate [MIN_HISTORY]\n", argv[0]);
+    return 2;
+  }
   try {
     crt::SceneParser parser;
     crt::Scene scene = parser.parseScene(scenePath, folder);
@@ -129,6 +139,12 @@ int main(int argc, char **argv) {
     const unsigned W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
     crt::RenderOptions options(crt::BVHBucketsThreadPool, depth, useGI, giSamples, 1);
     if (guideBounces > 0) tracer.setGuideBounces((unsigned)guideBounces);
+    if (varianceEstimate) {
+      crt_variance_estimate e;
+      crt_variance_estimate_defaults(&e);
+      if (minHistory >= 0.0f) e.min_history = minHistory;
+      tracer.setVarianceEstimate(&e);
+    }
     if (useGI) tracer.setGISeed(seed);  // frame k uses seed + k: renderAdaptive takes the next one
     Writers writers(writeFiles ? (nWriters ? nWriters : 1) : 0, W, H);
     const float DEG_CHANGE = 360.0f / (FPS * SECONDS);

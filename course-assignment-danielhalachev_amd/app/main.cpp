@@ -22,11 +22,13 @@ int main(int argc, char **argv) {
                  "        --progressive: the same frame K samples a call, in memory that does not depend on RAYS_PER_PIXEL)\n"
                  "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL --adaptive THRESHOLD MIN MAX [--counts FILE]]   (every pixel is shot until the rule of\n"
                  "        crt_hip.h's crt_adaptive stops it, MIN .. MAX times; RAYS_PER_PIXEL is not read; --counts: the samples per pixel as a P2 PGM)\n"
-                 "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL --adaptive THRESHOLD MIN MAX --denoise [ITERATIONS] [--split] [--guide-bounces B]]   (out.ppm is that frame through\n"
+                 "       [--gi GI_SAMPLE_SIZE RAYS_PER_PIXEL --adaptive THRESHOLD MIN MAX --denoise [ITERATIONS] [--split] [--guide-bounces B] [--variance-estimate [MIN_HISTORY]]]   (out.ppm is that frame through\n"
                  "        the variance-guided a-trous filter of crt_hip.h's crt_denoise, its defaults but for ITERATIONS, 0..8; --split: the filter acts\n"
                  "        on the indirect light only and the direct light is added back, crt_hip.h's \"Split GI frames\"; it needs --adaptive;\n"
                  "        --guide-bounces B, 0..63: the filter runs under guides that follow mirrors and glass for up to B bounces, crt_hip.h's \"Chain guides\";\n"
-                 "        it needs --denoise)\n"
+                 "        it needs --denoise;\n"
+                 "        --variance-estimate [MIN_HISTORY]: a pixel whose moments stand for fewer samples gets a 7x7 estimate of its variance before the\n"
+                 "        filter, crt_hip.h's \"Variance estimate\", its defaults but for MIN_HISTORY; it needs --denoise)\n"
                  "       [--probe ROW COL]   (no render: the closest hit of that pixel's camera ray; out.ppm is not written)\n",
                  argv[0]);
     return 2;
@@ -45,6 +47,8 @@ int main(int argc, char **argv) {
   int denoiseIterations = -1;  // (-1: crt_denoise_defaults')
   bool split = false;
   int guideBounces = -1;  // (-1: not given)
+  bool varianceEstimate = false;
+  float minHistory = -1.0f;  // (-1: crt_variance_estimate_defaults')
   bool probe = false;
   unsigned probeRow = 0, probeCol = 0;
   for (int i = 3; i < argc; i++) {
@@ -78,6 +82,10 @@ int main(int argc, char **argv) {
     }
     else if (!strcmp(argv[i], "--split")) split = true;
     else if (!strcmp(argv[i], "--guide-bounces") && i + 1 < argc) guideBounces = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--variance-estimate")) {
+      varianceEstimate = true;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') minHistory = (float)atof(argv[++i]);
+    }
     else if (!strcmp(argv[i], "--probe") && i + 2 < argc) { probe = true; probeRow = (unsigned)atoi(argv[++i]); probeCol = (unsigned)atoi(argv[++i]); }
   }
   if (progressive && (!useGI || devices.size() > 0)) {
@@ -107,6 +115,11 @@ int main(int argc, char **argv) {
                  argv[0]);
     return 2;
   }
+  if (varianceEstimate && !denoise) {
+    std::fprintf(stderr, "error: --variance-estimate needs --denoise\nusage: %s scene.crtscene out.ppm --gi GI_SAMPLE_SIZE RAYS_PER_PIXEL --adaptive THRESHOLD MIN MAX --denoise [ITERATIONS] --variance-estimate [MIN_HISTORY]\n",
+                 argv[0]);
+    return 2;
+  }
   try {
     crt::SceneParser parser;
     crt::Scene scene = parser.parseScene(scenePath, folder);
@@ -128,6 +141,12 @@ int main(int argc, char **argv) {
     }
     crt::RenderOptions options((crt::RenderOptimization)mode, depth, useGI, giSamples, raysPerPixel);
     if (guideBounces > 0) tracer.setGuideBounces((unsigned)guideBounces);
+    if (varianceEstimate) {
+      crt_variance_estimate e;
+      crt_variance_estimate_defaults(&e);
+      if (minHistory >= 0.0f) e.min_history = minHistory;
+      tracer.setVarianceEstimate(&e);
+    }
     tracer.setGISeed(seed);  // frame r of this run uses seed + r (the reference's GI frames all differ: clock() ^ thread id)
     double best = 1e30;
     for (int r = 0; r < repeat; r++) {

@@ -12,6 +12,8 @@
 //   a split frame     crt_render_adaptive_split, crt_render_denoised_split, crt_render_accumulated_split: the three calls above with every
 //                     sample cut into its direct light and the rest (crt_split.hip, csrc/split_rule.h) -- the rest is what is filtered and
 //                     reprojected, the direct part is added back untouched
+//   the variance estimate  crt_set_variance_estimate: one launch more (crt_variance.hip) between the stage that produces colour and variance
+//                     and the a-trous filter of the denoised and accumulated calls, under the filter's guides
 // One body per stage: render_samples for the three sample-pass calls, post_begin and post_output around the two kinds of post-processing.
 // Which call may continue which frame, and when a history's `current` becomes `previous`: csrc/giframe_rule.h.
 #include "device_array.h"
@@ -68,6 +70,11 @@ struct crt_giframe_state {
     History hist[2];
     DeviceArray<float> acc_rgb, acc_var;
     DeviceArray<uint8_t> acc_valid;
+    // crt_set_variance_estimate: the setting (off by default), and for the denoised calls, which have no records, the moment records of
+    // the frame's state: written by the temporal launch with no history, read by the estimate, never a history slot
+    bool estimate_on = false;
+    crt_variance_estimate estimate{};
+    DeviceArray<crt_history_pixel> est_records;
     void new_frame() { guides = false; serial++; }   // the guides and `current` are the ended frame's
     ~crt_giframe_state() {
         if (pin_next_n) (void)hipHostFree(pin_next_n);
@@ -88,12 +95,17 @@ void giframe_reset(crt_ctx *ctx) {
     f->new_frame();
 }
 
-// a frame call's bracket and this file's state, made by the first one
-static int giframe_begin(crt_ctx *ctx, const CallKind kind) {
-    if (int rc = query_begin(ctx, ctx->stream, kind)) return rc;
+// this file's state, made by the first call that needs it
+static int giframe_state(crt_ctx *ctx) {
     if (!ctx->giframe) ctx->giframe = new (std::nothrow) crt_giframe_state;
     if (!ctx->giframe) { ctx->error = "out of memory"; return CRT_ERR_NOMEM; }
     return CRT_OK;
+}
+
+// a frame call's bracket
+static int giframe_begin(crt_ctx *ctx, const CallKind kind) {
+    if (int rc = query_begin(ctx, ctx->stream, kind)) return rc;
+    return giframe_state(ctx);
 }
 
 // the adaptive calls' pinned word, made by the first of them (a uniform frame reads nothing back)
@@ -408,6 +420,25 @@ extern "C" int crt_set_guide_bounces(crt_ctx *ctx, uint32_t max_bounces) {
 }
 extern "C" uint32_t crt_guide_bounces(const crt_ctx *ctx) { return ctx ? ctx->guide_bounces : 0u; }
 
+// the setting alone: the guides, the histories and the frame's serial stay
+extern "C" int crt_set_variance_estimate(crt_ctx *ctx, const crt_variance_estimate *est) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (!est) {
+        if (ctx->giframe) ctx->giframe->estimate_on = false;
+        return CRT_OK;
+    }
+    int rc;
+    if ((rc = variance_check(ctx, "crt_set_variance_estimate", est)) || (rc = giframe_state(ctx))) return rc;
+    ctx->giframe->estimate = *est;
+    ctx->giframe->estimate_on = true;
+    return CRT_OK;
+}
+extern "C" int crt_get_variance_estimate(const crt_ctx *ctx, crt_variance_estimate *out) {
+    const bool on = ctx && ctx->giframe && ctx->giframe->estimate_on;
+    if (on && out) *out = ctx->giframe->estimate;
+    return on ? 1 : 0;
+}
+
 // What the denoised and -- `accumulated` -- the accumulated calls do before their own launches: the settings' checks (the accumulated
 // call's filter is optional), the frame's, the call bracket, room for what the call writes, the guides.
 static int post_begin(crt_ctx *ctx, const char *what, const bool split, const bool accumulated, const crt_temporal *temporal, const crt_denoise *denoise) {
@@ -422,6 +453,7 @@ static int post_begin(crt_ctx *ctx, const char *what, const bool split, const bo
     if ((rc = reserve_all(ctx, f->den_hits, pixels, f->den_q8, 3 * pixels)) ||
         (rc = accumulated ? reserve_all(ctx, hist.slot[0], pixels, hist.slot[1], pixels, f->acc_rgb, 3 * pixels, f->acc_var, pixels, f->acc_valid, pixels)
                           : reserve_all(ctx, f->den_mean, 3 * pixels, f->den_var, pixels)) ||
+        (!accumulated && f->estimate_on && (rc = reserve_all(ctx, f->est_records, pixels))) ||
         (denoise && (rc = reserve_all(ctx, f->den_out, 3 * pixels, f->den_work, float4s(crt_denoise_work_bytes(ctx->width, ctx->height))))))
         return rc;
     return frame_guides(ctx, pixels);
@@ -450,14 +482,31 @@ static FoldState fold_state(const crt_giframe_state *f, const bool split) {
     return split ? FoldState{f->split_rsum.p, f->split_rsq.p} : FoldState{f->prog_sum.p, f->prog_sq.p};
 }
 
+// crt_set_variance_estimate: one launch between the stage that produces colour and variance and the a-trous filter, under the filter's
+// guides; the variance is replaced in place, the colour is not touched
+static int estimate_stage(crt_ctx *ctx, const crt_history_pixel *d_moments, float *d_var) {
+    return variance_launch(ctx, &ctx->giframe->estimate, ctx->width, ctx->height, d_moments, filter_guides(ctx), d_var, d_var, ctx->stream);
+}
+
 // crt_render_denoised and, `split`, crt_render_denoised_split: the rest is filtered and the direct part's mean added back untouched
 static int render_denoised(crt_ctx *ctx, const char *what, const bool split, const crt_denoise *denoise, float *out_rgb, uint8_t *out_rgb8) {
     int rc;
     if ((rc = post_begin(ctx, what, split, false, nullptr, denoise))) return rc;
     crt_giframe_state *f = ctx->giframe;
     const FoldState state = fold_state(f, split);
-    if ((rc = denoise_launch_variance(ctx, state.sum, state.sq, f->prog_counts.p, (uint64_t)ctx->width * ctx->height, f->den_mean.p, f->den_var.p, ctx->stream)) ||
-        (rc = denoise_launch(ctx, denoise, ctx->width, ctx->height, f->den_mean.p, f->den_var.p, filter_guides(ctx), f->den_out.p, nullptr, f->den_work.p,
+    if (f->estimate_on) {
+        // the call has no records: the temporal launch with no history writes {G, C_c, q_c, n_c} into scratch records -- no history ledger,
+        // slot or frame count is involved --, and its colour and variance are crt_sample_variance_device's, bit for bit (temporal_rule.h)
+        crt_temporal none;
+        crt_temporal_defaults(&none);
+        if ((rc = temporal_launch(ctx, &none, ctx->width, ctx->height, nullptr, nullptr, state.sum, state.sq, f->prog_counts.p, f->den_hits.p,
+                                  f->est_records.p, f->den_mean.p, f->den_var.p, nullptr, ctx->stream)) ||
+            (rc = estimate_stage(ctx, f->est_records.p, f->den_var.p)))
+            return rc;
+    } else if ((rc = denoise_launch_variance(ctx, state.sum, state.sq, f->prog_counts.p, (uint64_t)ctx->width * ctx->height, f->den_mean.p, f->den_var.p,
+                                             ctx->stream)))
+        return rc;
+    if ((rc = denoise_launch(ctx, denoise, ctx->width, ctx->height, f->den_mean.p, f->den_var.p, filter_guides(ctx), f->den_out.p, nullptr, f->den_work.p,
                              ctx->stream)))
         return rc;
     return post_output(ctx, split, f->den_out.p, out_rgb, out_rgb8, nullptr);
@@ -489,7 +538,8 @@ static int render_accumulated(crt_ctx *ctx, const char *what, const bool split, 
     memcpy(hist.pose[cur].position, ctx->frame.cam_pos, sizeof(hist.pose[cur].position));
     memcpy(hist.pose[cur].matrix, ctx->frame.cam, sizeof(hist.pose[cur].matrix));
     float *result = f->acc_rgb.p;
-    if (denoise) {
+    if (denoise) {   // (without a spatial stage there is nothing the estimate would serve)
+        if (f->estimate_on && (rc = estimate_stage(ctx, hist.slot[cur].p, f->acc_var.p))) return rc;
         if ((rc = denoise_launch(ctx, denoise, ctx->width, ctx->height, f->acc_rgb.p, f->acc_var.p, filter_guides(ctx), f->den_out.p, nullptr, f->den_work.p,
                                  ctx->stream)))
             return rc;

@@ -12,6 +12,7 @@
 //   crt_temporal.hip  the temporal accumulation's primitive: the last frame's history reprojected and merged with the fold's state
 //   crt_split.hip     the split GI frames' primitives: a sample's direct light kept, the fold of the two parts, putting them back together
 //   crt_guides.hip    the chain guides' kernel launch and work-area layout: filter guides that follow mirrors and glass
+//   crt_variance.hip  the variance estimate's primitive: a 7x7 cross-bilateral estimate of the variance where a pixel's history is short
 //   crt_testhooks.hip unit-test hooks (libcrt_hip_test.so only)
 #pragma once
 
@@ -211,6 +212,10 @@ CRT_INTERNAL int temporal_check(crt_ctx *ctx, const char *what, const crt_tempor
 CRT_INTERNAL int temporal_launch(crt_ctx *ctx, const crt_temporal *t, uint32_t width, uint32_t height, const crt_camera_pose *prev_pose,
                                  const crt_history_pixel *d_prev, const float *d_sum, const float *d_sq, const uint32_t *d_counts, const crt_hit *d_hits,
                                  crt_history_pixel *d_next, float *d_out_rgb, float *d_out_var, uint8_t *d_out_valid, hipStream_t stream);
+// ---- crt_variance.hip: the variance estimate's settings check and launch, for the frame calls' setting (crt_giframe.hip)
+CRT_INTERNAL int variance_check(crt_ctx *ctx, const char *what, const crt_variance_estimate *e);
+CRT_INTERNAL int variance_launch(crt_ctx *ctx, const crt_variance_estimate *e, uint32_t width, uint32_t height, const crt_history_pixel *d_moments,
+                                 const crt_hit *d_hits, const float *d_var, float *d_out_var, hipStream_t stream);
 // ---- crt_split.hip: the split GI frames' launches, for the radiance passes (crt_query.hip) and the *_split frame calls (crt_giframe.hip)
 CRT_INTERNAL int split_launch_keep_direct(crt_ctx *ctx, const uint8_t *d_status, const float *d_rgb, uint32_t n, uint32_t gi_sample_size, float *d_direct,
                                           hipStream_t stream);

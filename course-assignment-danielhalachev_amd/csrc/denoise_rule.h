@@ -64,7 +64,8 @@
 //     weight alone.  The split frames (csrc/split_rule.h) feed this rule the indirect light only and add the direct light, which carries
 //     the texels, back untouched.
 //   * Reflections in a flat mirror are guided by the mirror's own plane.
-//   * With count == 1 every variance is 0, so the filter hardly smooths.  Use at least 2 samples.
+//   * With count == 1 every variance is 0, so the filter hardly smooths.  Use at least 2 samples -- or the variance estimate
+//     (csrc/variance_rule.h), which replaces the variance of such pixels before this rule runs.
 #pragma once
 
 #include <math.h>

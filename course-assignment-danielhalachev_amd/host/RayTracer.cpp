@@ -215,6 +215,11 @@ void RayTracer::setGuideBounces(unsigned int maxBounces) {
   if (crt_set_guide_bounces(ctx, maxBounces) != CRT_OK) throw std::runtime_error(std::string("setGuideBounces failed: ") + crt_last_error(ctx));
 }
 
+void RayTracer::setVarianceEstimate(const crt_variance_estimate *estimate) {
+  if (multi) throw std::runtime_error("setVarianceEstimate: not available on a multi-device tracer");
+  if (crt_set_variance_estimate(ctx, estimate) != CRT_OK) throw std::runtime_error(std::string("setVarianceEstimate failed: ") + crt_last_error(ctx));
+}
+
 unsigned int RayTracer::guideBounces() const { return multi ? 0u : crt_guide_bounces(ctx); }
 
 std::vector<unsigned char> RayTracer::occludedRays(const std::vector<crt_ray> &rays, const std::vector<float> &maxDistance) {

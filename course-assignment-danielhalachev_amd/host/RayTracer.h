@@ -128,6 +128,9 @@ class RayTracer {
   // centre rays (crt_set_guide_bounces); the temporal stage keeps the first hits
   void setGuideBounces(unsigned int maxBounces);
   unsigned int guideBounces() const;
+  // null (the default): off; otherwise renderDenoised and renderAccumulated (with a filter) estimate the variance of pixels whose moments
+  // stand for fewer than estimate->min_history samples from their 7x7 neighbourhood before the filter (crt_set_variance_estimate)
+  void setVarianceEstimate(const crt_variance_estimate *estimate);
 
   // ---- progressive GI frames (crt_hip.h: crt_render_progressive): render()'s USE_GI frame with renderOptions.RAYS_PER_PIXEL rays per
   // pixel, samplesPerCall samples a call, in memory that does not depend on RAYS_PER_PIXEL; the frame's seed is taken as render() takes

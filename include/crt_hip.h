@@ -673,7 +673,8 @@ uint64_t crt_progressive_active(const crt_ctx *ctx);
  *   the colour weight alone -- in THIS call; crt_render_denoised_split ("Split GI frames", below) filters the indirect light only and
  *   adds the direct light, which carries the texels, back untouched.  Reflections in a flat mirror are guided by the mirror's own plane
  *   while crt_guide_bounces(ctx) is 0, the default: "Chain guides", below, gives such pixels the guide of the surface they show.  With count == 1 every variance is 0, so
- *   the filter hardly smooths: use at least 2 samples.
+ *   the filter hardly smooths: use at least 2 samples -- or crt_set_variance_estimate ("Variance estimate", below), which estimates the
+ *   variance of such pixels from their neighbours.
  * crt_denoise: size must be sizeof(crt_denoise) = 24, iterations <= 8, normal_squarings <= 16, sigma_colour and sigma_plane >= 0 and finite,
  *   floor > 0 and finite: anything else is CRT_ERR_INVALID, with nothing enqueued.  crt_denoise_defaults: 4, 5, 2.0f, 0.02f, 1e-6f.
  * crt_sample_variance_device: for i < n_pixels the lines "from the fold's state" on d_sum[3i ..], d_sq[i], d_counts[i] -- the arrays
@@ -968,6 +969,89 @@ int crt_guide_rays_device(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint3
                           crt_ray *d_out_last_rays /* may be NULL: the terminal segment's crt_ray */, void *d_work, void *stream);
 int crt_set_guide_bounces(crt_ctx *ctx, uint32_t max_bounces);
 uint32_t crt_guide_bounces(const crt_ctx *ctx);
+
+/* ---- Variance estimate: SVGF's variance-estimation stage.  The a-trous filter's colour weight is den / (den + d2) with
+ * den = sigma_colour^2 x vp + floor: where a pixel's variance is 0 or unreliable -- one sample and no history: the first frame after
+ * crt_history_reset, every disoccluded pixel of a moving camera, every pixel the adaptive rule stopped early -- the weight closes and the
+ * noise passes through.  Where the number of samples a pixel's moments stand for is below a threshold, this stage replaces the pixel's
+ * variance of the mean by a 7x7 cross-bilateral estimate from the moments of geometrically similar neighbours.  Only the variance is
+ * replaced; the colour is never touched.  Kernel: csrc/kernel_variance.h (variance_estimate: a 32x8 tile whose 38x14 halo is staged in LDS
+ * once, and tiles without a flagged pixel copy); the rule, one header for host and device: csrc/variance_rule.h; tests/variance_sets.py
+ * restates it.  It is additive: no frame, query, radiance, denoise, temporal, split or guide kernel is involved, and with the setting off,
+ * the default, every call gives the bits it gave before.  Single-device contexts only.
+ *
+ * The rule.  Every line is one float32 operation with one rounding, in the order written; there is no exp, pow or sqrt.
+ * Definitions.  finite(x) is (x - x) == 0.0f.  A moment record is M = {c[3], m2, weight}, the fields of a crt_history_pixel (the record's
+ *   own guide fields are not read).  usable(M): weight > 0 and c[0..2], m2, weight all finite.  A guide is G = {n[3], x[3], t, mesh}, taken
+ *   from a crt_hit as the denoiser takes it (mesh = 0xFFFFFFFF when hit == 0).  V_in is the incoming
+ *   variance of the mean.  The window radius is 3 and is not a setting.
+ * Centre p = (y, x) of a width x height image.  It passes through, V' = V_in, when
+ *     !usable(M_p), or mesh_p is a miss, or !(weight_p < min_history)
+ * Otherwise the centre is FLAGGED:
+ *     tol = sigma_plane * t_p
+ *     acc = {0,0,0}; accq = 0; wsum = 0
+ *     for dy in -3..3, dx in -3..3 (row-major), q = (y+dy, x+dx); the offsets are compared with the room the centre has before a coordinate is formed:
+ *         skip q outside the frame
+ *         skip q with !usable(M_q)
+ *         skip q with mesh_q != mesh_p
+ *         d  = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z
+ *         d  = d > 0 ? d : 0
+ *         d  = d * d, normal_squarings times
+ *         e  = (n_p.x*(x_q.x - x_p.x) + n_p.y*(x_q.y - x_p.y)) + n_p.z*(x_q.z - x_p.z)
+ *         ae = fabsf(e)
+ *         skip unless ae <= tol                      // a NaN skips
+ *         wz = tol > 0 ? 1.0f - ae / tol : 1.0f
+ *         w  = d * wz
+ *         acc_c = acc_c + w * c_q,c
+ *         accq  = accq + w * m2_q
+ *         wsum  = wsum + w
+ *     if wsum > 0:
+ *         inv = 1.0f / wsum
+ *         Cb_c = acc_c * inv
+ *         qb  = accq * inv
+ *         mm  = (Cb_r*Cb_r + Cb_g*Cb_g) + Cb_b*Cb_b
+ *         var = qb - mm
+ *         iw  = 1.0f / weight_p
+ *         V'  = (var > 0 ? var : 0) * iw
+ *     else:
+ *         V' = V_in                                  // a flagged centre with no surviving tap, or a NaN weight sum
+ *   The centre is its own tap (dy = dx = 0).  A NaN that arises from overflow or from a non-finite guide is whatever these lines give: a NaN
+ *   w makes wsum NaN, and the centre passes through.  The geometry lines are the denoiser's own.
+ * Known limits.  A miss pixel is never estimated.  The estimate is spatial: where the neighbourhood is a texture or a shadow edge inside
+ *   one mesh and plane, the detail counts as variance and the filter smooths it more; the split calls hand this rule the moments of the
+ *   indirect light only.  The window is 7x7 and dense; it does not widen where few taps survive.
+ * crt_variance_estimate: size must be sizeof(crt_variance_estimate) = 16, min_history > 0 and finite, normal_squarings <= 16, sigma_plane
+ *   >= 0 and finite: anything else is CRT_ERR_INVALID, with nothing enqueued.  crt_variance_estimate_defaults: 4.0f, 5, 0.02f.
+ * crt_variance_estimate_device: the rule for every pixel of a width x height image of the caller's: d_moments (one crt_history_pixel a
+ *   pixel, row-major, aligned to 16 bytes; c, m2 and weight are read), d_hits (one crt_hit a pixel: the guides), d_var (one float a
+ *   pixel: V_in) into d_out_var.  d_out_var may be d_var, because a pixel reads only its own V_in; no other overlap is allowed.
+ *   CRT_ERR_INVALID, with nothing enqueued: an invalid crt_variance_estimate (above), width * height >= 2^31, a NULL array, d_moments not
+ *   aligned to 16 bytes.  width * height of 0 with non-NULL arrays is CRT_OK and touches nothing.  It only ENQUEUES on `stream` (a
+ *   hipStream_t, NULL = default): one launch, no wait, no allocation, no readback; it can be captured into a graph.  It composes on one
+ *   stream between crt_temporal_device -- whose d_next is its d_moments and whose d_out_var is its d_var -- and crt_denoise_device.
+ * crt_set_variance_estimate / crt_get_variance_estimate: the frame calls' setting, off by default; NULL turns it off.  An invalid struct is
+ *   CRT_ERR_INVALID and leaves the setting as it was.  Changing it drops nothing: not the guides, not the history, not the frame's serial.
+ *   crt_get_variance_estimate returns 1 and copies the setting to *out (which may be NULL) when it is on, 0 when it is off.  With it on,
+ *   crt_render_denoised, crt_render_accumulated and their _split forms run the estimate between the stage that produces colour and variance
+ *   and the a-trous filter, under the guides the filter runs under: chain guides when crt_guide_bounces(ctx) > 0, first hits otherwise.
+ *   The accumulated calls take the records the merge just wrote to `current` (split: the moments of the rest); with denoise == NULL they
+ *   skip the estimate, since there is no spatial stage to serve.  The denoised calls have no records: they run the temporal launch with no
+ *   history (d_prev == NULL) into a context-owned scratch record array, allocated on first use and freed by crt_destroy, in place of
+ *   crt_sample_variance_device's launch -- by the temporal rule its colour and variance are that call's, bit for bit, and its records are
+ *   {G, C_c, q_c, n_c}.  That touches neither history: no ledger, slot or frame count.  Everything else -- the frame, its sums, counts and
+ *   lists, crt_stats, the histories -- is left as it is with the setting off, so a frame can still be processed after any pass and
+ *   continued. */
+typedef struct crt_variance_estimate {
+    uint32_t size;              /* sizeof(crt_variance_estimate) = 16 */
+    float min_history;          /* > 0, finite: a pixel whose record stands for fewer samples than this is estimated */
+    uint32_t normal_squarings;  /* 0..16 */
+    float sigma_plane;          /* >= 0, finite: a tap may lie sigma_plane x t off the centre's tangent plane */
+} crt_variance_estimate;
+void crt_variance_estimate_defaults(crt_variance_estimate *est);   /* 4.0f, 5, 0.02f */
+int crt_variance_estimate_device(crt_ctx *ctx, const crt_variance_estimate *est, uint32_t width, uint32_t height,
+                                 const crt_history_pixel *d_moments, const crt_hit *d_hits, const float *d_var, float *d_out_var, void *stream);
+int crt_set_variance_estimate(crt_ctx *ctx, const crt_variance_estimate *est /* NULL: off */);
+int crt_get_variance_estimate(const crt_ctx *ctx, crt_variance_estimate *out /* may be NULL */);
 
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
