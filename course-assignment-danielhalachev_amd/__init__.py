@@ -136,15 +136,20 @@ class Adaptive(C.Structure):
     _fields_ = [("size", C.c_uint32), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("threshold", C.c_float), ("floor", C.c_float)]
 
 
+def _make_settings(kind, name, fields, reserved=("size",), cast=None):
+    """a `kind` structure as crt_<name>_defaults fills it, with the given fields replaced"""
+    s = kind()
+    getattr(lib(), "crt_%s_defaults" % name)(C.byref(s))
+    for k, v in fields.items():
+        if k not in dict(kind._fields_) or k in reserved:
+            raise KeyError("crt_%s has no field %r" % (name, k))
+        setattr(s, k, cast(v) if cast else v)
+    return s
+
+
 def make_adaptive(**fields):
     """crt_adaptive_defaults (4, 64, 0.05, 1e-4) with the given fields replaced, e.g. make_adaptive(min_samples=2, max_samples=8)."""
-    a = Adaptive()
-    lib().crt_adaptive_defaults(C.byref(a))
-    for k, v in fields.items():
-        if k not in dict(Adaptive._fields_) or k == "size":
-            raise KeyError("crt_adaptive has no field %r" % k)
-        setattr(a, k, v)
-    return a
+    return _make_settings(Adaptive, "adaptive", fields)
 
 
 class Denoise(C.Structure):
@@ -155,13 +160,7 @@ class Denoise(C.Structure):
 
 def make_denoise(**fields):
     """crt_denoise_defaults (4, 5, 2.0, 0.02, 1e-6) with the given fields replaced, e.g. make_denoise(iterations=3)."""
-    d = Denoise()
-    lib().crt_denoise_defaults(C.byref(d))
-    for k, v in fields.items():
-        if k not in dict(Denoise._fields_) or k == "size":
-            raise KeyError("crt_denoise has no field %r" % k)
-        setattr(d, k, v)
-    return d
+    return _make_settings(Denoise, "denoise", fields)
 
 
 class Temporal(C.Structure):
@@ -176,13 +175,7 @@ class CameraPose(C.Structure):
 
 def make_temporal(**fields):
     """crt_temporal_defaults (64.0, 0.9, 0.02) with the given fields replaced, e.g. make_temporal(max_history=16.0)."""
-    t = Temporal()
-    lib().crt_temporal_defaults(C.byref(t))
-    for k, v in fields.items():
-        if k not in dict(Temporal._fields_) or k == "size":
-            raise KeyError("crt_temporal has no field %r" % k)
-        setattr(t, k, v)
-    return t
+    return _make_settings(Temporal, "temporal", fields)
 
 
 class VarianceEstimate(C.Structure):
@@ -192,13 +185,7 @@ class VarianceEstimate(C.Structure):
 
 def make_variance_estimate(**fields):
     """crt_variance_estimate_defaults (4.0, 5, 0.02) with the given fields replaced, e.g. make_variance_estimate(min_history=2.0)."""
-    e = VarianceEstimate()
-    lib().crt_variance_estimate_defaults(C.byref(e))
-    for k, v in fields.items():
-        if k not in dict(VarianceEstimate._fields_) or k == "size":
-            raise KeyError("crt_variance_estimate has no field %r" % k)
-        setattr(e, k, v)
-    return e
+    return _make_settings(VarianceEstimate, "variance_estimate", fields)
 
 
 def make_pose(position, matrix):
@@ -233,13 +220,7 @@ class Tuning(C.Structure):
 
 def make_tuning(**fields):
     """Default tuning (crt_tuning_defaults) with the given fields replaced, e.g. make_tuning(mode=MODE_LANES)."""
-    t = Tuning()
-    lib().crt_tuning_defaults(C.byref(t))
-    for k, v in fields.items():
-        if k not in dict(Tuning._fields_) or k in ("size", "reserved"):
-            raise KeyError("crt_tuning has no field %r" % k)
-        setattr(t, k, int(v))
-    return t
+    return _make_settings(Tuning, "tuning", fields, reserved=("size", "reserved"), cast=int)
 
 
 def tuning_from_string(text):

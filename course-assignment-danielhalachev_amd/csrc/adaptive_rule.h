@@ -21,15 +21,7 @@
 // has var <= 0 up to rounding and stops at min_samples.
 #pragma once
 
-#include <stdint.h>
-
-#ifndef CRT_HD
-#if defined(__HIPCC__) || defined(__HIP__)
-#define CRT_HD __host__ __device__ __forceinline__
-#else
-#define CRT_HD static inline
-#endif
-#endif
+#include "filter_rule.h"
 
 // what the rule reads of a crt_adaptive (include/crt_hip.h)
 struct crt_adaptive_rule {
@@ -44,16 +36,15 @@ CRT_HD bool crt_adaptive_step(const crt_adaptive_rule rule, const uint32_t s, co
     sum[0] = (s == 0u ? 0.0f : sum[0]) + r;
     sum[1] = (s == 0u ? 0.0f : sum[1]) + g;
     sum[2] = (s == 0u ? 0.0f : sum[2]) + b;
-    const float rr = r * r, gg = g * g, bb = b * b;
-    const float c2 = (rr + gg) + bb;
+    const float c[3] = {r, g, b};
+    const float c2 = crt_sum3(c, c);
     *sq = (s == 0u ? 0.0f : *sq) + c2;
     const float inv = 1.0f / (float)n;
     mean[0] = sum[0] * inv;
     mean[1] = sum[1] * inv;
     mean[2] = sum[2] * inv;
     const float q = *sq * inv;
-    const float m0 = mean[0] * mean[0], m1 = mean[1] * mean[1], m2 = mean[2] * mean[2];
-    const float mm = (m0 + m1) + m2;
+    const float mm = crt_sum3(mean, mean);
     const float var = q - mm;
     const float t2 = rule.threshold * rule.threshold;
     const float t2n = t2 * (float)n;

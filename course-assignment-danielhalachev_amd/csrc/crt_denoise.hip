@@ -9,10 +9,9 @@ namespace {
 }  // namespace
 
 static_assert(sizeof(crt_denoise) == 24, "include/crt_hip.h says 24");
-static_assert(sizeof(crt_denoise_guide) == 32 && sizeof(crt_denoise_pixel) == 16 && sizeof(crt_hit) == 48, "the records of the work area");
+static_assert(sizeof(crt_guide) == 32 && sizeof(crt_denoise_pixel) == 16 && sizeof(crt_hit) == 48, "the records of the work area");
 // the work area: the guides, then the two {r, g, b, V} buffers
-constexpr uint64_t DENOISE_WORK_PER_PIXEL = sizeof(crt_denoise_guide) + 2 * sizeof(crt_denoise_pixel);
-constexpr uint64_t DENOISE_MAX_PIXELS = 1ull << 31;   // width * height stays below it: pixel coordinates are int32_t
+constexpr uint64_t DENOISE_WORK_PER_PIXEL = sizeof(crt_guide) + 2 * sizeof(crt_denoise_pixel);
 
 extern "C" void crt_denoise_defaults(crt_denoise *d) {
     if (!d) return;
@@ -35,9 +34,7 @@ int denoise_check(crt_ctx *ctx, const char *what, const crt_denoise *d) {
     else if (!(d->sigma_colour >= 0.0f) || !std::isfinite(d->sigma_colour)) why = "sigma_colour is negative or not finite";
     else if (!(d->sigma_plane >= 0.0f) || !std::isfinite(d->sigma_plane)) why = "sigma_plane is negative or not finite";
     else if (!(d->floor > 0.0f) || !std::isfinite(d->floor)) why = "floor is not finite or not above 0";
-    if (!why) return CRT_OK;
-    ctx->error = std::string(what) + ": " + why;
-    return CRT_ERR_INVALID;
+    return why ? refuse(ctx, what, why) : (int)CRT_OK;
 }
 
 int denoise_launch_variance(crt_ctx *ctx, const float *d_sum, const float *d_sq, const uint32_t *d_counts, uint64_t n, float *d_mean, float *d_var,
@@ -57,7 +54,7 @@ int denoise_launch(crt_ctx *ctx, const crt_denoise *d, uint32_t width, uint32_t 
         if (d_out_var && d_out_var != d_var) CRT_HIP_CHECK(ctx, hipMemcpyAsync(d_out_var, d_var, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
         return CRT_OK;
     }
-    crt_denoise_guide *guides = (crt_denoise_guide *)d_work;
+    crt_guide *guides = (crt_guide *)d_work;
     crt_denoise_pixel *buf[2];
     buf[0] = (crt_denoise_pixel *)(guides + n);
     buf[1] = buf[0] + n;
@@ -67,9 +64,9 @@ int denoise_launch(crt_ctx *ctx, const crt_denoise *d, uint32_t width, uint32_t 
     DenoiseAtrousArgs A{};
     A.rule = crt_denoise_rule{d->normal_squarings, d->sigma_colour, d->sigma_plane, d->floor};
     A.width = (int32_t)width; A.height = (int32_t)height;
-    A.tiles_x = (width + DENOISE_TILE_X - 1) / DENOISE_TILE_X;
+    A.tiles_x = tiles_x_of(width);
     A.guides = guides;
-    const uint32_t tiles_y = (height + DENOISE_TILE_Y - 1) / DENOISE_TILE_Y;
+    const uint32_t tiles_y = tiles_y_of(height);
     for (uint32_t k = 0; k < d->iterations; k++) {
         const bool last = k + 1 == d->iterations;
         A.step = (int32_t)(1u << k);
@@ -77,7 +74,7 @@ int denoise_launch(crt_ctx *ctx, const crt_denoise *d, uint32_t width, uint32_t 
         A.out = last ? nullptr : buf[(k & 1u) ^ 1u];
         A.out_rgb = last ? d_out_rgb : nullptr;
         A.out_var = last ? d_out_var : nullptr;
-        hipLaunchKernelGGL(denoise_atrous, dim3(A.tiles_x * tiles_y), dim3(DENOISE_TILE_X, DENOISE_TILE_Y), 0, stream, A);
+        hipLaunchKernelGGL(denoise_atrous, dim3(A.tiles_x * tiles_y), dim3(TILE_X, TILE_Y), 0, stream, A);
         CRT_HIP_CHECK(ctx, hipGetLastError());
     }
     return CRT_OK;
@@ -88,11 +85,8 @@ extern "C" int crt_sample_variance_device(crt_ctx *ctx, const float *d_sum, cons
     const char *what = "crt_sample_variance_device";
     if (!ctx) return CRT_ERR_INVALID;
     if (n_pixels == 0) return CRT_OK;
-    if (!d_sum || !d_sq || !d_counts || !d_mean || !d_var) {
-        ctx->error = std::string(what) + ": d_sum, d_sq, d_counts, d_mean or d_var is NULL";
-        return CRT_ERR_INVALID;
-    }
-    if ((n_pixels + BLOCK - 1) / BLOCK > 0x7FFFFFFFull) { ctx->error = std::string(what) + ": more pixels than one launch holds"; return CRT_ERR_INVALID; }
+    if (!d_sum || !d_sq || !d_counts || !d_mean || !d_var) return refuse(ctx, what, "d_sum, d_sq, d_counts, d_mean or d_var is NULL");
+    if ((n_pixels + BLOCK - 1) / BLOCK > 0x7FFFFFFFull) return refuse(ctx, what, "more pixels than one launch holds");
     CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     return denoise_launch_variance(ctx, d_sum, d_sq, d_counts, n_pixels, d_mean, d_var, (hipStream_t)stream);
 }
@@ -103,12 +97,9 @@ extern "C" int crt_denoise_device(crt_ctx *ctx, const crt_denoise *denoise, uint
     if (!ctx) return CRT_ERR_INVALID;
     if (int rc = denoise_check(ctx, what, denoise)) return rc;
     const uint64_t n = (uint64_t)width * height;
-    if (n >= DENOISE_MAX_PIXELS) { ctx->error = std::string(what) + ": width * height = " + std::to_string(n) + " >= 2^31"; return CRT_ERR_INVALID; }
-    if (!d_rgb || !d_var || !d_hits || !d_out_rgb || !d_work) {
-        ctx->error = std::string(what) + ": d_rgb, d_var, d_hits, d_out_rgb or d_work is NULL";
-        return CRT_ERR_INVALID;
-    }
-    if ((uintptr_t)d_work % 16u) { ctx->error = std::string(what) + ": d_work must be aligned to 16 bytes"; return CRT_ERR_INVALID; }
+    if (int rc = pixels_check(ctx, what, n)) return rc;
+    if (!d_rgb || !d_var || !d_hits || !d_out_rgb || !d_work) return refuse(ctx, what, "d_rgb, d_var, d_hits, d_out_rgb or d_work is NULL");
+    if ((uintptr_t)d_work % 16u) return refuse(ctx, what, "d_work must be aligned to 16 bytes");
     if (n == 0) return CRT_OK;
     CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     return denoise_launch(ctx, denoise, width, height, d_rgb, d_var, d_hits, d_out_rgb, d_out_var, d_work, (hipStream_t)stream);

@@ -114,11 +114,6 @@ static int pin_reserve(crt_ctx *ctx, uint32_t *&pin) {
     return CRT_OK;
 }
 
-static int refuse(crt_ctx *ctx, const char *what, const std::string &why) {
-    ctx->error = std::string(what) + ": " + why;
-    return CRT_ERR_INVALID;
-}
-
 // ---- progressive GI frames (csrc/kernel_progressive.h): the frame's left fold over a pixel's samples, cut into sample passes.
 
 // what the two primitives ask of (d_pixels, n): without a list the call is for the whole frame; one thread per entry must fit a grid
@@ -381,7 +376,7 @@ static int adaptive_frame_check(crt_ctx *ctx, const char *what, const bool split
                                  "with min_samples = max_samples");
     if (split && kind != FRAME_ADAPTIVE_SPLIT)
         return refuse(ctx, what, "the frame under way is an UNSPLIT adaptive frame, which keeps no direct part: crt_render_adaptive_split makes a split one");
-    if ((uint64_t)ctx->width * ctx->height >= (1ull << 31)) return refuse(ctx, what, "width * height >= 2^31");
+    if ((uint64_t)ctx->width * ctx->height >= CRT_MAX_PIXELS) return refuse(ctx, what, "width * height >= 2^31");
     return CRT_OK;
 }
 

@@ -164,6 +164,18 @@ extern CRT_INTERNAL std::string g_create_error;   // crt_scene.hip
         }                                                                                           \
     } while (0)
 
+// an invalid call: the message is "<what>: <why>"
+static inline int refuse(crt_ctx *ctx, const char *what, const std::string &why) {
+    ctx->error = std::string(what) + ": " + why;
+    return CRT_ERR_INVALID;
+}
+
+// width * height of an image the filter stages take stays below it: pixel coordinates are int32_t
+constexpr uint64_t CRT_MAX_PIXELS = 1ull << 31;
+static inline int pixels_check(crt_ctx *ctx, const char *what, const uint64_t n) {
+    return n >= CRT_MAX_PIXELS ? refuse(ctx, what, "width * height = " + std::to_string(n) + " >= 2^31") : (int)CRT_OK;
+}
+
 template <typename T>
 static int upload(crt_ctx *ctx, const T *src, size_t count, const T **dst) {
     void *p = nullptr;

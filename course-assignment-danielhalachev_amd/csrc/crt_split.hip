@@ -45,10 +45,7 @@ extern "C" int crt_split_fold_device(crt_ctx *ctx, const float *d_rgb, const flo
     if (!ctx) return CRT_ERR_INVALID;
     if (int rc = progressive_check(ctx, what, d_pixels, n)) return rc;
     if (n == 0) return CRT_OK;
-    if (!d_rgb || !d_direct || !d_dsum || !d_rsum || !d_rsq) {
-        ctx->error = std::string(what) + ": d_rgb, d_direct, d_dsum, d_rsum or d_rsq is NULL";
-        return CRT_ERR_INVALID;
-    }
+    if (!d_rgb || !d_direct || !d_dsum || !d_rsum || !d_rsq) return refuse(ctx, what, "d_rgb, d_direct, d_dsum, d_rsum or d_rsq is NULL");
     CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     return split_launch_fold(ctx, d_rgb, d_direct, d_pixels, n, sample, d_dsum, d_rsum, d_rsq, (hipStream_t)stream);
 }
@@ -57,15 +54,9 @@ extern "C" int crt_split_recombine_device(crt_ctx *ctx, const float *d_filtered,
                                           float *d_out, void *stream) {
     const char *what = "crt_split_recombine_device";
     if (!ctx) return CRT_ERR_INVALID;
-    if ((n_pixels + BLOCK - 1) / BLOCK > 0x7FFFFFFFull) {
-        ctx->error = std::string(what) + ": more pixels than one launch holds";
-        return CRT_ERR_INVALID;
-    }
+    if ((n_pixels + BLOCK - 1) / BLOCK > 0x7FFFFFFFull) return refuse(ctx, what, "more pixels than one launch holds");
     if (n_pixels == 0) return CRT_OK;
-    if (!d_filtered || !d_dsum || !d_counts || !d_out) {
-        ctx->error = std::string(what) + ": d_filtered, d_dsum, d_counts or d_out is NULL";
-        return CRT_ERR_INVALID;
-    }
+    if (!d_filtered || !d_dsum || !d_counts || !d_out) return refuse(ctx, what, "d_filtered, d_dsum, d_counts or d_out is NULL");
     CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     return split_launch_recombine(ctx, d_filtered, d_dsum, d_counts, n_pixels, d_out, (hipStream_t)stream);
 }

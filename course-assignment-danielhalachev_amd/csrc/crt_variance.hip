@@ -9,14 +9,9 @@ namespace {
 }  // namespace
 
 static_assert(sizeof(crt_variance_estimate) == 16, "include/crt_hip.h says 16");
-static_assert(sizeof(crt_history_pixel) == 64 && sizeof(crt_temporal_record) == 64 && alignof(crt_temporal_record) == 16, "one record, two names");
-static_assert(offsetof(crt_history_pixel, c) == offsetof(crt_temporal_record, c) && offsetof(crt_history_pixel, m2) == offsetof(crt_temporal_record, m2) &&
-                  offsetof(crt_history_pixel, weight) == offsetof(crt_temporal_record, weight),
-              "crt_history_pixel is the rule's record");
 static_assert(sizeof(crt_variance_tap_geometry) == 16 && sizeof(crt_variance_tap_place) == 16 && sizeof(crt_variance_tap_moments) == 16,
               "a tap is three 16-byte vectors");
 static_assert(3 * VARIANCE_HALO * 16 == 25536, "the LDS tile DESIGN.md 8o describes");
-constexpr uint64_t VARIANCE_MAX_PIXELS = 1ull << 31;   // width * height stays below it: pixel coordinates are int32_t
 
 extern "C" void crt_variance_estimate_defaults(crt_variance_estimate *e) {
     if (!e) return;
@@ -33,9 +28,7 @@ int variance_check(crt_ctx *ctx, const char *what, const crt_variance_estimate *
     else if (!(e->min_history > 0.0f) || !std::isfinite(e->min_history)) why = "min_history is not finite or not above 0";
     else if (e->normal_squarings > 16u) why = "normal_squarings > 16";
     else if (!(e->sigma_plane >= 0.0f) || !std::isfinite(e->sigma_plane)) why = "sigma_plane is negative or not finite";
-    if (!why) return CRT_OK;
-    ctx->error = std::string(what) + ": " + why;
-    return CRT_ERR_INVALID;
+    return why ? refuse(ctx, what, why) : (int)CRT_OK;
 }
 
 // one launch; 0 < width * height < 2^31, `e` checked, no array NULL, d_moments aligned to 16 bytes
@@ -44,13 +37,13 @@ int variance_launch(crt_ctx *ctx, const crt_variance_estimate *e, uint32_t width
     VarianceArgs A{};
     A.rule = crt_variance_rule{e->min_history, e->normal_squarings, e->sigma_plane};
     A.width = (int32_t)width; A.height = (int32_t)height;
-    A.tiles_x = (width + VARIANCE_TILE_X - 1) / VARIANCE_TILE_X;
-    A.moments = (const crt_temporal_record *)d_moments;
+    A.tiles_x = tiles_x_of(width);
+    A.moments = (const crt_history_record *)d_moments;
     A.hits = d_hits;
     A.var = d_var;
     A.out_var = d_out_var;
-    const uint32_t tiles_y = (height + VARIANCE_TILE_Y - 1) / VARIANCE_TILE_Y;
-    hipLaunchKernelGGL(variance_estimate, dim3(A.tiles_x * tiles_y), dim3(VARIANCE_TILE_X, VARIANCE_TILE_Y), 0, stream, A);
+    const uint32_t tiles_y = tiles_y_of(height);
+    hipLaunchKernelGGL(variance_estimate, dim3(A.tiles_x * tiles_y), dim3(TILE_X, TILE_Y), 0, stream, A);
     CRT_HIP_CHECK(ctx, hipGetLastError());
     return CRT_OK;
 }
@@ -61,12 +54,9 @@ extern "C" int crt_variance_estimate_device(crt_ctx *ctx, const crt_variance_est
     if (!ctx) return CRT_ERR_INVALID;
     if (int rc = variance_check(ctx, what, est)) return rc;
     const uint64_t n = (uint64_t)width * height;
-    if (n >= VARIANCE_MAX_PIXELS) { ctx->error = std::string(what) + ": width * height = " + std::to_string(n) + " >= 2^31"; return CRT_ERR_INVALID; }
-    if (!d_moments || !d_hits || !d_var || !d_out_var) {
-        ctx->error = std::string(what) + ": d_moments, d_hits, d_var or d_out_var is NULL";
-        return CRT_ERR_INVALID;
-    }
-    if ((uintptr_t)d_moments % 16u) { ctx->error = std::string(what) + ": d_moments must be aligned to 16 bytes"; return CRT_ERR_INVALID; }
+    if (int rc = pixels_check(ctx, what, n)) return rc;
+    if (!d_moments || !d_hits || !d_var || !d_out_var) return refuse(ctx, what, "d_moments, d_hits, d_var or d_out_var is NULL");
+    if ((uintptr_t)d_moments % 16u) return refuse(ctx, what, "d_moments must be aligned to 16 bytes");
     if (n == 0) return CRT_OK;
     CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     return variance_launch(ctx, est, width, height, d_moments, d_hits, d_var, d_out_var, (hipStream_t)stream);

@@ -68,18 +68,7 @@
 //     (csrc/variance_rule.h), which replaces the variance of such pixels before this rule runs.
 #pragma once
 
-#include <math.h>
-#include <stdint.h>
-
-#ifndef CRT_HD
-#if defined(__HIPCC__) || defined(__HIP__)
-#define CRT_HD __host__ __device__ __forceinline__
-#else
-#define CRT_HD static inline
-#endif
-#endif
-
-#define CRT_DENOISE_MISS 0xFFFFFFFFu   // a guide's mesh where the camera's ray hit nothing
+#include "filter_rule.h"
 
 // what the rule reads of a crt_denoise (include/crt_hip.h)
 struct crt_denoise_rule {
@@ -87,45 +76,24 @@ struct crt_denoise_rule {
     float sigma_colour, sigma_plane, floor;
 };
 
-// the two records of the work area (kernel_denoise.h: denoise_pack): 32 and 16 bytes, aligned to their size
-struct alignas(16) crt_denoise_guide {
-    float n[3], t;
-    float x[3];
-    uint32_t mesh;
-};
+// the work area's records (kernel_denoise.h: denoise_pack): a crt_guide and this one, 16 bytes, aligned to its size
 struct alignas(16) crt_denoise_pixel {
     float c[3], v;
 };
 
-CRT_HD bool crt_denoise_finite(const float x) { return (x - x) == 0.0f; }
-CRT_HD bool crt_denoise_usable(const crt_denoise_pixel p) {
-    return crt_denoise_finite(p.c[0]) && crt_denoise_finite(p.c[1]) && crt_denoise_finite(p.c[2]) && crt_denoise_finite(p.v);
-}
-
-// the guide of a first hit: (t, point, normal, mesh, hit) of a crt_hit
-CRT_HD crt_denoise_guide crt_denoise_guide_of(const float t, const float point[3], const float normal[3], const uint32_t mesh, const uint32_t hit) {
-    crt_denoise_guide g;
-    g.n[0] = normal[0]; g.n[1] = normal[1]; g.n[2] = normal[2];
-    g.t = t;
-    g.x[0] = point[0]; g.x[1] = point[1]; g.x[2] = point[2];
-    g.mesh = hit ? mesh : CRT_DENOISE_MISS;
-    return g;
-}
+CRT_HD bool crt_denoise_usable(const crt_denoise_pixel p) { return crt_finite(p.c[0]) && crt_finite(p.c[1]) && crt_finite(p.c[2]) && crt_finite(p.v); }
 
 // From the fold's state: the mean and the variance of the mean.
 CRT_HD crt_denoise_pixel crt_denoise_variance(const float sum[3], const float sq, const uint32_t count) {
     crt_denoise_pixel p;
     p.c[0] = 0.0f; p.c[1] = 0.0f; p.c[2] = 0.0f; p.v = 0.0f;
     if (count == 0u) return p;
-    const float inv = 1.0f / (float)count;
-    p.c[0] = sum[0] * inv;
-    p.c[1] = sum[1] * inv;
-    p.c[2] = sum[2] * inv;
+    const float n = (float)count;
+    const float inv = 1.0f / n;
+    const float C[3] = {sum[0] * inv, sum[1] * inv, sum[2] * inv};
+    p.c[0] = C[0]; p.c[1] = C[1]; p.c[2] = C[2];
     const float q = sq * inv;
-    const float m0 = p.c[0] * p.c[0], m1 = p.c[1] * p.c[1], m2 = p.c[2] * p.c[2];
-    const float mm = (m0 + m1) + m2;
-    const float var = q - mm;
-    p.v = (var > 0.0f ? var : 0.0f) * inv;
+    p.v = crt_variance_of_mean(C, q, n);   // the rule's "* inv": the same division of the same operands gives the same float
     return p;
 }
 
@@ -133,7 +101,7 @@ CRT_HD crt_denoise_pixel crt_denoise_variance(const float sum[3], const float sq
 // row-major records of the whole image.  Every tap offset is compared with the room the centre has BEFORE the coordinate is formed, so no
 // signed sum overflows and no address outside the image exists.
 CRT_HD crt_denoise_pixel crt_denoise_atrous(const crt_denoise_rule rule, const int32_t width, const int32_t height, const int32_t step, const int32_t y,
-                                            const int32_t x, const crt_denoise_pixel *in, const crt_denoise_guide *guides) {
+                                            const int32_t x, const crt_denoise_pixel *in, const crt_guide *guides) {
     const float H5[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     const float G3[3][3] = {{1.0f, 2.0f, 1.0f}, {2.0f, 4.0f, 2.0f}, {1.0f, 2.0f, 1.0f}};
     const int64_t at = (int64_t)y * width + x;
@@ -145,7 +113,7 @@ CRT_HD crt_denoise_pixel crt_denoise_atrous(const crt_denoise_rule rule, const i
         for (int32_t dx = -1; dx <= 1; dx++) {
             if (dx < -x || dx >= width - x) continue;
             const float vq = in[(int64_t)(y + dy) * width + (x + dx)].v;
-            if (!crt_denoise_finite(vq)) continue;
+            if (!crt_finite(vq)) continue;
             const float gv = G3[dy + 1][dx + 1] * vq;
             vnum = vnum + gv;
             vden = vden + G3[dy + 1][dx + 1];
@@ -155,7 +123,7 @@ CRT_HD crt_denoise_pixel crt_denoise_atrous(const crt_denoise_rule rule, const i
     const float s2 = rule.sigma_colour * rule.sigma_colour;
     const float s2v = s2 * vp;
     const float den = s2v + rule.floor;
-    const crt_denoise_guide GP = guides[at];
+    const crt_guide GP = guides[at];
     const float tol = rule.sigma_plane * GP.t;
     float acc[3] = {0.0f, 0.0f, 0.0f}, accv = 0.0f, wsum = 0.0f;
     for (int32_t dy = -2; dy <= 2; dy++) {
@@ -167,29 +135,12 @@ CRT_HD crt_denoise_pixel crt_denoise_atrous(const crt_denoise_rule rule, const i
             const int64_t q = (int64_t)(y + oy) * width + (x + ox);
             const crt_denoise_pixel Q = in[q];
             if (!crt_denoise_usable(Q)) continue;
-            const crt_denoise_guide GQ = guides[q];
+            const crt_guide GQ = guides[q];
             if (GQ.mesh != GP.mesh) continue;
             float g = 1.0f;
-            if (GP.mesh != CRT_DENOISE_MISS) {
-                const float n0 = GP.n[0] * GQ.n[0], n1 = GP.n[1] * GQ.n[1], n2 = GP.n[2] * GQ.n[2];
-                float d = (n0 + n1) + n2;
-                d = d > 0.0f ? d : 0.0f;
-                for (uint32_t k = 0; k < rule.normal_squarings; k++) d = d * d;
-                const float x0 = GQ.x[0] - GP.x[0], x1 = GQ.x[1] - GP.x[1], x2 = GQ.x[2] - GP.x[2];
-                const float e0 = GP.n[0] * x0, e1 = GP.n[1] * x1, e2 = GP.n[2] * x2;
-                const float e = (e0 + e1) + e2;
-                const float ae = fabsf(e);
-                if (!(ae <= tol)) continue;
-                float wz = 1.0f;
-                if (tol > 0.0f) {
-                    const float r = ae / tol;
-                    wz = 1.0f - r;
-                }
-                g = d * wz;
-            }
-            const float dr = Q.c[0] - P.c[0], dg = Q.c[1] - P.c[1], db = Q.c[2] - P.c[2];
-            const float r2 = dr * dr, g2 = dg * dg, b2 = db * db;
-            const float d2 = (r2 + g2) + b2;
+            if (GP.mesh != CRT_GUIDE_MISS && !crt_geometry_weight(GP, tol, rule.normal_squarings, GQ.n, GQ.x, &g)) continue;
+            const float dc[3] = {Q.c[0] - P.c[0], Q.c[1] - P.c[1], Q.c[2] - P.c[2]};
+            const float d2 = crt_sum3(dc, dc);
             const float dd = den + d2;
             const float wl = den / dd;
             const float hh = H5[dy + 2] * H5[dx + 2];

@@ -4,7 +4,7 @@
 //   denoise_pack      one thread per pixel: the caller's crt_hit (48 bytes) -> a 32-byte guide record {nx, ny, nz, t, px, py, pz, mesh}, and
 //                     colour + variance -> one 16-byte {r, g, b, V}; both into the work area, so that a tap of the filter is three 16-byte
 //                     loads from aligned records, and so that the caller's output may be its input (everything is copied first)
-//   denoise_atrous    one thread per pixel, a workgroup covers a DENOISE_TILE_X x DENOISE_TILE_Y tile of the image: one iteration of the
+//   denoise_atrous    one thread per pixel, a workgroup covers a TILE_X x TILE_Y tile of the image (kernel_tile.h): one iteration of the
 //                     rule, every tap from global memory or L2.  The {r, g, b, V} buffers ping-pong between the iterations, the guides are
 //                     read-only; the last iteration writes the caller's layout: 3 floats a pixel, and the variance apart.
 // Every tap coordinate is computed in signed 32-bit arithmetic and checked against the frame before any address is formed
@@ -16,9 +16,7 @@
 #pragma once
 
 #include "denoise_rule.h"
-
-constexpr uint32_t DENOISE_TILE_X = 32, DENOISE_TILE_Y = 8;
-static_assert(DENOISE_TILE_X * DENOISE_TILE_Y == BLOCK, "one thread per pixel of a tile");
+#include "kernel_tile.h"
 
 struct DenoiseVarianceArgs {
     const float *sum, *sq;
@@ -41,14 +39,13 @@ struct DenoisePackArgs {
     const float *rgb, *var;
     const crt_hit *hits;
     uint64_t n;
-    crt_denoise_guide *guides;
+    crt_guide *guides;
     crt_denoise_pixel *pixels;
 };
 __global__ __launch_bounds__(BLOCK) void denoise_pack(const DenoisePackArgs P) {
     const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= P.n) return;
-    const crt_hit h = P.hits[i];
-    P.guides[i] = crt_denoise_guide_of(h.t, h.point, h.normal, h.mesh, h.hit);
+    P.guides[i] = guide_of_hit(P.hits[i]);
     const float *c = P.rgb + 3 * i;
     crt_denoise_pixel p;
     p.c[0] = c[0]; p.c[1] = c[1]; p.c[2] = c[2];
@@ -59,20 +56,17 @@ __global__ __launch_bounds__(BLOCK) void denoise_pack(const DenoisePackArgs P) {
 struct DenoiseAtrousArgs {
     crt_denoise_rule rule;
     int32_t width, height, step;
-    uint32_t tiles_x;         // ceil(width / DENOISE_TILE_X)
+    uint32_t tiles_x;         // ceil(width / TILE_X)
     const crt_denoise_pixel *in;
-    const crt_denoise_guide *guides;
+    const crt_guide *guides;
     crt_denoise_pixel *out;   // an iteration that is not the last: the other {r, g, b, V} buffer; the last one: null
     float *out_rgb, *out_var; // the last iteration: the caller's arrays (out_var: or null)
 };
-// The grid is one-dimensional, tiles row-major (a grid's second dimension holds 65535 workgroups, an image may be higher than that): at
-// most (width / 32 + 1) * (height / 8 + 1) < 2^29 workgroups for width * height < 2^31.
 __global__ __launch_bounds__(BLOCK) void denoise_atrous(const DenoiseAtrousArgs P) {
-    const uint32_t tx = blockIdx.x % P.tiles_x, ty = blockIdx.x / P.tiles_x;
-    const uint32_t ux = tx * DENOISE_TILE_X + threadIdx.x, uy = ty * DENOISE_TILE_Y + threadIdx.y;
-    if (ux >= (uint32_t)P.width || uy >= (uint32_t)P.height) return;
-    const crt_denoise_pixel r = crt_denoise_atrous(P.rule, P.width, P.height, P.step, (int32_t)uy, (int32_t)ux, P.in, P.guides);
-    const uint64_t i = (uint64_t)uy * (uint32_t)P.width + ux;
+    const TilePixel t = tile_pixel(P.tiles_x, P.width, P.height);
+    if (!t.inside) return;
+    const crt_denoise_pixel r = crt_denoise_atrous(P.rule, P.width, P.height, P.step, (int32_t)t.uy, (int32_t)t.ux, P.in, P.guides);
+    const uint64_t i = tile_index(t, P.width);
     if (P.out) {
         P.out[i] = r;
         return;

@@ -1,6 +1,6 @@
 // kernel_variance.h -- the kernel of the GI frames' variance estimate (include/crt_hip.h: crt_variance_estimate_device,
 // crt_set_variance_estimate); the rule, one header for host and device: csrc/variance_rule.h.
-//   variance_estimate  one thread per pixel, a workgroup covers a VARIANCE_TILE_X x VARIANCE_TILE_Y tile of the image.
+//   variance_estimate  one thread per pixel, a workgroup covers a TILE_X x TILE_Y tile of the image (kernel_tile.h).
 // Tile skip.  Every thread reads its own record (c, m2, weight: 20 of its 64 bytes), crt_hit and V_in and decides whether its pixel is
 // flagged (crt_variance_flagged); a thread outside the image is not.  The workgroup agrees on "any flagged" at a barrier that EVERY thread
 // reaches.  A tile without a flagged pixel writes V' = V_in and ends: nothing is staged -- the steady state of a still camera with a long
@@ -18,42 +18,38 @@
 #pragma once
 
 #include "variance_rule.h"
+#include "kernel_tile.h"
 
-constexpr uint32_t VARIANCE_TILE_X = 32, VARIANCE_TILE_Y = 8;
-static_assert(VARIANCE_TILE_X * VARIANCE_TILE_Y == BLOCK, "one thread per pixel of a tile");
-constexpr uint32_t VARIANCE_HALO_X = VARIANCE_TILE_X + 2 * CRT_VARIANCE_RADIUS, VARIANCE_HALO_Y = VARIANCE_TILE_Y + 2 * CRT_VARIANCE_RADIUS;
+constexpr uint32_t VARIANCE_HALO_X = TILE_X + 2 * CRT_VARIANCE_RADIUS, VARIANCE_HALO_Y = TILE_Y + 2 * CRT_VARIANCE_RADIUS;
 constexpr uint32_t VARIANCE_HALO = VARIANCE_HALO_X * VARIANCE_HALO_Y;   // 38 x 14 = 532 slots a plane
 
 struct VarianceArgs {
     crt_variance_rule rule;
     int32_t width, height;
-    uint32_t tiles_x;                    // ceil(width / VARIANCE_TILE_X)
-    const crt_temporal_record *moments;  // c, m2 and weight are read
+    uint32_t tiles_x;                    // ceil(width / TILE_X)
+    const crt_history_record *moments;   // c, m2 and weight are read
     const crt_hit *hits;
     const float *var;
     float *out_var;                      // may be var
 };
-// The grid is one-dimensional, tiles row-major, as denoise_atrous's: fewer than 2^29 workgroups for width * height < 2^31.
 __global__ __launch_bounds__(BLOCK) void variance_estimate(const VarianceArgs P) {
     __shared__ crt_variance_tap_geometry tile_a[VARIANCE_HALO];
     __shared__ crt_variance_tap_place tile_b[VARIANCE_HALO];
     __shared__ crt_variance_tap_moments tile_c[VARIANCE_HALO];
-    const uint32_t tx = blockIdx.x % P.tiles_x, ty = blockIdx.x / P.tiles_x;
-    const uint32_t ox = tx * VARIANCE_TILE_X, oy = ty * VARIANCE_TILE_Y;   // the tile's origin: inside the frame
-    const uint32_t ux = ox + threadIdx.x, uy = oy + threadIdx.y;
-    const bool inside = ux < (uint32_t)P.width && uy < (uint32_t)P.height;
-    const uint64_t i = (uint64_t)uy * (uint32_t)P.width + ux;
-    crt_denoise_guide GP{};
+    const TilePixel t = tile_pixel(P.tiles_x, P.width, P.height);
+    const uint32_t ox = t.ox, oy = t.oy;   // the tile's origin: inside the frame
+    const bool inside = t.inside;
+    const uint64_t i = tile_index(t, P.width);
+    crt_guide GP{};
     float weight_p = 0.0f, v_in = 0.0f;
     bool flagged = false;
     if (inside) {
-        const crt_temporal_record *m = P.moments + i;
+        const crt_history_record *m = P.moments + i;
         crt_variance_tap_moments MP;
         MP.c[0] = m->c[0]; MP.c[1] = m->c[1]; MP.c[2] = m->c[2];
         MP.m2 = m->m2;
         weight_p = m->weight;
-        const crt_hit h = P.hits[i];
-        GP = crt_denoise_guide_of(h.t, h.point, h.normal, h.mesh, h.hit);
+        GP = guide_of_hit(P.hits[i]);
         v_in = P.var[i];
         flagged = crt_variance_flagged(P.rule, MP, weight_p, GP.mesh);
     }
@@ -61,27 +57,27 @@ __global__ __launch_bounds__(BLOCK) void variance_estimate(const VarianceArgs P)
         if (inside) P.out_var[i] = v_in;
         return;
     }
-    const uint32_t tid = threadIdx.y * VARIANCE_TILE_X + threadIdx.x;
+    const uint32_t tid = threadIdx.y * TILE_X + threadIdx.x;
     for (uint32_t k = tid; k < VARIANCE_HALO; k += BLOCK) {
         const int32_t dx = (int32_t)(k % VARIANCE_HALO_X) - CRT_VARIANCE_RADIUS, dy = (int32_t)(k / VARIANCE_HALO_X) - CRT_VARIANCE_RADIUS;
         crt_variance_tap_geometry A;
         crt_variance_tap_place B;
         crt_variance_tap_moments Q;
-        A.n[0] = 0.0f; A.n[1] = 0.0f; A.n[2] = 0.0f; A.mesh = CRT_DENOISE_MISS;
+        A.n[0] = 0.0f; A.n[1] = 0.0f; A.n[2] = 0.0f; A.mesh = CRT_GUIDE_MISS;
         B.x[0] = 0.0f; B.x[1] = 0.0f; B.x[2] = 0.0f; B.weight = 0.0f;
         Q.c[0] = 0.0f; Q.c[1] = 0.0f; Q.c[2] = 0.0f; Q.m2 = 0.0f;
         // the offset against the room the origin has: ox < width and oy < height, so neither difference overflows
         if (!(dx < -(int32_t)ox || dx >= P.width - (int32_t)ox || dy < -(int32_t)oy || dy >= P.height - (int32_t)oy)) {
             const uint32_t qx = (uint32_t)((int32_t)ox + dx), qy = (uint32_t)((int32_t)oy + dy);
             const uint64_t q = (uint64_t)qy * (uint32_t)P.width + qx;
-            const crt_temporal_record *m = P.moments + q;
+            const crt_history_record *m = P.moments + q;
             Q.c[0] = m->c[0]; Q.c[1] = m->c[1]; Q.c[2] = m->c[2];
             Q.m2 = m->m2;
             B.weight = m->weight;
-            const crt_hit h = P.hits[q];
-            A.n[0] = h.normal[0]; A.n[1] = h.normal[1]; A.n[2] = h.normal[2];
-            A.mesh = h.hit ? h.mesh : CRT_DENOISE_MISS;
-            B.x[0] = h.point[0]; B.x[1] = h.point[1]; B.x[2] = h.point[2];
+            const crt_guide G = guide_of_hit(P.hits[q]);
+            A.n[0] = G.n[0]; A.n[1] = G.n[1]; A.n[2] = G.n[2];
+            A.mesh = G.mesh;
+            B.x[0] = G.x[0]; B.x[1] = G.x[1]; B.x[2] = G.x[2];
         }
         tile_a[k] = A;
         tile_b[k] = B;

@@ -25,15 +25,7 @@
 // A sample with an infinite channel in both parts gives inf - inf = NaN in the rest.
 #pragma once
 
-#include <stdint.h>
-
-#ifndef CRT_HD
-#if defined(__HIPCC__) || defined(__HIP__)
-#define CRT_HD __host__ __device__ __forceinline__
-#else
-#define CRT_HD static inline
-#endif
-#endif
+#include "filter_rule.h"
 
 // the CRT_SHADE_* values the rule tells apart (include/crt_hip.h)
 enum : uint32_t { CRT_SPLIT_BACKGROUND = 0u, CRT_SPLIT_DIFFUSE = 1u };
@@ -50,8 +42,7 @@ CRT_HD void crt_split_fold(const uint32_t sample, const float rgb[3], const floa
         dsum[c] = (sample == 0u ? 0.0f : dsum[c]) + direct[c];
         rsum[c] = (sample == 0u ? 0.0f : rsum[c]) + r[c];
     }
-    const float rr = r[0] * r[0], gg = r[1] * r[1], bb = r[2] * r[2];
-    const float r2 = (rr + gg) + bb;
+    const float r2 = crt_sum3(r, r);
     *rsq = (sample == 0u ? 0.0f : *rsq) + r2;
 }
 

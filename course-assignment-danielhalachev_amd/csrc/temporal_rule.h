@@ -7,7 +7,7 @@
 // this file.  There is no exp, pow or sqrt in it; floorf is exact.
 //
 // Records.  A history pixel is 64 bytes, aligned 16: {n[3], t, x[3], mesh, c[3], m2, weight, pad[3]}.  n[3], t, x[3], mesh is the guide of
-// the frame that wrote it (denoise_rule.h: crt_denoise_guide_of; mesh = 0xFFFFFFFF is a miss), c[3] the accumulated mean colour, m2 the
+// the frame that wrote it (filter_rule.h: crt_guide_of; mesh = 0xFFFFFFFF is a miss), c[3] the accumulated mean colour, m2 the
 // accumulated mean of r*r + g*g + b*b, weight the number of samples the record stands for, as a float; pad is written as 0.  A tap reads it
 // with four 16-byte loads from one 64-byte half line.  A pose is {position[3], matrix[9]}, what crt_set_camera takes: (o, m) below.
 // finite(x) is (x - x) == 0.0f.
@@ -73,7 +73,7 @@
 //   * The history holds the unfiltered moments: the filtered colour is not fed back.
 #pragma once
 
-#include "denoise_rule.h"
+#include "filter_rule.h"
 
 // what the rule reads of a crt_temporal (include/crt_hip.h)
 struct crt_temporal_rule {
@@ -85,25 +85,18 @@ struct crt_temporal_pose {
     float o[3], m[9];
 };
 
-// crt_history_pixel's layout (include/crt_hip.h), aligned so that a record is four 16-byte loads
-struct alignas(16) crt_temporal_record {
-    crt_denoise_guide g;
-    float c[3], m2;
-    float weight, pad[3];
-};
-
 // what a pixel gives beside its record
 struct crt_temporal_out {
-    crt_temporal_record r;
+    crt_history_record r;
     float v;
     uint32_t valid;
 };
 
 // The pixel (y, x) of a width x height frame (width * height < 2^31, so both fit int32_t); `prev` is the previous frame's row-major records
 // or null.  A tap's coordinates are compared with the frame as integers before its address is formed.
-CRT_HD crt_temporal_out crt_temporal_pixel(const crt_temporal_rule rule, const int32_t width, const int32_t height, const crt_denoise_guide GP,
+CRT_HD crt_temporal_out crt_temporal_pixel(const crt_temporal_rule rule, const int32_t width, const int32_t height, const crt_guide GP,
                                            const float sum[3], const float sq, const uint32_t count, const crt_temporal_pose pose,
-                                           const crt_temporal_record *prev) {
+                                           const crt_history_record *prev) {
     // current
     const float nc = (float)count;
     float cc[3] = {0.0f, 0.0f, 0.0f}, qc = 0.0f;
@@ -117,7 +110,7 @@ CRT_HD crt_temporal_out crt_temporal_pixel(const crt_temporal_rule rule, const i
     // reproject
     float ch[3] = {0.0f, 0.0f, 0.0f}, qh = 0.0f, nh = 0.0f;
     uint32_t valid = 0u;
-    if (prev && GP.mesh != CRT_DENOISE_MISS) {
+    if (prev && GP.mesh != CRT_GUIDE_MISS) {
         const float w0 = GP.x[0] - pose.o[0], w1 = GP.x[1] - pose.o[1], w2 = GP.x[2] - pose.o[2];
         float v[3];
         for (int i = 0; i < 3; i++) {
@@ -147,21 +140,13 @@ CRT_HD crt_temporal_out crt_temporal_pixel(const crt_temporal_rule rule, const i
                 for (int k = 0; k < 4; k++) {
                     const int32_t qx = ix + (k & 1), qy = iy + (k >> 1);
                     if (qx < 0 || qx >= width || qy < 0 || qy >= height) continue;
-                    const crt_temporal_record Q = prev[(int64_t)qy * width + qx];
-                    if (!(Q.weight > 0.0f)) continue;
-                    if (!(crt_denoise_finite(Q.c[0]) && crt_denoise_finite(Q.c[1]) && crt_denoise_finite(Q.c[2]) && crt_denoise_finite(Q.m2) &&
-                          crt_denoise_finite(Q.weight)))
-                        continue;
+                    const crt_history_record Q = prev[(int64_t)qy * width + qx];
+                    if (!CRT_USABLE(Q.c, Q.m2, Q.weight)) continue;
                     if (Q.g.mesh != GP.mesh) continue;
-                    const float n0 = GP.n[0] * Q.g.n[0], n1 = GP.n[1] * Q.g.n[1], n2 = GP.n[2] * Q.g.n[2];
-                    const float n01 = n0 + n1;
-                    const float d = n01 + n2;
+                    const float d = crt_normal_dot(GP, Q.g.n);
                     if (!(d >= rule.normal_min)) continue;
-                    const float d0 = Q.g.x[0] - GP.x[0], d1 = Q.g.x[1] - GP.x[1], d2 = Q.g.x[2] - GP.x[2];
-                    const float e0 = GP.n[0] * d0, e1 = GP.n[1] * d1, e2 = GP.n[2] * d2;
-                    const float e01 = e0 + e1;
-                    const float e = e01 + e2;
-                    if (!(fabsf(e) <= tol)) continue;
+                    const float ae = crt_plane_distance(GP, Q.g.x);
+                    if (!(ae <= tol)) continue;
                     const float b = B[k];
                     wsum = wsum + b;
                     const float b0 = b * Q.c[0], b1 = b * Q.c[1], b2 = b * Q.c[2];
@@ -204,12 +189,7 @@ CRT_HD crt_temporal_out crt_temporal_pixel(const crt_temporal_rule rule, const i
         C[0] = 0.0f; C[1] = 0.0f; C[2] = 0.0f;
         q = 0.0f;
     } else {
-        const float m0 = C[0] * C[0], m1 = C[1] * C[1], m2 = C[2] * C[2];
-        const float m01 = m0 + m1;
-        const float mm = m01 + m2;
-        const float var = q - mm;
-        const float invn = 1.0f / n;
-        V = (var > 0.0f ? var : 0.0f) * invn;
+        V = crt_variance_of_mean(C, q, n);
     }
     // write
     crt_temporal_out R;

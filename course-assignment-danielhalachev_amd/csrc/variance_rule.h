@@ -7,7 +7,7 @@
 //
 // Definitions.  finite(x) is (x - x) == 0.0f.  A moment record is M = {c[3], m2, weight}, the fields of a crt_history_pixel (the record's
 // own guide fields are not read).  usable(M): weight > 0 and c[0..2], m2, weight all finite.  A guide is G = {n[3], x[3], t, mesh}, taken
-// from a crt_hit as the denoiser takes it (denoise_rule.h: crt_denoise_guide_of; mesh = 0xFFFFFFFF when hit == 0).  V_in is the incoming
+// from a crt_hit as the denoiser takes it (filter_rule.h: crt_guide_of; mesh = 0xFFFFFFFF when hit == 0).  V_in is the incoming
 // variance of the mean.  The window radius is 3 and is not a setting.
 //
 // Centre p = (y, x) of a width x height image.  It passes through, V' = V_in, when
@@ -43,8 +43,8 @@
 // The centre is its own tap (dy = dx = 0) and passes every test whose operands are finite, with d = |n_p|^2 squared and wz = 1.  A NaN that
 // arises from overflow or from a non-finite guide is whatever these lines give: a NaN w makes wsum NaN, and the centre passes through.
 //
-// The geometry lines are the denoiser's own (denoise_rule.h), with the same names.  weight_p is the number of samples the centre's record
-// stands for, so V' is a variance OF THE MEAN, as the denoiser's and the temporal rule's V are.
+// The geometry lines are the denoiser's own (filter_rule.h: crt_geometry_weight), with the same names.  weight_p is the number of samples
+// the centre's record stands for, so V' is a variance OF THE MEAN, as the denoiser's and the temporal rule's V are.
 //
 // Known limits.
 //   * A miss pixel is never estimated: it has no geometry to compare, and the a-trous filter averages misses under the colour weight alone.
@@ -53,7 +53,7 @@
 //   * The window is 7x7 and dense; it does not widen where few taps survive.
 #pragma once
 
-#include "temporal_rule.h"
+#include "filter_rule.h"
 
 #define CRT_VARIANCE_RADIUS 3   // the window is (2 * 3 + 1)^2 = 49 taps
 
@@ -80,15 +80,13 @@ struct crt_variance_sums {
     float acc[3], accq, wsum;
 };
 
-CRT_HD bool crt_variance_usable(const crt_variance_tap_moments m, const float weight) {
-    return weight > 0.0f && crt_denoise_finite(m.c[0]) && crt_denoise_finite(m.c[1]) && crt_denoise_finite(m.c[2]) && crt_denoise_finite(m.m2) &&
-           crt_denoise_finite(weight);
-}
+// usable(M) of a tap's or the centre's moments (a function of the 16-byte vector, as the kernel reads it from its plane)
+CRT_HD bool crt_variance_usable(const crt_variance_tap_moments m, const float weight) { return CRT_USABLE(m.c, m.m2, weight); }
 
 // the centre test: true when the centre is FLAGGED, false when it passes through
 CRT_HD bool crt_variance_flagged(const crt_variance_rule rule, const crt_variance_tap_moments m, const float weight, const uint32_t mesh) {
     if (!crt_variance_usable(m, weight)) return false;
-    if (mesh == CRT_DENOISE_MISS) return false;
+    if (mesh == CRT_GUIDE_MISS) return false;
     return weight < rule.min_history;
 }
 
@@ -102,25 +100,12 @@ CRT_HD crt_variance_sums crt_variance_begin() {
 
 // One tap inside the frame against the flagged centre's guide GP and tol = sigma_plane * t_p.  A tap staged for a place outside the frame
 // has weight 0 and is skipped as not usable.
-CRT_HD void crt_variance_tap(const crt_variance_rule rule, const crt_denoise_guide GP, const float tol, const crt_variance_tap_geometry A,
+CRT_HD void crt_variance_tap(const crt_variance_rule rule, const crt_guide GP, const float tol, const crt_variance_tap_geometry A,
                              const crt_variance_tap_place B, const crt_variance_tap_moments Q, crt_variance_sums &s) {
     if (!crt_variance_usable(Q, B.weight)) return;
     if (A.mesh != GP.mesh) return;
-    const float n0 = GP.n[0] * A.n[0], n1 = GP.n[1] * A.n[1], n2 = GP.n[2] * A.n[2];
-    float d = (n0 + n1) + n2;
-    d = d > 0.0f ? d : 0.0f;
-    for (uint32_t k = 0; k < rule.normal_squarings; k++) d = d * d;
-    const float x0 = B.x[0] - GP.x[0], x1 = B.x[1] - GP.x[1], x2 = B.x[2] - GP.x[2];
-    const float e0 = GP.n[0] * x0, e1 = GP.n[1] * x1, e2 = GP.n[2] * x2;
-    const float e = (e0 + e1) + e2;
-    const float ae = fabsf(e);
-    if (!(ae <= tol)) return;
-    float wz = 1.0f;
-    if (tol > 0.0f) {
-        const float r = ae / tol;
-        wz = 1.0f - r;
-    }
-    const float w = d * wz;
+    float w;
+    if (!crt_geometry_weight(GP, tol, rule.normal_squarings, A.n, B.x, &w)) return;
     const float w0 = w * Q.c[0], w1 = w * Q.c[1], w2 = w * Q.c[2];
     s.acc[0] = s.acc[0] + w0;
     s.acc[1] = s.acc[1] + w1;
@@ -134,16 +119,12 @@ CRT_HD void crt_variance_tap(const crt_variance_rule rule, const crt_denoise_gui
 CRT_HD float crt_variance_finish(const crt_variance_sums s, const float weight_p, const float v_in) {
     if (!(s.wsum > 0.0f)) return v_in;
     const float inv = 1.0f / s.wsum;
-    const float c0 = s.acc[0] * inv, c1 = s.acc[1] * inv, c2 = s.acc[2] * inv;
+    const float cb[3] = {s.acc[0] * inv, s.acc[1] * inv, s.acc[2] * inv};
     const float qb = s.accq * inv;
-    const float m0 = c0 * c0, m1 = c1 * c1, m2 = c2 * c2;
-    const float mm = (m0 + m1) + m2;
-    const float var = qb - mm;
-    const float iw = 1.0f / weight_p;
-    return (var > 0.0f ? var : 0.0f) * iw;
+    return crt_variance_of_mean(cb, qb, weight_p);
 }
 
-CRT_HD crt_variance_tap_moments crt_variance_moments_of(const crt_temporal_record r) {
+CRT_HD crt_variance_tap_moments crt_variance_moments_of(const crt_history_record r) {
     crt_variance_tap_moments m;
     m.c[0] = r.c[0]; m.c[1] = r.c[1]; m.c[2] = r.c[2];
     m.m2 = r.m2;
@@ -155,10 +136,10 @@ CRT_HD crt_variance_tap_moments crt_variance_moments_of(const crt_temporal_recor
 // BEFORE the coordinate is formed, so no signed sum overflows and no address outside the image exists.  The kernel runs the same three
 // functions on a tile staged in LDS.
 CRT_HD float crt_variance_pixel(const crt_variance_rule rule, const int32_t width, const int32_t height, const int32_t y, const int32_t x,
-                                const crt_temporal_record *moments, const crt_denoise_guide *guides, const float v_in) {
+                                const crt_history_record *moments, const crt_guide *guides, const float v_in) {
     const int64_t at = (int64_t)y * width + x;
-    const crt_temporal_record MP = moments[at];
-    const crt_denoise_guide GP = guides[at];
+    const crt_history_record MP = moments[at];
+    const crt_guide GP = guides[at];
     if (!crt_variance_flagged(rule, crt_variance_moments_of(MP), MP.weight, GP.mesh)) return v_in;
     const float tol = rule.sigma_plane * GP.t;
     crt_variance_sums s = crt_variance_begin();
@@ -167,8 +148,8 @@ CRT_HD float crt_variance_pixel(const crt_variance_rule rule, const int32_t widt
         for (int32_t dx = -CRT_VARIANCE_RADIUS; dx <= CRT_VARIANCE_RADIUS; dx++) {
             if (dx < -x || dx >= width - x) continue;
             const int64_t q = (int64_t)(y + dy) * width + (x + dx);
-            const crt_temporal_record MQ = moments[q];
-            const crt_denoise_guide GQ = guides[q];
+            const crt_history_record MQ = moments[q];
+            const crt_guide GQ = guides[q];
             crt_variance_tap_geometry A;
             A.n[0] = GQ.n[0]; A.n[1] = GQ.n[1]; A.n[2] = GQ.n[2];
             A.mesh = GQ.mesh;

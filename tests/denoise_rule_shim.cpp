@@ -20,11 +20,11 @@ extern "C" void shim_denoise(uint32_t iterations, uint32_t normal_squarings, flo
     const crt_denoise_rule rule{normal_squarings, sigma_colour, sigma_plane, floor};
     const int64_t n = (int64_t)width * height;
     std::vector<crt_denoise_pixel> a(n), b(n);
-    std::vector<crt_denoise_guide> g(n);
+    std::vector<crt_guide> g(n);
     for (int64_t i = 0; i < n; i++) {
         a[i].c[0] = rgb[3 * i]; a[i].c[1] = rgb[3 * i + 1]; a[i].c[2] = rgb[3 * i + 2];
         a[i].v = var[i];
-        g[i] = crt_denoise_guide_of(t[i], point + 3 * i, normal + 3 * i, mesh[i], hit[i]);
+        g[i] = crt_guide_of(t[i], point + 3 * i, normal + 3 * i, mesh[i], hit[i]);
     }
     for (uint32_t k = 0; k < iterations; k++) {
         for (int32_t y = 0; y < height; y++)

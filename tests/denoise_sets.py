@@ -40,23 +40,70 @@ def finite(x):
         return (x - x).astype(F) == F(0.0)
 
 
+# ---- what the stages' rules share (csrc/filter_rule.h), restated once: tests/temporal_sets.py and tests/variance_sets.py call these too
+
+def sum3(a, b):
+    """(a0*b0 + a1*b1) + a2*b2 over the last axis: three products, then two sums in this association"""
+    p0 = (a[..., 0] * b[..., 0]).astype(F)
+    p1 = (a[..., 1] * b[..., 1]).astype(F)
+    p2 = (a[..., 2] * b[..., 2]).astype(F)
+    p01 = (p0 + p1).astype(F)
+    return (p01 + p2).astype(F)
+
+
+def normal_dot(n_p, n_q):
+    """d = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z"""
+    return sum3(n_p, n_q)
+
+
+def plane_distance(n_p, x_p, x_q):
+    """ae = fabsf(e), e = (n_p.x*(x_q.x - x_p.x) + n_p.y*(x_q.y - x_p.y)) + n_p.z*(x_q.z - x_p.z)"""
+    o0 = (x_q[..., 0] - x_p[..., 0]).astype(F)
+    o1 = (x_q[..., 1] - x_p[..., 1]).astype(F)
+    o2 = (x_q[..., 2] - x_p[..., 2]).astype(F)
+    e = sum3(n_p, np.stack([o0, o1, o2], axis=-1))
+    return np.abs(e).astype(F)
+
+
+def geometry_weight(n_p, x_p, tol, squarings, n_q, x_q):
+    """the denoiser's and the variance estimate's weight of a tap -> (near, g): near is False where the tap is skipped (either side NaN too)"""
+    d = normal_dot(n_p, n_q)
+    d = np.where(d > F(0.0), d, F(0.0)).astype(F)
+    for _k in range(squarings):
+        d = (d * d).astype(F)
+    ae = plane_distance(n_p, x_p, x_q)
+    near = ae <= tol
+    r = (ae / tol).astype(F)
+    wz = np.where(tol > F(0.0), (F(1.0) - r).astype(F), F(1.0)).astype(F)
+    return near, (d * wz).astype(F)
+
+
+def usable(c, m2, weight):
+    """weight > 0 and c[0..2], m2, weight all finite"""
+    with np.errstate(all="ignore"):
+        return (weight > F(0.0)) & finite(c[..., 0]) & finite(c[..., 1]) & finite(c[..., 2]) & finite(m2) & finite(weight)
+
+
+def variance_of_mean(c, q, n):
+    """V = (var > 0 ? var : 0) * (1.0f / n), var = q - ((C_r*C_r + C_g*C_g) + C_b*C_b)"""
+    mm = sum3(c, c)
+    var = (q - mm).astype(F)
+    inv = (F(1.0) / n).astype(F)
+    return (np.where(var > F(0.0), var, F(0.0)).astype(F) * inv).astype(F)
+
+
 def variance(total, sq, counts):
     """From the fold's state: total float32 [P, 3], sq float32 [P], counts uint32 [P] -> (mean [P, 3], V [P], the variance of the mean)."""
     total, sq, counts = np.asarray(total, dtype=F).reshape(-1, 3), np.asarray(sq, dtype=F).reshape(-1), np.asarray(counts).reshape(-1)
     with np.errstate(all="ignore"):
-        inv = (F(1.0) / np.maximum(counts, 1).astype(F)).astype(F)
+        n = np.maximum(counts, 1).astype(F)
+        inv = (F(1.0) / n).astype(F)
         c0 = (total[:, 0] * inv).astype(F)
         c1 = (total[:, 1] * inv).astype(F)
         c2 = (total[:, 2] * inv).astype(F)
         q = (sq * inv).astype(F)
-        m0 = (c0 * c0).astype(F)
-        m1 = (c1 * c1).astype(F)
-        m2 = (c2 * c2).astype(F)
-        mm = (m0 + m1).astype(F)
-        mm = (mm + m2).astype(F)
-        var = (q - mm).astype(F)
-        v = (np.where(var > F(0.0), var, F(0.0)).astype(F) * inv).astype(F)
-    mean = np.stack([c0, c1, c2], axis=1)
+        mean = np.stack([c0, c1, c2], axis=1)
+        v = variance_of_mean(mean, q, n)
     none = counts == 0
     mean[none] = F(0.0)
     v[none] = F(0.0)
@@ -115,37 +162,12 @@ def iteration(colour, var, guides, step, denoise, tally=None):
                 count["mesh"] += int((take & (guides["mesh"][ys, xs] != mesh_p)).sum())
                 take = take & (guides["mesh"][ys, xs] == mesh_p)
                 n_q, x_q, c_q, v_q = n_p[ys, xs], x_p[ys, xs], colour[ys, xs], var[ys, xs]
-                n0 = (n_p[..., 0] * n_q[..., 0]).astype(F)
-                n1 = (n_p[..., 1] * n_q[..., 1]).astype(F)
-                n2 = (n_p[..., 2] * n_q[..., 2]).astype(F)
-                d = (n0 + n1).astype(F)
-                d = (d + n2).astype(F)
-                d = np.where(d > F(0.0), d, F(0.0)).astype(F)
-                for _k in range(squarings):
-                    d = (d * d).astype(F)
-                x0 = (x_q[..., 0] - x_p[..., 0]).astype(F)
-                x1 = (x_q[..., 1] - x_p[..., 1]).astype(F)
-                x2 = (x_q[..., 2] - x_p[..., 2]).astype(F)
-                e0 = (n_p[..., 0] * x0).astype(F)
-                e1 = (n_p[..., 1] * x1).astype(F)
-                e2 = (n_p[..., 2] * x2).astype(F)
-                e = (e0 + e1).astype(F)
-                e = (e + e2).astype(F)
-                ae = np.abs(e).astype(F)
-                near = ae <= tol                                  # False when either side is NaN
+                near, g = geometry_weight(n_p, x_p, tol, squarings, n_q, x_q)
                 count["plane"] += int((take & is_hit & ~near).sum())
                 take = take & (~is_hit | near)
-                r = (ae / tol).astype(F)
-                wz = np.where(tol > F(0.0), (F(1.0) - r).astype(F), F(1.0)).astype(F)
-                g = np.where(is_hit, (d * wz).astype(F), F(1.0)).astype(F)
-                dr = (c_q[..., 0] - colour[..., 0]).astype(F)
-                dg = (c_q[..., 1] - colour[..., 1]).astype(F)
-                db = (c_q[..., 2] - colour[..., 2]).astype(F)
-                r2 = (dr * dr).astype(F)
-                g2 = (dg * dg).astype(F)
-                b2 = (db * db).astype(F)
-                d2 = (r2 + g2).astype(F)
-                d2 = (d2 + b2).astype(F)
+                g = np.where(is_hit, g, F(1.0)).astype(F)
+                dc = (c_q - colour).astype(F)
+                d2 = sum3(dc, dc)
                 dd = (den + d2).astype(F)
                 wl = (den / dd).astype(F)
                 hh = F(H5[dy + 2] * H5[dx + 2])

@@ -113,28 +113,16 @@ def frame(temporal, width, height, pose, prev, total, sq, counts, hits, tally=No
                 heavy = w_q > F(0.0)
                 count["weight0"] += int((take & ~heavy).sum())
                 take = take & heavy
-                fin = dns.finite(c_q[:, 0]) & dns.finite(c_q[:, 1]) & dns.finite(c_q[:, 2]) & dns.finite(m2_q) & dns.finite(w_q)
-                count["nonfinite"] += int((take & ~fin).sum())
-                take = take & fin
+                good = dns.usable(c_q, m2_q, w_q)                 # heavy and all finite
+                count["nonfinite"] += int((take & ~good).sum())
+                take = take & good
                 count["mesh"] += int((take & (q["mesh"] != mesh_p)).sum())
                 take = take & (q["mesh"] == mesh_p)
-                n0 = (n_p[:, 0] * q["n"][:, 0]).astype(F)
-                n1 = (n_p[:, 1] * q["n"][:, 1]).astype(F)
-                n2 = (n_p[:, 2] * q["n"][:, 2]).astype(F)
-                d = (n0 + n1).astype(F)
-                d = (d + n2).astype(F)
+                d = dns.normal_dot(n_p, q["n"])
                 facing = d >= normal_min
                 count["normal"] += int((take & ~facing).sum())
                 take = take & facing
-                d0 = (q["x"][:, 0] - x_p[:, 0]).astype(F)
-                d1 = (q["x"][:, 1] - x_p[:, 1]).astype(F)
-                d2 = (q["x"][:, 2] - x_p[:, 2]).astype(F)
-                e0 = (n_p[:, 0] * d0).astype(F)
-                e1 = (n_p[:, 1] * d1).astype(F)
-                e2 = (n_p[:, 2] * d2).astype(F)
-                e = (e0 + e1).astype(F)
-                e = (e + e2).astype(F)
-                near = np.abs(e).astype(F) <= tol
+                near = dns.plane_distance(n_p, x_p, q["x"]) <= tol
                 count["plane"] += int((take & ~near).sum())
                 take = take & near
                 b = weights[k]
@@ -175,14 +163,7 @@ def frame(temporal, width, height, pose, prev, total, sq, counts, hits, tally=No
         none = weight == F(0.0)
         colour[none] = F(0.0)
         q[none] = F(0.0)
-        m0 = (colour[:, 0] * colour[:, 0]).astype(F)
-        m1 = (colour[:, 1] * colour[:, 1]).astype(F)
-        m2 = (colour[:, 2] * colour[:, 2]).astype(F)
-        mm = (m0 + m1).astype(F)
-        mm = (mm + m2).astype(F)
-        var = (q - mm).astype(F)
-        invn = (F(1.0) / weight).astype(F)
-        v = (np.where(var > F(0.0), var, F(0.0)).astype(F) * invn).astype(F)
+        v = dns.variance_of_mean(colour, q, weight)
         v[none] = F(0.0)
     records = np.zeros(n, dtype=HISTORY_DTYPE)
     records["n"], records["t"], records["x"], records["mesh"] = n_p, t_p, x_p, mesh_p

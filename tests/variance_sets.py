@@ -27,9 +27,7 @@ def settings(estimate):
     return (float(estimate.min_history), int(estimate.normal_squarings), float(estimate.sigma_plane))
 
 
-def usable(c, m2, weight):
-    with np.errstate(all="ignore"):
-        return (weight > F(0.0)) & dns.finite(c[..., 0]) & dns.finite(c[..., 1]) & dns.finite(c[..., 2]) & dns.finite(m2) & dns.finite(weight)
+usable = dns.usable
 
 
 def estimate(setting, width, height, records, hits, var, tally=None):
@@ -66,29 +64,9 @@ def estimate(setting, width, height, records, hits, var, tally=None):
                 count["mesh"] += int((take & (mesh_p[ys, xs] != mesh_p)).sum())
                 take = take & (mesh_p[ys, xs] == mesh_p)
                 n_q, x_q, c_q, m2_q = n_p[ys, xs], x_p[ys, xs], c[ys, xs], m2[ys, xs]
-                n0 = (n_p[..., 0] * n_q[..., 0]).astype(F)
-                n1 = (n_p[..., 1] * n_q[..., 1]).astype(F)
-                n2 = (n_p[..., 2] * n_q[..., 2]).astype(F)
-                d = (n0 + n1).astype(F)
-                d = (d + n2).astype(F)
-                d = np.where(d > F(0.0), d, F(0.0)).astype(F)
-                for _k in range(squarings):
-                    d = (d * d).astype(F)
-                x0 = (x_q[..., 0] - x_p[..., 0]).astype(F)
-                x1 = (x_q[..., 1] - x_p[..., 1]).astype(F)
-                x2 = (x_q[..., 2] - x_p[..., 2]).astype(F)
-                e0 = (n_p[..., 0] * x0).astype(F)
-                e1 = (n_p[..., 1] * x1).astype(F)
-                e2 = (n_p[..., 2] * x2).astype(F)
-                e = (e0 + e1).astype(F)
-                e = (e + e2).astype(F)
-                ae = np.abs(e).astype(F)
-                near = ae <= tol                                  # False when either side is NaN
+                near, w = dns.geometry_weight(n_p, x_p, tol, squarings, n_q, x_q)
                 count["plane"] += int((take & ~near).sum())
                 take = take & near
-                r = (ae / tol).astype(F)
-                wz = np.where(tol > F(0.0), (F(1.0) - r).astype(F), F(1.0)).astype(F)
-                w = (d * wz).astype(F)
                 for k in range(3):
                     wc = (w * c_q[..., k]).astype(F)
                     acc[..., k] = np.where(take, (acc[..., k] + wc).astype(F), acc[..., k])
@@ -99,18 +77,9 @@ def estimate(setting, width, height, records, hits, var, tally=None):
         count["no_tap"] = int((flagged & ~(wsum > F(0.0))).sum())
         count["estimated"] = int(weighs.sum())
         inv = (F(1.0) / wsum).astype(F)
-        c0 = (acc[..., 0] * inv).astype(F)
-        c1 = (acc[..., 1] * inv).astype(F)
-        c2 = (acc[..., 2] * inv).astype(F)
+        cb = (acc * inv[..., None]).astype(F)
         qb = (accq * inv).astype(F)
-        m0 = (c0 * c0).astype(F)
-        m1 = (c1 * c1).astype(F)
-        m2s = (c2 * c2).astype(F)
-        mm = (m0 + m1).astype(F)
-        mm = (mm + m2s).astype(F)
-        v = (qb - mm).astype(F)
-        iw = (F(1.0) / weight).astype(F)
-        new_v = (np.where(v > F(0.0), v, F(0.0)).astype(F) * iw).astype(F)
+        new_v = dns.variance_of_mean(cb, qb, weight)
     if tally is not None:
         for k in ROUTES:
             tally[k] = tally.get(k, 0) + count[k]
