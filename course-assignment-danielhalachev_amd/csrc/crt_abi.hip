@@ -308,7 +308,7 @@ extern "C" int crt_get_executed_counters(crt_ctx *ctx, uint64_t out[4]) {
     if (!ctx || !out) return CRT_ERR_INVALID;
     out[0] = ctx->exec_counters[0] + ctx->exec_counters[2];  // the whole render
     out[1] = ctx->exec_counters[1] + ctx->exec_counters[3];
-    out[2] = ctx->exec_counters[2];                          // of which shadow pass 0 (stream_trace_shadow_lean<0>)
+    out[2] = ctx->exec_counters[2];                          // of which shadow pass 0 (the bulk shadow pass: crt_launch.hip, SHADOW[0])
     out[3] = ctx->exec_counters[3];
     return CRT_OK;
 }
@@ -330,29 +330,11 @@ extern "C" int crt_debug_stream_counts(crt_ctx *ctx, uint32_t *out, uint32_t max
     return CRT_OK;
 }
 
-// Which kernels a production frame of this context runs (bench.py names the roofline's kernel with it): the plain builds' names, whatever
-// build the last frame asked for.  "shadow0" follows the LAST frame's launch: by pixel before the first frame and after a frame that had
-// fixed slots outside the GI mode, by slot after a GI frame or a frame without fixed slots -- it describes what ran, not what the next
-// frame's options will choose.
+// Which kernels a production frame of this context runs (crt_launch.hip: describe_frame_kernels -- the frame's plan, named from the launch tables),
+// and the scene's candidate filter.
 extern "C" int crt_describe_kernels(const crt_ctx *ctx, char *out, size_t size) {
     if (!ctx || !out || size == 0) return CRT_ERR_INVALID;
-    const SceneArgs &A = ctx->scene;
-    std::string d;
-    if (ctx->mode == crt_ctx::MODE_LANES) d = "all=render_lanes<false>";
-    else {
-        const bool heavy = ctx->step_budget && A.nested_boxes && (A.top_fast || A.plan_seq);
-        const bool lean = heavy && ctx->lean_ok && (A.plan_ok || A.plan_wide);
-        const bool wide = lean && !A.plan_ok;
-        const bool bvh = A.bvh_ok && ctx->tuning.bvh;
-        // (the bulk shadow pass by pixel, unless the last frame had to walk slots: the GI mode, no fixed slots -- crt_launch.hip)
-        const char *shadow0 = ctx->shadow0_by_slot ? ";shadow0=bvh_trace_shadow<0u, 0, false>" : ";shadow0=bvh_trace_shadow<0u, 0, true>";
-        if (bvh && ctx->tuning.level_queue) d = std::string("level0=bvh_trace_level0<0>") + shadow0 + ";levels=bvh_trace_queue<0>";
-        else if (bvh) d = std::string("level0=bvh_trace_shade") + shadow0 + ";levels=bvh_trace_shade";
-        else d = std::string("level0=") + (!lean ? "stream_trace_shade<false>" : wide ? "stream_trace_shade_plan_wide" : "stream_trace_shade_plan");
-        if (!bvh) d += std::string(";shadow0=") + (!lean ? "stream_trace_shadow<false>" : wide ? "stream_trace_shadow_plan_wide<0u>" : "stream_trace_shadow_plan<0u>");
-        if (!bvh) d += std::string(";levels=") + (!heavy ? "stream_trace_shade<false>" : "heavy_trace_closest");
-    }
-    d += std::string(";filter=") + (A.bvh_ok ? ctx->bvh_stats : "none (" + ctx->bvh_note + ")");
+    const std::string d = describe_frame_kernels(ctx) + ";filter=" + (ctx->scene.bvh_ok ? ctx->bvh_stats : "none (" + ctx->bvh_note + ")");
     snprintf(out, size, "%s", d.c_str());
     return CRT_OK;
 }

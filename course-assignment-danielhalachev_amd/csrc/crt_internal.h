@@ -1,7 +1,8 @@
 // crt_internal.h -- what the translation units behind include/crt_hip.h share: the context, the layouts the kernels and the host
 // agree on (kernel_common.h), and the few functions that cross a file boundary.  Nothing here is part of the ABI.
 //   crt_scene.hip     crt_create / crt_destroy: the flattened scene and everything derived from it, uploaded once
-//   crt_launch.hip    the kernels and one frame's launches: frame plan, queue sizing, events
+//   crt_launch.hip    the kernels and one frame's launches: the frame's plan (make_plan: the one place its kernels are chosen), the kernels'
+//                     tables, queue sizing, events
 //   crt_abi.hip       the render entry points, tiles, statistics
 //   crt_multi.hip     one scene on several devices behind one call
 //   crt_query.hip     the queries for what the caller supplies, behind one call path: ray queries (closest hit / occlusion, the camera's rays),
@@ -57,7 +58,7 @@ struct crt_ctx {
     hipEvent_t ev0[EV_RING] = {}, ev1[EV_RING] = {}, ev2[EV_RING] = {}, ev3[EV_RING] = {}, ev4[EV_RING] = {};  // phase boundaries of a render
     hipEvent_t ev_fork[EV_RING] = {}, ev_s0[EV_RING] = {}, ev_s1[EV_RING] = {}, ev_s2[EV_RING] = {};        // ... of its side stream
     bool slot_ev2_is_s1[EV_RING] = {};       // the slot's frame ran its pass on the frame's stream and did not record ev2: the later of ev1 and ev_s1 marks that point (crt_launch.hip, crt_kernel_times_ms)
-    bool shadow0_by_slot = false;            // the last filter frame's bulk shadow pass walked slots, not pixels: the GI mode, a frame without fixed slots (crt_launch.hip; crt_describe_kernels)
+    bool shadow0_by_pixel = true;            // the last filter frame's plan walked its bulk shadow pass by pixel, not by slot (the GI mode, a frame without fixed slots): crt_launch.hip, finish_plan
     uint64_t launches = 0;
     uint32_t width = 0, height = 0, tiles_x = 0, tiles_y = 0;
     SceneArgs scene{};                // host copy of what crt_create uploads to d_scene
@@ -125,6 +126,7 @@ struct crt_ctx {
     uint64_t stream_items = 0;        // work items the stream buffers are sized for
     uint64_t overflows = 0;           // frames redone by the fallback (diagnostic)
     uint32_t n_lights = 0;
+    uint32_t lights() const { return n_lights ? n_lights : 1u; }   // what sizes are made for: a scene without lights still has queues
     crt_tuning tuning{};
     std::string bvh_note;             // why this scene has no candidate filter (empty: it has one)
     std::string bvh_stats;            // ... and what it consists of
@@ -193,6 +195,7 @@ CRT_INTERNAL int ensure_items(crt_ctx *ctx, size_t n);
 CRT_INTERNAL int launch_render(crt_ctx *ctx, const crt_options *o, uint32_t n_items, float *d_out, uint32_t packed, hipStream_t stream);
 CRT_INTERNAL void note_overflow(crt_ctx *ctx);
 CRT_INTERNAL int fetch_counters(crt_ctx *ctx, const crt_options *o, uint64_t pixels);
+CRT_INTERNAL std::string describe_frame_kernels(const crt_ctx *ctx);   // crt_describe_kernels: a production frame's plan, named from the kernels' tables
 // ---- crt_query.hip: what the GI frame calls (crt_giframe.hip) run of the queries, on the queries' scratch
 CRT_INTERNAL void query_destroy(crt_ctx *ctx);
 CRT_INTERNAL int query_begin(crt_ctx *ctx, hipStream_t stream, CallKind kind);   // before a call on `stream`: the waiting rule, the scratch every query needs
