@@ -188,6 +188,29 @@ def make_variance_estimate(**fields):
     return _make_settings(VarianceEstimate, "variance_estimate", fields)
 
 
+class Bake(C.Structure):
+    """crt_bake, 28 bytes: what is baked (make_bake fills it)"""
+    _fields_ = [("mesh", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("samples", C.c_uint32), ("dilate", C.c_uint32),
+                ("check_probes", C.c_uint32), ("probe_offset", C.c_float)]
+
+
+class BakeStats(C.Structure):
+    """crt_bake_stats: the last Tracer.bake_lightmap call"""
+    _fields_ = [("texels", C.c_uint64), ("covered", C.c_uint64), ("dilated", C.c_uint64), ("probe_self", C.c_uint64),
+                ("raster_ms", C.c_double), ("shoot_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+def make_bake(**fields):
+    """crt_bake_defaults (mesh 0, 256 x 256, 1 sample, dilate 2, check_probes 0, probe_offset 1e-3) with the given fields replaced."""
+    return _make_settings(Bake, "bake", fields, reserved=())
+
+
+# crt_bake_texel as a numpy record (48 bytes; the layout of a torch.uint8 [n, 48] tensor)
+BAKE_TEXEL_DTYPE = np.dtype([("point", np.float32, 3), ("u", np.float32), ("normal", np.float32, 3), ("v", np.float32), ("triangle", np.uint32),
+                             ("mesh", np.uint32), ("status", np.uint32), ("pad", np.uint32)])
+BAKE_EMPTY, BAKE_COVERED, BAKE_DILATED = range(3)
+
+
 def make_pose(position, matrix):
     """a crt_camera_pose of 3 and 9 floats"""
     pose = CameraPose()
@@ -253,6 +276,7 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_st
                   "crt_render_adaptive_split", "crt_read_split_state", "crt_render_denoised_split", "crt_render_accumulated_split", "crt_history_frames_split",
                   "crt_guide_work_bytes", "crt_guide_rays", "crt_guide_rays_device", "crt_set_guide_bounces", "crt_guide_bounces",
                   "crt_variance_estimate_defaults", "crt_variance_estimate_device", "crt_set_variance_estimate", "crt_get_variance_estimate",
+                  "crt_bake_defaults", "crt_bake_work_bytes", "crt_bake_texels_device", "crt_bake_dilate_device", "crt_bake_lightmap", "crt_get_bake_stats",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -367,6 +391,14 @@ def lib():
     L.crt_set_variance_estimate.argtypes = [vp, C.POINTER(VarianceEstimate)]
     L.crt_get_variance_estimate.argtypes = [vp, C.POINTER(VarianceEstimate)]
     L.crt_history_frames_split.restype = u32
+    L.crt_bake_defaults.argtypes = [C.POINTER(Bake)]
+    L.crt_bake_defaults.restype = None
+    L.crt_bake_work_bytes.argtypes = [u32, u32]
+    L.crt_bake_work_bytes.restype = C.c_size_t
+    L.crt_bake_texels_device.argtypes = [vp, C.POINTER(Bake), vp, vp, vp, vp]
+    L.crt_bake_dilate_device.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp]
+    L.crt_bake_lightmap.argtypes = [vp, C.POINTER(Bake), C.POINTER(Options), vp, vp, vp, vp]
+    L.crt_get_bake_stats.argtypes = [vp, C.POINTER(BakeStats)]
     L.crt_host_shoot_stats_layout.argtypes = [C.POINTER(u32), u32]
     L.crt_host_shoot_stats_layout.restype = u32
     L.crt_get_kernel_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -1055,6 +1087,49 @@ class Tracer:
         """The frames merged into the history (split: into the split calls' history) since the last history_reset."""
         self._single("history_frames")
         return int((lib().crt_history_frames_split if split else lib().crt_history_frames)(self.ctx))
+
+    # ---- lightmap baking (include/crt_hip.h: crt_bake_texels_device, crt_bake_dilate_device, crt_bake_lightmap, crt_get_bake_stats)
+    @staticmethod
+    def bake_work_bytes(width, height) -> int:
+        return int(lib().crt_bake_work_bytes(int(width), int(height)))
+
+    def bake_texels_device(self, bake, d_texels_ptr, d_rays_ptr, d_work_ptr, stream_ptr=None):
+        """The records of every texel of the bake's map -> texels uint8 [H * W, 48] (BAKE_TEXEL_DTYPE, aligned to 16 bytes) and the probe
+        rays of the covered ones -> rays float32 [H * W, 6] (an empty texel's ray is not written); work: bake_work_bytes(W, H) bytes,
+        aligned to 16.  Enqueues and returns (the first call for a mesh reads the scene's trees back once)."""
+        self._single("bake_texels_device")
+        self._check(lib().crt_bake_texels_device(self.ctx, C.byref(bake), C.c_void_p(d_texels_ptr), C.c_void_p(d_rays_ptr), C.c_void_p(d_work_ptr),
+                                                 C.c_void_p(stream_ptr or 0)))
+
+    def bake_dilate_device(self, width, height, passes, d_rgb_ptr, d_status_ptr, d_work_ptr, stream_ptr=None):
+        """`passes` dilation passes on rgb float32 [H * W * 3] and status uint8 [H * W], in place; work: bake_work_bytes(W, H) bytes, aligned
+        to 16.  Enqueues and returns."""
+        self._single("bake_dilate_device")
+        self._check(lib().crt_bake_dilate_device(self.ctx, int(width), int(height), int(passes), C.c_void_p(d_rgb_ptr), C.c_void_p(d_status_ptr),
+                                                 C.c_void_p(d_work_ptr), C.c_void_p(stream_ptr or 0)))
+
+    def bake_lightmap(self, mesh, width, height, options=None, samples=1, dilate=2, probe_offset=1e-3, check_probes=False, rgb8=False):
+        """The lightmap of `mesh`'s UV layout, width x height texels, row 0 the top: every covered texel is what shootRay returns for its
+        probe ray (options: make_options; None: the defaults; with use_gi the mean of `samples` GI samples), the texels beside a chart are
+        filled by `dilate` dilation passes -> (rgb float32 [H, W, 3], status uint8 [H, W] of BAKE_EMPTY / BAKE_COVERED / BAKE_DILATED,
+        texels BAKE_TEXEL_DTYPE [H, W]); with rgb8 the PPMColor quantisation uint8 [H, W, 3] as a fourth.  bake_stats() describes the call."""
+        self._single("bake_lightmap")
+        b = make_bake(mesh=int(mesh), width=int(width), height=int(height), samples=int(samples), dilate=int(dilate), check_probes=int(bool(check_probes)),
+                      probe_offset=float(probe_offset))
+        o = options if options is not None else make_options()
+        shape = (max(int(height), 0), max(int(width), 0))
+        rgb = np.zeros(shape + (3,), dtype=np.float32)
+        status = np.zeros(shape, dtype=np.uint8)
+        texels = np.zeros(shape, dtype=BAKE_TEXEL_DTYPE)
+        q8 = np.zeros(shape + (3,), dtype=np.uint8) if rgb8 else None
+        self._check(lib().crt_bake_lightmap(self.ctx, C.byref(b), C.byref(o), _p(rgb), _p(q8) if rgb8 else None, _p(status), _p(texels)))
+        return (rgb, status, texels) + ((q8,) if rgb8 else ())
+
+    def bake_stats(self) -> BakeStats:
+        self._single("bake_stats")
+        st = BakeStats()
+        self._check(lib().crt_get_bake_stats(self.ctx, C.byref(st)))
+        return st
 
     # ---- chain guides (include/crt_hip.h: crt_guide_rays*, crt_set_guide_bounces): filter guides that follow mirrors and glass
     def guide_work_bytes(self, n) -> int:

@@ -29,7 +29,9 @@ int main(int argc, char **argv) {
                  "        it needs --denoise;\n"
                  "        --variance-estimate [MIN_HISTORY]: a pixel whose moments stand for fewer samples gets a 7x7 estimate of its variance before the\n"
                  "        filter, crt_hip.h's \"Variance estimate\", its defaults but for MIN_HISTORY; it needs --denoise)\n"
-                 "       [--probe ROW COL]   (no render: the closest hit of that pixel's camera ray; out.ppm is not written)\n",
+                 "       [--probe ROW COL]   (no render: the closest hit of that pixel's camera ray; out.ppm is not written)\n"
+                 "       [--bake MESH WIDTH HEIGHT [--gi GI_SAMPLE_SIZE SAMPLES_PER_TEXEL [--seed S]] [--dilate K] [--probe-offset X]]   (no render: out.ppm is the\n"
+                 "        WIDTH x HEIGHT lightmap of that mesh's UV layout, crt_hip.h's \"Lightmap baking\", its defaults but for what is given; one device)\n",
                  argv[0]);
     return 2;
   }
@@ -51,6 +53,11 @@ int main(int argc, char **argv) {
   float minHistory = -1.0f;  // (-1: crt_variance_estimate_defaults')
   bool probe = false;
   unsigned probeRow = 0, probeCol = 0;
+  bool bake = false;
+  unsigned bakeMesh = 0, bakeWidth = 0, bakeHeight = 0;
+  bool dilateGiven = false, probeOffsetGiven = false;   // (not given: crt_bake_defaults')
+  long long bakeDilate = 0;
+  float probeOffset = 0.0f;
   for (int i = 3; i < argc; i++) {
     if (!strcmp(argv[i], "--folder") && i + 1 < argc) folder = argv[++i];
     else if (!strcmp(argv[i], "--depth") && i + 1 < argc) depth = (unsigned)atoi(argv[++i]);
@@ -86,7 +93,24 @@ int main(int argc, char **argv) {
       varianceEstimate = true;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') minHistory = (float)atof(argv[++i]);
     }
+    else if (!strcmp(argv[i], "--bake") && i + 3 < argc) {
+      bake = true; bakeMesh = (unsigned)atoi(argv[++i]); bakeWidth = (unsigned)atoi(argv[++i]); bakeHeight = (unsigned)atoi(argv[++i]);
+    }
+    else if (!strcmp(argv[i], "--dilate") && i + 1 < argc) { dilateGiven = true; bakeDilate = atoll(argv[++i]); }
+    else if (!strcmp(argv[i], "--probe-offset") && i + 1 < argc) { probeOffsetGiven = true; probeOffset = (float)atof(argv[++i]); }
     else if (!strcmp(argv[i], "--probe") && i + 2 < argc) { probe = true; probeRow = (unsigned)atoi(argv[++i]); probeCol = (unsigned)atoi(argv[++i]); }
+  }
+  if (bake && (devices.size() > 0 || progressive || adaptive || denoise || probe)) {
+    std::fprintf(stderr, "error: --bake needs one device and excludes --progressive, --adaptive, --denoise and --probe\n");
+    return 2;
+  }
+  if (dilateGiven && (bakeDilate < 0 || bakeDilate > 0xFFFFFFFFll)) {
+    std::fprintf(stderr, "error: --dilate takes a pass count of 0 .. 4294967295\n");
+    return 2;
+  }
+  if ((dilateGiven || probeOffsetGiven) && !bake) {
+    std::fprintf(stderr, "error: --dilate and --probe-offset need --bake\n");
+    return 2;
   }
   if (progressive && (!useGI || devices.size() > 0)) {
     std::fprintf(stderr, "error: --progressive needs --gi and one device\n");
@@ -140,6 +164,21 @@ int main(int argc, char **argv) {
       return 0;
     }
     crt::RenderOptions options((crt::RenderOptimization)mode, depth, useGI, giSamples, raysPerPixel);
+    if (bake) {
+      // the lightmap of a mesh's UV layout: with --gi N R, N GI samples per hit and R samples per texel
+      crt_bake b;
+      crt_bake_defaults(&b);
+      b.mesh = bakeMesh; b.width = bakeWidth; b.height = bakeHeight;
+      if (useGI) b.samples = raysPerPixel;
+      if (dilateGiven) b.dilate = (uint32_t)bakeDilate;
+      if (probeOffsetGiven) b.probe_offset = probeOffset;   // (the library refuses one that is not above 0)
+      tracer.setGISeed(seed);
+      crt_bake_stats bs{};
+      tracer.bakeLightmap(outPath, b, options, nullptr, &bs);
+      std::printf("{\"texels\": %llu, \"covered\": %llu, \"dilated\": %llu, \"raster_ms\": %.4f, \"shoot_ms\": %.4f, \"total_ms\": %.4f}\n",
+                  (unsigned long long)bs.texels, (unsigned long long)bs.covered, (unsigned long long)bs.dilated, bs.raster_ms, bs.shoot_ms, bs.total_ms);
+      return 0;
+    }
     if (guideBounces > 0) tracer.setGuideBounces((unsigned)guideBounces);
     if (varianceEstimate) {
       crt_variance_estimate e;

@@ -14,6 +14,7 @@
 //   crt_split.hip     the split GI frames' primitives: a sample's direct light kept, the fold of the two parts, putting them back together
 //   crt_guides.hip    the chain guides' kernel launch and work-area layout: filter guides that follow mirrors and glass
 //   crt_variance.hip  the variance estimate's primitive: a 7x7 cross-bilateral estimate of the variance where a pixel's history is short
+//   crt_bake.hip      lightmap baking: a mesh's UV texels rasterised to records and probe rays, lit by the radiance queries, dilated
 //   crt_testhooks.hip unit-test hooks (libcrt_hip_test.so only)
 #pragma once
 
@@ -138,6 +139,7 @@ struct crt_ctx {
     int num_cus = 0;
     struct crt_query_state *query = nullptr;   // crt_query.hip: the ray queries' scratch and statistics, created by the first query
     struct crt_giframe_state *giframe = nullptr;   // crt_giframe.hip: the GI frame under way and the histories, created by the first frame call
+    struct crt_bake_state *bake = nullptr;     // crt_bake.hip: the meshes' triangle lists and the bake call's arrays, created by the first bake call
     uint64_t scratch_generation = 0;           // crt_query_scratch_generation: every growth of an array of either (device_array.h)
     uint32_t guide_bounces = 0;                // crt_set_guide_bounces: > 0, the frame calls' spatial filter runs under chain guides
     uint64_t query_host_rays = QUERY_HOST_RAYS, query_launch_rays = QUERY_LAUNCH_RAYS, shoot_pass_rays = SHOOT_PASS_RAYS;   // ... and its chunk sizes
@@ -201,6 +203,7 @@ CRT_INTERNAL void query_destroy(crt_ctx *ctx);
 CRT_INTERNAL int query_begin(crt_ctx *ctx, hipStream_t stream, CallKind kind);   // before a call on `stream`: the waiting rule, the scratch every query needs
 // the GI radiance calls' own check for a frame's rays (PRIMARY rays, the context's arrays); *pass: the rays of one pass
 CRT_INTERNAL int query_gi_check(crt_ctx *ctx, const char *what, const crt_options *options, uint64_t *pass);
+CRT_INTERNAL int query_shoot_check(crt_ctx *ctx, const char *what, const crt_options *options);   // what the radiance entry point of options->use_gi would refuse of them
 // crt_shoot_rays_gi_device (d_direct: crt_shoot_rays_gi_split_device) for n PRIMARY rays, `pass` at a time
 CRT_INTERNAL int query_gi_run(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t *d_keys, uint64_t n, const crt_options *options, float *d_rgb,
                               float *d_direct, uint64_t pass, hipStream_t stream);
@@ -216,6 +219,8 @@ CRT_INTERNAL int guide_enqueue(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, 
 CRT_INTERNAL void giframe_destroy(crt_ctx *ctx);
 CRT_INTERNAL void giframe_reset(crt_ctx *ctx);   // crt_set_camera, crt_render*: the frame under way has ended, crt_progressive_samples is 0 again
 CRT_INTERNAL int progressive_check(crt_ctx *ctx, const char *what, const uint32_t *d_pixels, uint64_t n);   // what the fold's primitives ask of (d_pixels, n)
+// ---- crt_bake.hip
+CRT_INTERNAL void bake_destroy(crt_ctx *ctx);
 // ---- crt_denoise.hip: the denoiser's settings check and launches, for crt_render_denoised (crt_giframe.hip)
 CRT_INTERNAL int denoise_check(crt_ctx *ctx, const char *what, const crt_denoise *d);
 CRT_INTERNAL int denoise_launch_variance(crt_ctx *ctx, const float *d_sum, const float *d_sq, const uint32_t *d_counts, uint64_t n, float *d_mean,

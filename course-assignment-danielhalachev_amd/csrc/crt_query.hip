@@ -970,6 +970,14 @@ int query_gi_check(crt_ctx *ctx, const char *what, const crt_options *options, u
     return query_check(ctx, shoot_needs(what, ctx, options, ctx, CRT_RAY_PRIMARY, true, pass));
 }
 
+// what crt_shoot_rays_device (use_gi == 0) or crt_shoot_rays_gi_device (use_gi != 0) would refuse of `options` for REFLECTION rays in the
+// caller's arrays, asked before anything is enqueued: the entry points' own check, so the rules cannot drift apart
+int query_shoot_check(crt_ctx *ctx, const char *what, const crt_options *options) {
+    uint64_t pass = 0;
+    const bool gi = options->use_gi != 0;
+    return query_check(ctx, shoot_needs(what, ctx, options, ctx, CRT_RAY_REFLECTION, gi, gi ? &pass : nullptr));
+}
+
 int query_gi_run(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t *d_keys, uint64_t n, const crt_options *options, float *d_rgb, float *d_direct,
                  const uint64_t pass, hipStream_t stream) {
     const ShootGi gi{d_keys, 0u, d_direct};

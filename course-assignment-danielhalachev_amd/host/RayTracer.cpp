@@ -304,6 +304,29 @@ std::vector<float> RayTracer::shootRaysGI(const std::vector<crt_ray> &rays, cons
   return rgb;
 }
 
+std::vector<float> RayTracer::bakeLightmap(const std::string &pathToImage, const crt_bake &bake, const RenderOptions &ro, std::vector<unsigned char> *status,
+                                           crt_bake_stats *stats) {
+  if (multi) throw std::runtime_error("bakeLightmap: not available on a multi-device tracer");
+  const size_t n = (size_t)bake.width * bake.height;
+  std::vector<float> rgb(n * 3);
+  std::vector<uint8_t> q(pathToImage.empty() ? 0 : n * 3);
+  if (status) status->assign(n, 0);
+  crt_options options{};
+  options.max_depth = ro.MAX_DEPTH;
+  options.shadow_bias = ro.SHADOW_BIAS;
+  options.reflection_bias = ro.REFLECTION_BIAS;
+  options.refraction_bias = ro.REFRACTION_BIAS;
+  options.use_gi = ro.USE_GI ? 1u : 0u;
+  options.gi_sample_size = ro.GI_SAMPLE_SIZE;
+  options.monte_carlo_bias = ro.MONTE_CARLO_BIAS;
+  options.gi_seed = giSeed;
+  if (crt_bake_lightmap(ctx, &bake, &options, n ? rgb.data() : nullptr, q.empty() ? nullptr : q.data(), status && n ? status->data() : nullptr, nullptr) != CRT_OK)
+    throw std::runtime_error(std::string("bakeLightmap failed: ") + crt_last_error(ctx));
+  if (stats && crt_get_bake_stats(ctx, stats) != CRT_OK) throw std::runtime_error(std::string("bakeLightmap failed: ") + crt_last_error(ctx));
+  if (!pathToImage.empty()) writePPMQuantized(pathToImage, q.data(), bake.width, bake.height);
+  return rgb;
+}
+
 crt_query_stats RayTracer::queryStats() const {
   crt_query_stats s{};
   if (!multi) crt_get_query_stats(ctx, &s);

@@ -117,6 +117,14 @@ class RayTracer {
   std::vector<float> shootRaysGI(const std::vector<crt_ray> &rays, const std::vector<uint32_t> &keys, const RenderOptions &renderOptions,
                                  unsigned int rayType = CRT_RAY_REFLECTION, crt_shoot_stats *stats = nullptr);
 
+  // ---- lightmap baking (crt_hip.h: "Lightmap baking", crt_bake_lightmap): the bake.width x bake.height lightmap of mesh bake.mesh's UV layout,
+  // row 0 the top, 3 floats per texel: every covered texel is what shootRay returns for its probe ray -- MAX_DEPTH and the biases from
+  // renderOptions; with USE_GI the mean of bake.samples GI samples of GI_SAMPLE_SIZE rays per hit under the tracer's seed (setGISeed) --,
+  // the texels beside a chart filled by bake.dilate dilation passes.  pathToImage: the map as a PPM when it is not empty; *status: a byte a
+  // texel (CRT_BAKE_EMPTY / COVERED / DILATED), *stats: the call's crt_bake_stats, when they are given.  Single-device tracers only.
+  std::vector<float> bakeLightmap(const std::string &pathToImage, const crt_bake &bake, const RenderOptions &renderOptions,
+                                  std::vector<unsigned char> *status = nullptr, crt_bake_stats *stats = nullptr);
+
   // ---- chain guides (crt_hip.h: "Chain guides", crt_guide_rays): for every ray the guide record of the surface it shows -- the chain of
   // closest hits through reflective and refractive meshes to the first diffuse or constant surface, a miss or maxBounces (<= 63) --, with
   // the path length as t and a tagged mesh; the biases come from renderOptions.  *status: a byte a ray (bits 0-5 the bounces, bit 7 cut),

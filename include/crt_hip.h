@@ -1053,6 +1053,99 @@ int crt_variance_estimate_device(crt_ctx *ctx, const crt_variance_estimate *est,
 int crt_set_variance_estimate(crt_ctx *ctx, const crt_variance_estimate *est /* NULL: off */);
 int crt_get_variance_estimate(const crt_ctx *ctx, crt_variance_estimate *out /* may be NULL */);
 
+/* ---- Lightmap baking: a mesh's UV texels lit by the radiance queries -- ambient-occlusion and light baking, lightmap texels with bounce
+ * light.  The library says where a texel of a mesh's UV layout (crt_scene_desc::vertex_uvs) lies in the world, which triangle owns it and
+ * through which probe ray it is lit; the colours are crt_shoot_rays_device's or, with crt_options::use_gi, crt_shoot_rays_gi_device's, so
+ * both modes rest on queries that are pinned to the reference.  Kernels: csrc/kernel_bake.h; the rule, one header for host and device:
+ * csrc/bake_rule.h.  It is additive: no frame, walk, query, radiance or GI-frame kernel is involved or changed.  Single-device contexts only.
+ *
+ * The rule (csrc/bake_rule.h, verbatim; tests/bake_sets.py restates it in numpy and the GPU gives its bits):
+ * Texel centres.  Texel (row, col) of a W x H map, row 0 the top, has the centre
+ *     q.x = ((float)col + 0.5f) / (float)W
+ *     q.y = 1.0f - ((float)row + 0.5f) / (float)H
+ *   the convention of BitmapTexture::getColor (Texture.cpp:62-72: x = (int)(uv.x * W), y = (int)((1 - uv.y) * H)): a baked map read back
+ *   as a bitmap texture lands on the texel that was baked.
+ * Coverage.  a, b, c are the x and y of the three vertex_uvs of a triangle, finite(x) is (x - x) == 0.0f:
+ *     A = (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x)
+ *     the triangle covers nothing unless finite(A) and A != 0
+ *     box: umin, umax, vmin, vmax the smallest and largest of the three x and of the three y
+ *         f0 = umin * (float)W; f1 = umax * (float)W; g0 = (1.0f - vmax) * (float)H; g1 = (1.0f - vmin) * (float)H
+ *         each clamped: f < 0 ? 0 : (f > (float)W ? (float)W : f), with (float)H for g
+ *         col0 = max((int)f0 - 1, 0); col1 = min((int)f1 + 1, W - 1); row0 = max((int)g0 - 1, 0); row1 = min((int)g1 + 1, H - 1)
+ *     only texels with col0 <= col <= col1 and row0 <= row <= row1 are considered: integer comparison, before any address is formed
+ *     e1 = (q.x - a.x) * (c.y - a.y) - (q.y - a.y) * (c.x - a.x)
+ *     e2 = (b.x - a.x) * (q.y - a.y) - (b.y - a.y) * (q.x - a.x)
+ *     e0 = (b.x - q.x) * (c.y - q.y) - (b.y - q.y) * (c.x - q.x)
+ *     covered: A > 0 ? (e0 >= 0 && e1 >= 0 && e2 >= 0) : (e0 <= 0 && e1 <= 0 && e2 <= 0)
+ *   The test is inclusive, so both triangles at a shared edge cover the texels on it; a NaN covers nothing.
+ * Ownership.  A texel's owner is the covering triangle of the mesh with the LOWEST global triangle index; no covering triangle: EMPTY.
+ * Record.  With the owner's crt_triangle (v0, v1, v2, the unit face normal nx, ny, nz):
+ *     u = e1 / A; v = e2 / A
+ *     w = (1.0f - u) - v
+ *     point.k = (v0.k * w + v1.k * u) + v2.k * v, k = 0..2
+ *     normal = (nx, ny, nz)
+ *   u is the weight of vertex 1 and v the weight of vertex 2, the (u, v) of crt_hit and of Texture::getColor.
+ * Probe ray.  origin.k = point.k + normal.k * probe_offset; direction.k = -normal.k; the ray type is CRT_RAY_REFLECTION, so back faces
+ *   are not culled.  A texel's colour is DEFINED as what shootRay returns for that ray.
+ * Keys in the GI mode.  Sample s of texel p = row * W + col has the key crt_gi_mix(crt_gi_mix(gi_seed, p), s); every sample of a texel
+ *   uses the same probe ray.  The fold: sum = (s == 0 ? 0 : sum) + c_s; mean = sum * (1.0f / (float)(s + 1)).
+ * Dilation.  A pass reads the statuses and colours as they are at the START of the pass.  A texel with status EMPTY takes the colour of
+ *   the first of its neighbours, in the order (row - 1, col) (row + 1, col) (row, col - 1) (row, col + 1) (row - 1, col - 1)
+ *   (row - 1, col + 1) (row + 1, col - 1) (row + 1, col + 1), whose status is not EMPTY, and becomes DILATED; every other texel keeps
+ *   what it has.  A pass copies and does no arithmetic; neighbours outside the map are skipped by integer comparison.  After max(W, H)
+ *   passes nothing can change any more, so no more than that are run.
+ *
+ * Known limits.
+ *   * There is no jitter inside a texel: every sample of a texel goes through its centre.
+ *   * Overlapping UV charts resolve to the lowest triangle index.
+ *   * A probe can meet another surface lying within probe_offset in front of the texel.
+ *   * Mirrors and glass are baked as seen along the normal.
+ *   * Multi-device contexts are not supported.
+ * crt_bake: mesh < n_meshes; width, height and samples > 0; width * height < 2^31; probe_offset finite and > 0; the scene must have been
+ *   created with vertex_uvs: anything else is CRT_ERR_INVALID, with nothing enqueued and nothing changed.  crt_bake_defaults: mesh 0,
+ *   256 x 256, 1 sample, dilate 2, check_probes 0, probe_offset 1e-3f.  A mesh's triangles are the ones its tree's leaves list.
+ * crt_bake_texel, 48 bytes: {point[3], u, normal[3], v, triangle, mesh, status, pad}.  A COVERED texel holds the record above, triangle the
+ *   owner's global index, mesh the bake's mesh; an EMPTY texel holds 0 in every float, triangle = 0xFFFFFFFF, the bake's mesh and status 0;
+ *   pad is written as 0.
+ * crt_bake_texels_device: the records of every texel of the width x height map to d_texels (row-major, aligned to 16 bytes) and the probe
+ *   rays of the COVERED texels to d_rays (by texel; an EMPTY texel's ray is not written); samples, dilate and check_probes are not read.
+ *   d_work: crt_bake_work_bytes(width, height) bytes, aligned to 16, the caller's; the call keeps the owner plane in it.  It only
+ *   ENQUEUES on `stream`: no wait, no allocation, no readback -- except that the FIRST call for a mesh reads the scene's trees back and
+ *   allocates the mesh's triangle list, which is kept for the context's life, and that a pending crt_render_async frame is waited for.
+ *   Inside a stream capture it refuses with CRT_ERR_INVALID what would do either, before it enqueues anything.  Two runs give the same
+ *   bytes: ownership is a minimum, whatever the order of the triangles' waves.  Calls that bake the same mesh must be ordered by the caller
+ *   (the mesh's list of large triangles is the context's).
+ * crt_bake_dilate_device: `passes` dilation passes on the caller's map d_rgb (width * height * 3 floats) and d_status (width * height
+ *   bytes), in place as the caller sees it: the passes ping-pong between the map and d_work (crt_bake_work_bytes bytes, aligned to 16) and
+ *   the result ends in d_rgb and d_status.  Enqueue-only: no wait, no allocation, no readback; it can be captured.  passes == 0 is CRT_OK
+ *   and touches nothing.
+ * crt_bake_lightmap is the frame-level call, synchronous; out_rgb (width * height * 3 floats), out_rgb8 (width * height * 3 bytes),
+ *   out_status (width * height bytes) and out_texels (width * height records) are host memory and every one may be NULL.  It rasterises,
+ *   reads back ONE count (the covered texels), compacts the covered texels into a row-major list (no atomic decides a position), shoots
+ *   the list's probe rays as CRT_RAY_REFLECTION -- use_gi == 0: through crt_shoot_rays_device, `samples` is ignored and a texel is that
+ *   colour as it is; use_gi != 0: through crt_shoot_rays_gi_device `samples` times in order under the keys above, with the fold --,
+ *   scatters to the map (EMPTY texels are 0), dilates, and quantises with crt_quantize_device.  It shoots in the queries' usual passes, so
+ *   the level arrays are bounded by one pass.  With check_probes it also traces the probe rays with crt_trace_rays_device and counts in
+ *   crt_bake_stats::probe_self the texels whose probe's closest hit is the owner triangle; otherwise probe_self is 0.
+ *   Like the queries it leaves the persistent colour buffer, crt_stats, the ray queues' sizing, the progressive and adaptive frame and
+ *   the history exactly as they were, and it waits for a pending crt_render_async frame.  CRT_ERR_INVALID, with nothing changed: what
+ *   crt_bake refuses above, NULL options, and whatever the underlying radiance call refuses (max_depth + 1 > 64, gi_sample_size > 64,
+ *   levels that cannot be held).  Its arrays are the context's: they grow and are kept.
+ * crt_get_bake_stats: the last crt_bake_lightmap call; raster_ms spans the rasteriser, the records, the count's readback and the
+ *   compaction, shoot_ms the radiance calls, the scatter and the probes' trace, total_ms the whole call's device work (HIP events). */
+typedef struct crt_bake { uint32_t mesh, width, height, samples, dilate, check_probes; float probe_offset; } crt_bake;   /* 28 bytes */
+void crt_bake_defaults(crt_bake *b);                /* mesh 0, 256 x 256, 1 sample, dilate 2, check_probes 0, probe_offset 1e-3f */
+typedef struct crt_bake_texel { float point[3], u, normal[3], v; uint32_t triangle, mesh, status, pad; } crt_bake_texel;   /* 48 bytes */
+enum { CRT_BAKE_EMPTY = 0, CRT_BAKE_COVERED = 1, CRT_BAKE_DILATED = 2 };
+typedef struct crt_bake_stats { uint64_t texels, covered, dilated, probe_self; double raster_ms, shoot_ms, total_ms; } crt_bake_stats;
+size_t crt_bake_work_bytes(uint32_t width, uint32_t height);   /* 0 when width * height is 0 or >= 2^31 */
+int crt_bake_texels_device(crt_ctx *ctx, const crt_bake *bake, crt_bake_texel *d_texels, crt_ray *d_rays, void *d_work, void *stream);
+int crt_bake_dilate_device(crt_ctx *ctx, uint32_t width, uint32_t height, uint32_t passes, float *d_rgb, uint8_t *d_status, void *d_work,
+                           void *stream);
+int crt_bake_lightmap(crt_ctx *ctx, const crt_bake *bake, const crt_options *options, float *out_rgb, uint8_t *out_rgb8, uint8_t *out_status,
+                      crt_bake_texel *out_texels);
+int crt_get_bake_stats(crt_ctx *ctx, crt_bake_stats *out);
+
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
  * stream per listed device (a device may be listed more than once); the covered 8x8 tiles are dealt round-robin, every
