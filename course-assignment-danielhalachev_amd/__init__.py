@@ -211,6 +211,36 @@ BAKE_TEXEL_DTYPE = np.dtype([("point", np.float32, 3), ("u", np.float32), ("norm
 BAKE_EMPTY, BAKE_COVERED, BAKE_DILATED = range(3)
 
 
+class ProbeVolume(C.Structure):
+    """crt_probe_volume, 48 bytes: where the probes stand and how many rays each shoots (make_probe_volume fills it)"""
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("nx", C.c_uint32), ("ny", C.c_uint32), ("nz", C.c_uint32), ("rays", C.c_uint32),
+                ("gi_seed", C.c_uint32), ("backface_limit", C.c_float)]
+
+
+class ProbeStats(C.Structure):
+    """crt_probe_stats: the last Tracer.bake_probes call"""
+    _fields_ = [("probes", C.c_uint64), ("invalid", C.c_uint64), ("rays", C.c_uint64), ("shoot_ms", C.c_double), ("project_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+
+def make_probe_volume(**fields):
+    """crt_probe_volume_defaults (origin 0, spacing 1, 1 x 1 x 1, 64 rays, gi_seed 0, backface_limit 1.0) with the given fields replaced;
+    origin and spacing take three numbers each."""
+    v = ProbeVolume()
+    lib().crt_probe_volume_defaults(C.byref(v))
+    for k, val in fields.items():
+        if k not in dict(ProbeVolume._fields_):
+            raise KeyError("crt_probe_volume has no field %r" % (k,))
+        setattr(v, k, (C.c_float * 3)(*[float(x) for x in val]) if k in ("origin", "spacing") else val)
+    return v
+
+
+# crt_probe as a numpy record (128 bytes; the layout of a torch.uint8 [n, 128] tensor)
+PROBE_DTYPE = np.dtype([("coef", np.float32, (9, 3)), ("rays", np.uint32), ("back", np.uint32), ("miss", np.uint32), ("state", np.uint32),
+                        ("pad", np.uint32)])
+PROBE_INVALID, PROBE_VALID = range(2)
+
+
 def make_pose(position, matrix):
     """a crt_camera_pose of 3 and 9 floats"""
     pose = CameraPose()
@@ -258,7 +288,7 @@ def tuning_from_string(text):
 
 # every symbol include/crt_hip.h and include/crt_host.h declare; the test hooks are exported by libcrt_hip_test.so only
 TEST_HOOK_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_stack", "crt_debug_set_query_chunks", "crt_test_pow5", "crt_test_gi",
-                     "crt_debug_multi_force_staged", "crt_debug_multi_fail_next_alloc"]
+                     "crt_debug_multi_force_staged", "crt_debug_multi_fail_next_alloc", "crt_debug_set_probe_chunk"]
 DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_stack", "crt_debug_set_query_chunks", "crt_tuning_defaults", "crt_create_tuned", "crt_create", "crt_set_camera", "crt_render", "crt_render_tiles_device", "crt_packed_tile_count",
                   "crt_unpack_tiles_device", "crt_quantize_device", "crt_read_quantized", "crt_kernel_elapsed_ms", "crt_kernel_times_ms",
                   "crt_get_stats", "crt_get_kernel_counters", "crt_synchronize", "crt_destroy", "crt_last_error", "crt_device_count", "crt_test_pow5", "crt_test_gi",
@@ -277,6 +307,8 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_st
                   "crt_guide_work_bytes", "crt_guide_rays", "crt_guide_rays_device", "crt_set_guide_bounces", "crt_guide_bounces",
                   "crt_variance_estimate_defaults", "crt_variance_estimate_device", "crt_set_variance_estimate", "crt_get_variance_estimate",
                   "crt_bake_defaults", "crt_bake_work_bytes", "crt_bake_texels_device", "crt_bake_dilate_device", "crt_bake_lightmap", "crt_get_bake_stats",
+                  "crt_probe_volume_defaults", "crt_probe_rays_device", "crt_probe_project_device", "crt_probe_validity_device", "crt_probe_irradiance_device",
+                  "crt_bake_probes", "crt_probe_irradiance", "crt_get_probe_stats", "crt_debug_set_probe_chunk",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -399,6 +431,15 @@ def lib():
     L.crt_bake_dilate_device.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp]
     L.crt_bake_lightmap.argtypes = [vp, C.POINTER(Bake), C.POINTER(Options), vp, vp, vp, vp]
     L.crt_get_bake_stats.argtypes = [vp, C.POINTER(BakeStats)]
+    L.crt_probe_volume_defaults.argtypes = [C.POINTER(ProbeVolume)]
+    L.crt_probe_volume_defaults.restype = None
+    L.crt_probe_rays_device.argtypes = [vp, C.POINTER(ProbeVolume), u32, u32, vp, vp, vp]
+    L.crt_probe_project_device.argtypes = [vp, vp, vp, u32, u32, vp, vp]
+    L.crt_probe_validity_device.argtypes = [vp, vp, vp, u32, u32, C.c_float, vp, vp]
+    L.crt_probe_irradiance_device.argtypes = [vp, C.POINTER(ProbeVolume), vp, vp, vp, C.c_uint64, vp, vp, vp]
+    L.crt_bake_probes.argtypes = [vp, C.POINTER(ProbeVolume), C.POINTER(Options), vp, vp]
+    L.crt_probe_irradiance.argtypes = [vp, C.POINTER(ProbeVolume), vp, vp, vp, C.c_uint64, vp, vp]
+    L.crt_get_probe_stats.argtypes = [vp, C.POINTER(ProbeStats)]
     L.crt_host_shoot_stats_layout.argtypes = [C.POINTER(u32), u32]
     L.crt_host_shoot_stats_layout.restype = u32
     L.crt_get_kernel_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -1130,6 +1171,74 @@ class Tracer:
         st = BakeStats()
         self._check(lib().crt_get_bake_stats(self.ctx, C.byref(st)))
         return st
+
+    # ---- irradiance probes (include/crt_hip.h: "Irradiance probes")
+    def probe_rays_device(self, volume, first, count, d_rays_ptr, d_keys_ptr=None, stream_ptr=None):
+        """The rays of the probes [first, first + count) of the volume -> rays float32 [count * rays, 6] (aligned to 16 bytes) and, unless
+        d_keys_ptr is None, their GI keys uint32 [count * rays].  Enqueues and returns."""
+        self._single("probe_rays_device")
+        self._check(lib().crt_probe_rays_device(self.ctx, C.byref(volume), int(first), int(count), C.c_void_p(d_rays_ptr), C.c_void_p(d_keys_ptr or 0),
+                                                C.c_void_p(stream_ptr or 0)))
+
+    def probe_project_device(self, d_rays_ptr, d_rgb_ptr, count, rays, d_probes_ptr, stream_ptr=None):
+        """The SH9 records of `count` probes of `rays` rays each from rays float32 [count * rays, 6] and their colours float32
+        [count * rays, 3] -> probes uint8 [count, 128] (PROBE_DTYPE, aligned to 16 bytes).  Enqueues and returns."""
+        self._single("probe_project_device")
+        self._check(lib().crt_probe_project_device(self.ctx, C.c_void_p(d_rays_ptr), C.c_void_p(d_rgb_ptr), int(count), int(rays), C.c_void_p(d_probes_ptr),
+                                                   C.c_void_p(stream_ptr or 0)))
+
+    def probe_validity_device(self, d_rays_ptr, d_hits_ptr, count, rays, backface_limit, d_probes_ptr, stream_ptr=None):
+        """back, miss and state of `count` records from the rays and the hits uint8 [count * rays, 48] trace_rays_device wrote for them.
+        Enqueues and returns."""
+        self._single("probe_validity_device")
+        self._check(lib().crt_probe_validity_device(self.ctx, C.c_void_p(d_rays_ptr), C.c_void_p(d_hits_ptr), int(count), int(rays), float(backface_limit),
+                                                    C.c_void_p(d_probes_ptr), C.c_void_p(stream_ptr or 0)))
+
+    def probe_irradiance_device(self, volume, d_probes_ptr, d_points_ptr, d_normals_ptr, n, d_rgb_ptr, d_status_ptr=None, stream_ptr=None):
+        """The lookup at n points in the volume's records: points, normals float32 [n, 3] -> rgb float32 [n, 3], status uint8 [n] (the
+        corners used, 0: no light) or None.  Enqueues and returns."""
+        self._single("probe_irradiance_device")
+        self._check(lib().crt_probe_irradiance_device(self.ctx, C.byref(volume), C.c_void_p(d_probes_ptr), C.c_void_p(d_points_ptr), C.c_void_p(d_normals_ptr),
+                                                      int(n), C.c_void_p(d_rgb_ptr), C.c_void_p(d_status_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def bake_probes(self, volume, options=None, d_probes_ptr=None):
+        """The volume's probes (make_probe_volume), each the SH9 projection of what shootRay returns for its rays (options: make_options;
+        None: the defaults; with use_gi the GI mode under the volume's gi_seed) -> PROBE_DTYPE [nz, ny, nx]; d_probes_ptr: device memory
+        that takes the records too.  probe_stats() describes the call."""
+        self._single("bake_probes")
+        o = options if options is not None else make_options()
+        out = np.zeros((max(int(volume.nz), 0), max(int(volume.ny), 0), max(int(volume.nx), 0)), dtype=PROBE_DTYPE)
+        self._check(lib().crt_bake_probes(self.ctx, C.byref(volume), C.byref(o), _p(out) if out.size else None, C.c_void_p(d_probes_ptr or 0)))
+        return out
+
+    def probe_irradiance(self, volume, probes, points, normals):
+        """The diffuse light a white Lambertian surface shows at points float32 [n, 3] with normals float32 [n, 3] (used as given) in the
+        volume's records `probes` (as bake_probes returns them) -> (rgb float32 [n, 3], status uint8 [n]: the corners used, 0: no light)."""
+        self._single("probe_irradiance")
+        probes = np.ascontiguousarray(probes, dtype=PROBE_DTYPE).reshape(-1)
+        points = np.ascontiguousarray(points, dtype=np.float32)
+        normals = np.ascontiguousarray(normals, dtype=np.float32)
+        if points.ndim != 2 or points.shape[1] != 3 or normals.shape != points.shape:
+            raise ValueError("points, normals: expected two arrays of shape [n, 3], got %r and %r" % (points.shape, normals.shape))
+        if len(probes) != int(volume.nx) * int(volume.ny) * int(volume.nz):
+            raise ValueError("probes: expected %d x %d x %d records, got %d" % (volume.nz, volume.ny, volume.nx, len(probes)))
+        rgb = np.zeros((len(points), 3), dtype=np.float32)
+        status = np.zeros(len(points), dtype=np.uint8)
+        self._check(lib().crt_probe_irradiance(self.ctx, C.byref(volume), _p(probes), _p(points), _p(normals), len(points), _p(rgb), _p(status)))
+        return rgb, status
+
+    def probe_stats(self) -> ProbeStats:
+        self._single("probe_stats")
+        st = ProbeStats()
+        self._check(lib().crt_get_probe_stats(self.ctx, C.byref(st)))
+        return st
+
+    def set_probe_chunk(self, probes=0):
+        """Test hook (libcrt_hip_test.so): bake_probes takes `probes` probes per chunk from now on; 0 restores the default."""
+        self._single("set_probe_chunk")
+        L = lib()
+        L.crt_debug_set_probe_chunk.argtypes = [C.c_void_p, C.c_uint32]
+        self._check(L.crt_debug_set_probe_chunk(self.ctx, int(probes)))
 
     # ---- chain guides (include/crt_hip.h: crt_guide_rays*, crt_set_guide_bounces): filter guides that follow mirrors and glass
     def guide_work_bytes(self, n) -> int:

@@ -31,7 +31,11 @@ int main(int argc, char **argv) {
                  "        filter, crt_hip.h's \"Variance estimate\", its defaults but for MIN_HISTORY; it needs --denoise)\n"
                  "       [--probe ROW COL]   (no render: the closest hit of that pixel's camera ray; out.ppm is not written)\n"
                  "       [--bake MESH WIDTH HEIGHT [--gi GI_SAMPLE_SIZE SAMPLES_PER_TEXEL [--seed S]] [--dilate K] [--probe-offset X]]   (no render: out.ppm is the\n"
-                 "        WIDTH x HEIGHT lightmap of that mesh's UV layout, crt_hip.h's \"Lightmap baking\", its defaults but for what is given; one device)\n",
+                 "        WIDTH x HEIGHT lightmap of that mesh's UV layout, crt_hip.h's \"Lightmap baking\", its defaults but for what is given; one device)\n"
+                 "       [--probes OX OY OZ SX SY SZ NX NY NZ [--probe-rays R] [--gi GI_SAMPLE_SIZE 1 [--seed S]] [--backface-limit X] [--probes-out FILE]]   (no\n"
+                 "        render: bakes the NX x NY x NZ irradiance probe volume at origin O with spacing S, crt_hip.h's \"Irradiance probes\"; out.ppm is the\n"
+                 "        volume seen by the camera: a hit pixel is the lookup at its point with its normal, every other pixel the background; FILE: the raw\n"
+                 "        128-byte records; one device)\n",
                  argv[0]);
     return 2;
   }
@@ -58,6 +62,11 @@ int main(int argc, char **argv) {
   bool dilateGiven = false, probeOffsetGiven = false;   // (not given: crt_bake_defaults')
   long long bakeDilate = 0;
   float probeOffset = 0.0f;
+  bool probes = false, backfaceLimitGiven = false;
+  crt_probe_volume volume;
+  crt_probe_volume_defaults(&volume);
+  long long probeRays = -1;   // (-1: crt_probe_volume_defaults')
+  std::string probesOut;
   for (int i = 3; i < argc; i++) {
     if (!strcmp(argv[i], "--folder") && i + 1 < argc) folder = argv[++i];
     else if (!strcmp(argv[i], "--depth") && i + 1 < argc) depth = (unsigned)atoi(argv[++i]);
@@ -98,10 +107,31 @@ int main(int argc, char **argv) {
     }
     else if (!strcmp(argv[i], "--dilate") && i + 1 < argc) { dilateGiven = true; bakeDilate = atoll(argv[++i]); }
     else if (!strcmp(argv[i], "--probe-offset") && i + 1 < argc) { probeOffsetGiven = true; probeOffset = (float)atof(argv[++i]); }
+    else if (!strcmp(argv[i], "--probes") && i + 9 < argc) {
+      probes = true;
+      for (int k = 0; k < 3; k++) volume.origin[k] = (float)atof(argv[++i]);
+      for (int k = 0; k < 3; k++) volume.spacing[k] = (float)atof(argv[++i]);
+      volume.nx = (uint32_t)strtoul(argv[++i], nullptr, 10); volume.ny = (uint32_t)strtoul(argv[++i], nullptr, 10); volume.nz = (uint32_t)strtoul(argv[++i], nullptr, 10);
+    }
+    else if (!strcmp(argv[i], "--probe-rays") && i + 1 < argc) probeRays = atoll(argv[++i]);
+    else if (!strcmp(argv[i], "--backface-limit") && i + 1 < argc) { backfaceLimitGiven = true; volume.backface_limit = (float)atof(argv[++i]); }
+    else if (!strcmp(argv[i], "--probes-out") && i + 1 < argc) probesOut = argv[++i];
     else if (!strcmp(argv[i], "--probe") && i + 2 < argc) { probe = true; probeRow = (unsigned)atoi(argv[++i]); probeCol = (unsigned)atoi(argv[++i]); }
   }
   if (bake && (devices.size() > 0 || progressive || adaptive || denoise || probe)) {
     std::fprintf(stderr, "error: --bake needs one device and excludes --progressive, --adaptive, --denoise and --probe\n");
+    return 2;
+  }
+  if (probes && (devices.size() > 0 || progressive || adaptive || denoise || probe || bake)) {
+    std::fprintf(stderr, "error: --probes needs one device and excludes --progressive, --adaptive, --denoise, --probe and --bake\n");
+    return 2;
+  }
+  if ((probeRays != -1 || backfaceLimitGiven || !probesOut.empty()) && !probes) {
+    std::fprintf(stderr, "error: --probe-rays, --backface-limit and --probes-out need --probes\n");
+    return 2;
+  }
+  if (probeRays != -1 && (probeRays < 0 || probeRays > 0xFFFFFFFFll)) {
+    std::fprintf(stderr, "error: --probe-rays takes a ray count\n");
     return 2;
   }
   if (dilateGiven && (bakeDilate < 0 || bakeDilate > 0xFFFFFFFFll)) {
@@ -177,6 +207,25 @@ int main(int argc, char **argv) {
       tracer.bakeLightmap(outPath, b, options, nullptr, &bs);
       std::printf("{\"texels\": %llu, \"covered\": %llu, \"dilated\": %llu, \"raster_ms\": %.4f, \"shoot_ms\": %.4f, \"total_ms\": %.4f}\n",
                   (unsigned long long)bs.texels, (unsigned long long)bs.covered, (unsigned long long)bs.dilated, bs.raster_ms, bs.shoot_ms, bs.total_ms);
+      return 0;
+    }
+    if (probes) {
+      // the irradiance probe volume: with --gi N 1, N GI samples per hit under the keys of --seed
+      if (probeRays != -1) volume.rays = (uint32_t)probeRays;   // (the library refuses a count outside 1 .. 4096)
+      volume.gi_seed = seed;
+      crt_probe_stats ps{};
+      const std::vector<crt_probe> records = tracer.bakeProbes(volume, options, &ps);
+      if (!probesOut.empty()) {
+        FILE *f = std::fopen(probesOut.c_str(), "wb");
+        if (!f || std::fwrite(records.data(), sizeof(crt_probe), records.size(), f) != records.size()) {
+          std::fprintf(stderr, "error: cannot write %s\n", probesOut.c_str());
+          return 1;
+        }
+        std::fclose(f);
+      }
+      tracer.probeIrradianceView(outPath, volume, records);
+      std::printf("{\"probes\": %llu, \"invalid\": %llu, \"rays\": %llu, \"shoot_ms\": %.4f, \"project_ms\": %.4f, \"total_ms\": %.4f}\n",
+                  (unsigned long long)ps.probes, (unsigned long long)ps.invalid, (unsigned long long)ps.rays, ps.shoot_ms, ps.project_ms, ps.total_ms);
       return 0;
     }
     if (guideBounces > 0) tracer.setGuideBounces((unsigned)guideBounces);

@@ -15,6 +15,7 @@
 //   crt_guides.hip    the chain guides' kernel launch and work-area layout: filter guides that follow mirrors and glass
 //   crt_variance.hip  the variance estimate's primitive: a 7x7 cross-bilateral estimate of the variance where a pixel's history is short
 //   crt_bake.hip      lightmap baking: a mesh's UV texels rasterised to records and probe rays, lit by the radiance queries, dilated
+//   crt_probes.hip    the irradiance probe volume: a probe's rays, their colours projected onto SH9 records, validity, the lookup at points
 //   crt_testhooks.hip unit-test hooks (libcrt_hip_test.so only)
 #pragma once
 
@@ -140,6 +141,8 @@ struct crt_ctx {
     struct crt_query_state *query = nullptr;   // crt_query.hip: the ray queries' scratch and statistics, created by the first query
     struct crt_giframe_state *giframe = nullptr;   // crt_giframe.hip: the GI frame under way and the histories, created by the first frame call
     struct crt_bake_state *bake = nullptr;     // crt_bake.hip: the meshes' triangle lists and the bake call's arrays, created by the first bake call
+    struct crt_probe_state *probes = nullptr;  // crt_probes.hip: the probe calls' arrays and statistics, created by the first crt_bake_probes or crt_probe_irradiance
+    uint32_t probe_chunk = 0;                  // crt_debug_set_probe_chunk: probes per chunk of crt_bake_probes (0: as many as fit its scratch)
     uint64_t scratch_generation = 0;           // crt_query_scratch_generation: every growth of an array of either (device_array.h)
     uint32_t guide_bounces = 0;                // crt_set_guide_bounces: > 0, the frame calls' spatial filter runs under chain guides
     uint64_t query_host_rays = QUERY_HOST_RAYS, query_launch_rays = QUERY_LAUNCH_RAYS, shoot_pass_rays = SHOOT_PASS_RAYS;   // ... and its chunk sizes
@@ -221,6 +224,8 @@ CRT_INTERNAL void giframe_reset(crt_ctx *ctx);   // crt_set_camera, crt_render*:
 CRT_INTERNAL int progressive_check(crt_ctx *ctx, const char *what, const uint32_t *d_pixels, uint64_t n);   // what the fold's primitives ask of (d_pixels, n)
 // ---- crt_bake.hip
 CRT_INTERNAL void bake_destroy(crt_ctx *ctx);
+// ---- crt_probes.hip
+CRT_INTERNAL void probes_destroy(crt_ctx *ctx);
 // ---- crt_denoise.hip: the denoiser's settings check and launches, for crt_render_denoised (crt_giframe.hip)
 CRT_INTERNAL int denoise_check(crt_ctx *ctx, const char *what, const crt_denoise *d);
 CRT_INTERNAL int denoise_launch_variance(crt_ctx *ctx, const float *d_sum, const float *d_sq, const uint32_t *d_counts, uint64_t n, float *d_mean,

@@ -1,0 +1,261 @@
+// crt_probes.hip -- the irradiance probe volume (include/crt_hip.h: "Irradiance probes"): crt_probe_volume_defaults, the four enqueue-only
+// primitives crt_probe_rays_device, crt_probe_project_device, crt_probe_validity_device and crt_probe_irradiance_device, the synchronous
+// crt_bake_probes and crt_probe_irradiance, and crt_get_probe_stats.  Kernels: csrc/kernel_probes.h; the rule: csrc/probe_rule.h.  The
+// colours are the radiance queries' (crt_shoot_rays_device, crt_shoot_rays_gi_device) and the hits crt_trace_rays_device's, called as any
+// caller calls them; nothing of a frame, a walk, a query or a lightmap bake is touched.
+#include "crt_internal.h"
+#include "device_array.h"
+
+namespace {
+#include "kernel_probes.h"
+}  // namespace
+
+static_assert(sizeof(crt_probe_volume) == 48 && sizeof(crt_probe_grid) == 48 && offsetof(crt_probe_volume, nx) == offsetof(crt_probe_grid, n) &&
+                  offsetof(crt_probe_volume, rays) == offsetof(crt_probe_grid, rays) && offsetof(crt_probe_volume, gi_seed) == offsetof(crt_probe_grid, gi_seed) &&
+                  offsetof(crt_probe_volume, backface_limit) == offsetof(crt_probe_grid, backface_limit),
+              "the rule reads crt_probe_volume as it is");
+static_assert(sizeof(crt_probe) == 128 && offsetof(crt_probe, rays) == 4 * CRT_PROBE_WORD_RAYS && offsetof(crt_probe, back) == 4 * CRT_PROBE_WORD_BACK &&
+                  offsetof(crt_probe, miss) == 4 * CRT_PROBE_WORD_MISS && offsetof(crt_probe, state) == 4 * CRT_PROBE_WORD_STATE &&
+                  offsetof(crt_probe, pad) == 4 * CRT_PROBE_WORD_PAD,
+              "a record is eight 16-byte stores, the state in the last");
+static_assert(CRT_PROBE_INVALID == CRT_PROBE_STATE_INVALID && CRT_PROBE_VALID == CRT_PROBE_STATE_VALID, "the rule's states are the header's");
+static_assert(sizeof(crt_ray) == 24 && sizeof(crt_hit) == 48, "a ray is a 16-byte and an 8-byte store");
+
+// rays of one chunk of crt_bake_probes: its scratch is 88 bytes a ray (ray, key, colour, hit)
+constexpr uint64_t PROBE_CHUNK_RAYS = 1ull << 20;
+
+struct crt_probe_state {
+    // crt_bake_probes: one chunk's rays, keys, colours and hits, the records when the caller keeps none on the device, the invalid count
+    DeviceArray<crt_ray> rays;
+    DeviceArray<uint32_t> keys, counts;
+    DeviceArray<float> rgb;
+    DeviceArray<crt_hit> hits;
+    DeviceArray<float4> probes;
+    // crt_probe_irradiance: the volume's records, the points, the normals, the colours, the statuses
+    DeviceArray<float4> look_probes;
+    DeviceArray<float> points, normals, look_rgb;
+    DeviceArray<uint8_t> status;
+    uint32_t *pin = nullptr;
+    hipEvent_t ev[4] = {};
+    crt_probe_stats stats{};
+    ~crt_probe_state() {
+        if (pin) (void)hipHostFree(pin);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+void probes_destroy(crt_ctx *ctx) {
+    delete ctx->probes;
+    ctx->probes = nullptr;
+}
+
+static int probes_state(crt_ctx *ctx) {
+    if (!ctx->probes) ctx->probes = new (std::nothrow) crt_probe_state;
+    if (!ctx->probes) { ctx->error = "out of memory"; return CRT_ERR_NOMEM; }
+    return CRT_OK;
+}
+
+extern "C" void crt_probe_volume_defaults(crt_probe_volume *v) {
+    if (!v) return;
+    for (int k = 0; k < 3; k++) { v->origin[k] = 0.0f; v->spacing[k] = 1.0f; }
+    v->nx = v->ny = v->nz = 1;
+    v->rays = 64;
+    v->gi_seed = 0;
+    v->backface_limit = 1.0f;
+}
+
+static crt_probe_grid grid_of(const crt_probe_volume *v) {
+    crt_probe_grid g;
+    memcpy(&g, v, sizeof(g));
+    return g;
+}
+
+static int volume_check(crt_ctx *ctx, const char *what, const crt_probe_volume *v) {
+    if (!v) return refuse(ctx, what, "volume is NULL");
+    if (!crt_probe_grid_valid(grid_of(v)))
+        return refuse(ctx, what, "the volume is not valid: nx, ny, nz >= 1, 1 <= rays <= 4096, nx * ny * nz < 2^24, finite origin, spacing finite and > 0, "
+                                 "backface_limit finite in [0, 1]");
+    return CRT_OK;
+}
+
+static uint32_t blocks_of(const uint64_t n) { return (uint32_t)((n + BLOCK - 1) / BLOCK); }
+static uint32_t wave_blocks_of(const uint64_t waves) { return (uint32_t)((waves + PROBE_WAVES - 1) / PROBE_WAVES); }
+
+// what the two per-probe primitives ask of (count, rays): count * rays rays in arrays of the caller's
+static int range_check(crt_ctx *ctx, const char *what, const uint64_t count, const uint32_t rays) {
+    if (rays == 0u || rays > CRT_PROBE_MAX_RAYS) return refuse(ctx, what, "rays = " + std::to_string(rays) + " is not in 1 .. 4096");
+    if (count >= CRT_PROBE_MAX_PROBES) return refuse(ctx, what, "count = " + std::to_string(count) + " >= 2^24");
+    return CRT_OK;
+}
+
+extern "C" int crt_probe_rays_device(crt_ctx *ctx, const crt_probe_volume *volume, uint32_t first, uint32_t count, crt_ray *d_rays, uint32_t *d_keys,
+                                     void *stream) {
+    const char *what = "crt_probe_rays_device";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = volume_check(ctx, what, volume)) return rc;
+    const crt_probe_grid g = grid_of(volume);
+    if ((uint64_t)first + count > crt_probe_count(g))
+        return refuse(ctx, what, "first + count = " + std::to_string((uint64_t)first + count) + " > the volume's " + std::to_string(crt_probe_count(g)) + " probes");
+    if (count == 0) return CRT_OK;
+    if (!d_rays) return refuse(ctx, what, "d_rays is NULL");
+    if ((uintptr_t)d_rays % 16u) return refuse(ctx, what, "d_rays must be aligned to 16 bytes");
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(probe_rays, dim3(blocks_of((uint64_t)count * g.rays)), dim3(BLOCK), 0, (hipStream_t)stream, ProbeRaysArgs{g, first, count, d_rays, d_keys});
+    CRT_HIP_CHECK(ctx, hipGetLastError());
+    return CRT_OK;
+}
+
+extern "C" int crt_probe_project_device(crt_ctx *ctx, const crt_ray *d_rays, const float *d_rgb, uint32_t count, uint32_t rays, crt_probe *d_probes,
+                                        void *stream) {
+    const char *what = "crt_probe_project_device";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = range_check(ctx, what, count, rays)) return rc;
+    if (count == 0) return CRT_OK;
+    if (!d_rays || !d_rgb || !d_probes) return refuse(ctx, what, "d_rays, d_rgb or d_probes is NULL");
+    if ((uintptr_t)d_probes % 16u) return refuse(ctx, what, "d_probes must be aligned to 16 bytes");
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(probe_project, dim3(wave_blocks_of(count)), dim3(BLOCK), 0, (hipStream_t)stream, ProbeProjectArgs{d_rays, d_rgb, count, rays, (float4 *)d_probes});
+    CRT_HIP_CHECK(ctx, hipGetLastError());
+    return CRT_OK;
+}
+
+extern "C" int crt_probe_validity_device(crt_ctx *ctx, const crt_ray *d_rays, const crt_hit *d_hits, uint32_t count, uint32_t rays, float backface_limit,
+                                         crt_probe *d_probes, void *stream) {
+    const char *what = "crt_probe_validity_device";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = range_check(ctx, what, count, rays)) return rc;
+    if (!crt_finite(backface_limit) || !(backface_limit >= 0.0f && backface_limit <= 1.0f)) return refuse(ctx, what, "backface_limit is not finite in [0, 1]");
+    if (count == 0) return CRT_OK;
+    if (!d_rays || !d_hits || !d_probes) return refuse(ctx, what, "d_rays, d_hits or d_probes is NULL");
+    if ((uintptr_t)d_probes % 16u) return refuse(ctx, what, "d_probes must be aligned to 16 bytes");
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(probe_validity, dim3(wave_blocks_of(count)), dim3(BLOCK), 0, (hipStream_t)stream,
+                       ProbeValidityArgs{d_rays, d_hits, count, rays, backface_limit, (float4 *)d_probes});
+    CRT_HIP_CHECK(ctx, hipGetLastError());
+    return CRT_OK;
+}
+
+extern "C" int crt_probe_irradiance_device(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe *d_probes, const float *d_points,
+                                           const float *d_normals, uint64_t n, float *d_rgb, uint8_t *d_status, void *stream) {
+    const char *what = "crt_probe_irradiance_device";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = volume_check(ctx, what, volume)) return rc;
+    if (n == 0) return CRT_OK;
+    if (n >= CRT_MAX_PIXELS) return refuse(ctx, what, "n = " + std::to_string(n) + " >= 2^31");
+    if (!d_probes || !d_points || !d_normals || !d_rgb) return refuse(ctx, what, "d_probes, d_points, d_normals or d_rgb is NULL");
+    if ((uintptr_t)d_probes % 16u) return refuse(ctx, what, "d_probes must be aligned to 16 bytes");
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(probe_lookup, dim3(blocks_of(n)), dim3(BLOCK), 0, (hipStream_t)stream,
+                       ProbeLookupArgs{grid_of(volume), (const float4 *)d_probes, d_points, d_normals, n, d_rgb, d_status});
+    CRT_HIP_CHECK(ctx, hipGetLastError());
+    return CRT_OK;
+}
+
+extern "C" int crt_bake_probes(crt_ctx *ctx, const crt_probe_volume *volume, const crt_options *options, crt_probe *out_probes, crt_probe *d_probes) {
+    const char *what = "crt_bake_probes";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = volume_check(ctx, what, volume)) return rc;
+    if (!options) return refuse(ctx, what, "options is NULL");
+    if (d_probes && (uintptr_t)d_probes % 16u) return refuse(ctx, what, "d_probes must be aligned to 16 bytes");
+    // what the radiance call behind it would refuse, asked before anything is enqueued
+    if (int rc = query_shoot_check(ctx, what, options)) return rc;
+    if (ctx->pending)
+        if (int rc = crt_wait(ctx)) return rc;
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (int rc = probes_state(ctx)) return rc;
+    crt_probe_state *B = ctx->probes;
+    hipStream_t stream = ctx->stream;
+    const crt_probe_grid g = grid_of(volume);
+    const uint32_t total = crt_probe_count(g), R = g.rays;
+    const bool gi = options->use_gi != 0, validity = g.backface_limit != 1.0f;
+    const uint32_t chunk = ctx->probe_chunk ? ctx->probe_chunk : (uint32_t)std::max<uint64_t>(PROBE_CHUNK_RAYS / R, 1u);
+    const uint64_t chunk_rays = (uint64_t)std::min(chunk, total) * R;
+    if (int rc = reserve_all(ctx, B->rays, chunk_rays, B->rgb, 3 * chunk_rays, B->counts, (uint64_t)1)) return rc;
+    if (gi)
+        if (int rc = B->keys.reserve(ctx, chunk_rays)) return rc;
+    if (validity)
+        if (int rc = B->hits.reserve(ctx, chunk_rays)) return rc;
+    if (!d_probes)
+        if (int rc = B->probes.reserve(ctx, 8 * (uint64_t)total)) return rc;
+    crt_probe *records = d_probes ? d_probes : (crt_probe *)B->probes.p;
+    if (!B->pin) CRT_HIP_CHECK(ctx, hipHostMalloc((void **)&B->pin, sizeof(uint32_t)));
+    for (hipEvent_t &e : B->ev)
+        if (!e) CRT_HIP_CHECK(ctx, hipEventCreate(&e));
+
+    double shoot_ms = 0, project_ms = 0, total_ms = 0;
+    for (uint32_t first = 0; first < total; first += chunk) {
+        const uint32_t count = std::min(chunk, total - first);
+        const uint64_t n = (uint64_t)count * R;
+        CRT_HIP_CHECK(ctx, hipEventRecord(B->ev[0], stream));
+        if (int rc = crt_probe_rays_device(ctx, volume, first, count, B->rays.p, gi ? B->keys.p : nullptr, stream)) return rc;
+        CRT_HIP_CHECK(ctx, hipEventRecord(B->ev[1], stream));
+        if (int rc = gi ? crt_shoot_rays_gi_device(ctx, B->rays.p, B->keys.p, n, CRT_RAY_REFLECTION, options, B->rgb.p, stream)
+                        : crt_shoot_rays_device(ctx, B->rays.p, n, CRT_RAY_REFLECTION, options, B->rgb.p, stream))
+            return rc;
+        CRT_HIP_CHECK(ctx, hipEventRecord(B->ev[2], stream));
+        if (int rc = crt_probe_project_device(ctx, B->rays.p, B->rgb.p, count, R, records + first, stream)) return rc;
+        if (validity) {
+            if (int rc = crt_trace_rays_device(ctx, B->rays.p, n, CRT_RAY_REFLECTION, B->hits.p, stream)) return rc;
+            if (int rc = crt_probe_validity_device(ctx, B->rays.p, B->hits.p, count, R, g.backface_limit, records + first, stream)) return rc;
+        }
+        CRT_HIP_CHECK(ctx, hipEventRecord(B->ev[3], stream));
+        CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));   // the next chunk writes the same scratch, and the events are read
+        float ms = 0;
+        CRT_HIP_CHECK(ctx, hipEventElapsedTime(&ms, B->ev[1], B->ev[2]));
+        shoot_ms += ms;
+        CRT_HIP_CHECK(ctx, hipEventElapsedTime(&ms, B->ev[2], B->ev[3]));
+        project_ms += ms;
+        CRT_HIP_CHECK(ctx, hipEventElapsedTime(&ms, B->ev[0], B->ev[3]));
+        total_ms += ms;
+    }
+    CRT_HIP_CHECK(ctx, hipMemsetAsync(B->counts.p, 0, sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(probe_count_invalid, dim3(blocks_of(total)), dim3(BLOCK), 0, stream, (const float4 *)records, (uint64_t)total, B->counts.p);
+    CRT_HIP_CHECK(ctx, hipGetLastError());
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(B->pin, B->counts.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (out_probes) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_probes, records, (size_t)total * sizeof(crt_probe), hipMemcpyDeviceToHost, stream));
+    CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));
+
+    crt_probe_stats &st = B->stats;
+    st = crt_probe_stats{};
+    st.probes = total;
+    st.invalid = B->pin[0];
+    st.rays = (uint64_t)total * R;
+    st.shoot_ms = shoot_ms;
+    st.project_ms = project_ms;
+    st.total_ms = total_ms;
+    return CRT_OK;
+}
+
+extern "C" int crt_probe_irradiance(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe *probes, const float *points, const float *normals,
+                                    uint64_t n, float *out_rgb, uint8_t *out_status) {
+    const char *what = "crt_probe_irradiance";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = volume_check(ctx, what, volume)) return rc;
+    if (n == 0) return CRT_OK;
+    if (n >= CRT_MAX_PIXELS) return refuse(ctx, what, "n = " + std::to_string(n) + " >= 2^31");
+    if (!probes || !points || !normals || !out_rgb) return refuse(ctx, what, "probes, points, normals or out_rgb is NULL");
+    if (ctx->pending)
+        if (int rc = crt_wait(ctx)) return rc;
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (int rc = probes_state(ctx)) return rc;
+    crt_probe_state *B = ctx->probes;
+    hipStream_t stream = ctx->stream;
+    const uint64_t total = crt_probe_count(grid_of(volume));
+    if (int rc = reserve_all(ctx, B->look_probes, 8 * total, B->points, 3 * n, B->normals, 3 * n, B->look_rgb, 3 * n, B->status, n)) return rc;
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(B->look_probes.p, probes, (size_t)total * sizeof(crt_probe), hipMemcpyHostToDevice, stream));
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(B->points.p, points, (size_t)n * 12, hipMemcpyHostToDevice, stream));
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(B->normals.p, normals, (size_t)n * 12, hipMemcpyHostToDevice, stream));
+    if (int rc = crt_probe_irradiance_device(ctx, volume, (const crt_probe *)B->look_probes.p, B->points.p, B->normals.p, n, B->look_rgb.p, B->status.p, stream))
+        return rc;
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, B->look_rgb.p, (size_t)n * 12, hipMemcpyDeviceToHost, stream));
+    if (out_status) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_status, B->status.p, (size_t)n, hipMemcpyDeviceToHost, stream));
+    CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));
+    return CRT_OK;
+}
+
+extern "C" int crt_get_probe_stats(crt_ctx *ctx, crt_probe_stats *out) {
+    if (!ctx || !out) return CRT_ERR_INVALID;
+    *out = ctx->probes ? ctx->probes->stats : crt_probe_stats{};
+    return CRT_OK;
+}

@@ -578,6 +578,7 @@ extern "C" void crt_destroy(crt_ctx *ctx) {
     query_destroy(ctx);
     giframe_destroy(ctx);
     bake_destroy(ctx);
+    probes_destroy(ctx);
     if (ctx->d_frame) (void)hipFree(ctx->d_frame);
     if (ctx->d_quant) (void)hipFree(ctx->d_quant);
     if (ctx->d_items) (void)hipFree(ctx->d_items);

@@ -120,6 +120,13 @@ extern "C" int crt_debug_set_query_chunks(crt_ctx *ctx, uint64_t host_rays, uint
     return CRT_OK;
 }
 
+// Unit-test hook: crt_bake_probes takes `probes` probes per chunk from now on (0: as many as fit its scratch again)
+extern "C" int crt_debug_set_probe_chunk(crt_ctx *ctx, uint32_t probes) {
+    if (!ctx) return CRT_ERR_INVALID;
+    ctx->probe_chunk = std::min<uint32_t>(probes, 1u << 24);
+    return CRT_OK;
+}
+
 // Unit-test hook: level 0's fixed shadow slots (csrc/shadow_place.h) -- every slot of items x samples work items and n_lights lights through the
 // inverse placement and back through the forward one, on the host; *mismatches = the slots that do not come back.
 extern "C" int crt_test_shadow_place(uint32_t items, uint32_t samples, uint32_t n_lights, uint64_t *mismatches) {

@@ -327,6 +327,67 @@ std::vector<float> RayTracer::bakeLightmap(const std::string &pathToImage, const
   return rgb;
 }
 
+std::vector<crt_probe> RayTracer::bakeProbes(const crt_probe_volume &volume, const RenderOptions &ro, crt_probe_stats *stats) {
+  if (multi) throw std::runtime_error("bakeProbes: not available on a multi-device tracer");
+  std::vector<crt_probe> probes((size_t)volume.nx * volume.ny * volume.nz);
+  crt_options options{};
+  options.max_depth = ro.MAX_DEPTH;
+  options.shadow_bias = ro.SHADOW_BIAS;
+  options.reflection_bias = ro.REFLECTION_BIAS;
+  options.refraction_bias = ro.REFRACTION_BIAS;
+  options.use_gi = ro.USE_GI ? 1u : 0u;
+  options.gi_sample_size = ro.GI_SAMPLE_SIZE;
+  options.monte_carlo_bias = ro.MONTE_CARLO_BIAS;
+  options.gi_seed = giSeed;
+  if (crt_bake_probes(ctx, &volume, &options, probes.empty() ? nullptr : probes.data(), nullptr) != CRT_OK)
+    throw std::runtime_error(std::string("bakeProbes failed: ") + crt_last_error(ctx));
+  if (stats && crt_get_probe_stats(ctx, stats) != CRT_OK) throw std::runtime_error(std::string("bakeProbes failed: ") + crt_last_error(ctx));
+  return probes;
+}
+
+std::vector<float> RayTracer::probeIrradiance(const crt_probe_volume &volume, const std::vector<crt_probe> &probes, const std::vector<float> &points,
+                                              const std::vector<float> &normals, std::vector<unsigned char> *status) {
+  if (multi) throw std::runtime_error("probeIrradiance: not available on a multi-device tracer");
+  if (points.size() % 3 || normals.size() != points.size()) throw std::runtime_error("probeIrradiance: three floats per point, one normal per point");
+  if (probes.size() != (size_t)volume.nx * volume.ny * volume.nz) throw std::runtime_error("probeIrradiance: one record per probe of the volume");
+  const size_t n = points.size() / 3;
+  std::vector<float> rgb(points.size());
+  if (status) status->assign(n, 0);
+  if (crt_probe_irradiance(ctx, &volume, probes.data(), points.data(), normals.data(), n, rgb.data(), status && n ? status->data() : nullptr) != CRT_OK)
+    throw std::runtime_error(std::string("probeIrradiance failed: ") + crt_last_error(ctx));
+  return rgb;
+}
+
+std::vector<float> RayTracer::probeIrradianceView(const std::string &pathToImage, const crt_probe_volume &volume, const std::vector<crt_probe> &probes) {
+  const unsigned int W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
+  const size_t n = (size_t)W * H;
+  const std::vector<crt_hit> hits = traceRays(cameraRays(), CRT_RAY_PRIMARY);
+  std::vector<float> points(3 * n), normals(3 * n);
+  for (size_t i = 0; i < n; i++)
+    for (int k = 0; k < 3; k++) { points[3 * i + k] = hits[i].point[k]; normals[3 * i + k] = hits[i].normal[k]; }
+  std::vector<unsigned char> status;
+  std::vector<float> rgb = probeIrradiance(volume, probes, points, normals, &status);
+  const Color &bg = scene.sceneSettings.sceneBackgroundColor;
+  for (size_t i = 0; i < n; i++)
+    if (!hits[i].hit || !status[i]) { rgb[3 * i] = bg.x; rgb[3 * i + 1] = bg.y; rgb[3 * i + 2] = bg.z; }
+  if (!pathToImage.empty()) {
+    // page-locked host memory is the device's to read and write: the quantisation is crt_quantize_device's
+    float *in = static_cast<float *>(crt_alloc_pinned((n ? n : 1) * 3 * sizeof(float)));
+    uint8_t *q = static_cast<uint8_t *>(crt_alloc_pinned((n ? n : 1) * 3));
+    int rc = in && q ? CRT_OK : CRT_ERR_NOMEM;
+    if (rc == CRT_OK) {
+      std::copy(rgb.begin(), rgb.end(), in);
+      rc = crt_quantize_device(ctx, in, 3 * n, q, nullptr);
+    }
+    if (rc == CRT_OK) rc = crt_synchronize(ctx);
+    if (rc == CRT_OK) writePPMQuantized(pathToImage, q, W, H);
+    if (in) crt_free_pinned(in);
+    if (q) crt_free_pinned(q);
+    if (rc != CRT_OK) throw std::runtime_error(std::string("probeIrradianceView failed: ") + (rc == CRT_ERR_NOMEM ? "out of pinned host memory" : crt_last_error(ctx)));
+  }
+  return rgb;
+}
+
 crt_query_stats RayTracer::queryStats() const {
   crt_query_stats s{};
   if (!multi) crt_get_query_stats(ctx, &s);

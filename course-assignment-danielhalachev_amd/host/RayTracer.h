@@ -125,6 +125,18 @@ class RayTracer {
   std::vector<float> bakeLightmap(const std::string &pathToImage, const crt_bake &bake, const RenderOptions &renderOptions,
                                   std::vector<unsigned char> *status = nullptr, crt_bake_stats *stats = nullptr);
 
+  // ---- irradiance probes (crt_hip.h: "Irradiance probes", crt_bake_probes, crt_probe_irradiance): bakeProbes gives the volume's nx * ny * nz
+  // SH9 records, each the projection of what shootRay returns for the probe's rays -- MAX_DEPTH and the biases from renderOptions; with USE_GI
+  // the GI mode of GI_SAMPLE_SIZE rays per hit under the VOLUME's gi_seed --, *stats the call's crt_probe_stats.  probeIrradiance gives the
+  // light a white Lambertian surface shows at the points (3 floats each) with the normals, 3 floats per point, *status the corners used
+  // (0: no light).  probeIrradianceView is the volume seen by the camera: every pixel's camera ray is traced, a hit is looked up at its point
+  // with its normal, a miss or a lookup without light is the background; pathToImage: the view as a PPM when it is not empty.
+  // Single-device tracers only.
+  std::vector<crt_probe> bakeProbes(const crt_probe_volume &volume, const RenderOptions &renderOptions, crt_probe_stats *stats = nullptr);
+  std::vector<float> probeIrradiance(const crt_probe_volume &volume, const std::vector<crt_probe> &probes, const std::vector<float> &points,
+                                     const std::vector<float> &normals, std::vector<unsigned char> *status = nullptr);
+  std::vector<float> probeIrradianceView(const std::string &pathToImage, const crt_probe_volume &volume, const std::vector<crt_probe> &probes);
+
   // ---- chain guides (crt_hip.h: "Chain guides", crt_guide_rays): for every ray the guide record of the surface it shows -- the chain of
   // closest hits through reflective and refractive meshes to the first diffuse or constant surface, a miss or maxBounces (<= 63) --, with
   // the path length as t and a tagged mesh; the biases come from renderOptions.  *status: a byte a ray (bits 0-5 the bounces, bit 7 cut),

@@ -1146,6 +1146,113 @@ int crt_bake_lightmap(crt_ctx *ctx, const crt_bake *bake, const crt_options *opt
                       crt_bake_texel *out_texels);
 int crt_get_bake_stats(crt_ctx *ctx, crt_bake_stats *out);
 
+/* ---- Irradiance probes: a volume of SH9 probes made from the radiance queries, sampled at points -- light for what has no lightmap texel:
+ * a moving object, a particle, a vertex of a mesh without UVs, a point in the air.  The library says which rays a probe shoots, projects the
+ * colours crt_shoot_rays_device or, with crt_options::use_gi, crt_shoot_rays_gi_device returns for them onto nine spherical-harmonic
+ * coefficients per channel, optionally marks the probes that stand inside geometry, and interpolates a volume of such records at arbitrary
+ * points with normals.  Kernels: csrc/kernel_probes.h; the rule, one header for host and device: csrc/probe_rule.h.  It is additive: no
+ * frame, walk, query, radiance, GI-frame or lightmap kernel is involved or changed.  Single-device contexts only (a crt_multi has none of
+ * these calls).
+ *
+ * The rule (csrc/probe_rule.h, verbatim; tests/probe_sets.py restates it in numpy and the GPU gives its bits):
+ * Volume.  crt_probe_volume { float origin[3], spacing[3]; uint32_t nx, ny, nz, rays; uint32_t gi_seed; float backface_limit; }.
+ *   Probe p = (iz * ny + iy) * nx + ix stands at position.k = origin.k + (float)i_k * spacing.k (the product is rounded, then the sum).
+ *   Valid volumes have nx, ny, nz >= 1, 1 <= rays <= 4096, nx * ny * nz < 2^24, finite origin, spacing finite and > 0, and backface_limit
+ *   finite in [0, 1].
+ * Directions.  Ray j of R = rays is a spherical Fibonacci point, the same set for every probe:
+ *     z = 1.0f - (float)(2j + 1) / (float)R
+ *     r = sqrtf(max(0, 1.0f - z * z))                   (m = 1.0f - z * z; m > 0 ? m : 0)
+ *     t = (float)j * 0.618034f, then t = t - (float)(int32_t)t
+ *     phi = t * 6.2831855f
+ *     d = (r * crt_cosf(phi), r * crt_sinf(phi), z)      (phi lies in [0, 2 pi], inside the |y| < 120 range of csrc/glibc_sincosf.h)
+ *   The ray is {probe position, d}, shot as CRT_RAY_REFLECTION (back faces are not culled).  Its GI key is
+ *   crt_gi_mix(crt_gi_mix(gi_seed, p), j).
+ * Basis.  Nine real SH functions of a direction (x, y, z), in the fixed order 1, y, z, x, xy, yz, 3z^2 - 1, xz, x^2 - y^2:
+ *     Y0 = 0.282095f
+ *     Y1 = 0.488603f * y; Y2 = 0.488603f * z; Y3 = 0.488603f * x
+ *     Y4 = 1.092548f * (x * y); Y5 = 1.092548f * (y * z); Y7 = 1.092548f * (x * z)
+ *     Y6 = 0.315392f * (3.0f * (z * z) - 1.0f)
+ *     Y8 = 0.546274f * (x * x - y * y)
+ * Projection.  For probe p, coefficient c, channel ch, with L the colour shootRay returned for ray (p, j) and d_j the direction READ FROM
+ *   THE RAY ARRAY as given (so the projection also serves a caller's own uniform direction set):
+ *     lane partial: part[l], l = 0..63, is the left fold, starting from 0.0f, over j = l, l + 64, ... in increasing order of
+ *         L[p][j][ch] * Y_c(d_j)
+ *     tree: for step = 32, 16, 8, 4, 2, 1: part[l] = part[l] + part[l + step] for l < step
+ *     coef[c][ch] = part[0] * (12.566371f / (float)R)
+ *   That is what a wave of 64 lanes does with cross-lane moves; numpy restates it with a reshape.
+ * Validity.  Optional, and off when backface_limit == 1.0f.  The same rays go through crt_trace_rays_device; back counts the hits with
+ *   (n.x * d.x + n.y * d.y) + n.z * d.z > 0.0f (n the hit's normal), miss the rays without a hit.  The probe is INVALID when
+ *   (float)back > backface_limit * (float)R, otherwise VALID.  The counts are integers (ballot and popcount): no order dependence.
+ * Record.  crt_probe is 128 bytes, one cache line: 27 floats coef[c][ch], then uint32 rays, back, miss, state, and one pad word written
+ *   as 0.  state: CRT_PROBE_INVALID = 0, CRT_PROBE_VALID = 1; the lookup takes every other value as INVALID.  The projection writes
+ *   back = 0, miss = 0, state = VALID; the validity pass writes back, miss and state over them.
+ * Lookup.  For a point x with normal n, used as given and not normalised:
+ *     if any coordinate of x or n is not finite ((v - v) == 0.0f fails): status 0, colour 0; decided before any conversion to an integer
+ *     per axis k: g = (x.k - origin.k) / spacing.k, clamped as a float: g < 0 ? 0 : (g > (float)(n_k - 1) ? (float)(n_k - 1) : g)
+ *         i0 = (int32_t)g, lowered to n_k - 2 when n_k > 1 and i0 > n_k - 2; f = g - (float)i0
+ *         the two corners i0 and i0 + 1 have the weights 1.0f - f and f; with n_k == 1 only i0 = 0 with weight 1.0f exists
+ *     corners run in the order dz, dy, dx (dx fastest), with weight w = (wx * wy) * wz
+ *     an INVALID corner and a corner of weight 0 are skipped; every corner index is compared with nx * ny * nz as an integer before an
+ *         address is formed
+ *     W = the left fold of the used weights, S[c][ch] = the left fold of w * coef[c][ch], both starting from 0.0f
+ *     no corner used: status 0, colour 0
+ *     e[ch] = the left fold over c = 0..8, starting from 0.0f, of (A_c * Y_c(n)) * S[c][ch], A = 1.0f, 0.6666667f (x3), 0.25f (x5)
+ *     q = e[ch] / W; out[ch] = q > 0.0f ? q : 0.0f          (a NaN gives 0)
+ *     status = the number of corners used (1 to 8)
+ *   A_c is the clamped-cosine convolution divided by pi: the result is the colour a white Lambertian surface would show.
+ *
+ * Known limits.
+ *   * Every probe uses the same direction set: there is no per-probe rotation, and re-baked volumes are not blended over time.
+ *   * There is no visibility (Chebyshev) term, so light leaks through thin walls.
+ *   * SH9 rings under hard directional light.
+ *   * The volume is not fed into the frame kernels: a frame does not read it.
+ *   * Single-device contexts only.
+ * crt_probe_volume_defaults: origin 0, spacing 1, 1 x 1 x 1 probes, 64 rays, gi_seed 0, backface_limit 1.0f (validity off).  A volume that is
+ *   not valid is CRT_ERR_INVALID in every call below, with nothing enqueued and nothing changed.
+ * The four primitives only ENQUEUE kernels on `stream` (a hipStream_t, NULL = default): no wait, no allocation, no readback, no memset or
+ *   copy node, so they can be captured and a captured chain replays in order.  count == 0 or n == 0 is CRT_OK and touches nothing; a NULL
+ *   array with work to do is CRT_ERR_INVALID.  d_rays of crt_probe_rays_device and every d_probes must be aligned to 16 bytes.
+ * crt_probe_rays_device: the rays of the probes [first, first + count) of the volume, rays * count of them, probe by probe, to d_rays, and
+ *   their GI keys to d_keys, which may be NULL: then nothing is written for keys.  first + count > nx * ny * nz is CRT_ERR_INVALID.
+ * crt_probe_project_device: the records of `count` probes of `rays` rays each (1 .. 4096; count < 2^24) from the rays d_rays and their
+ *   colours d_rgb (3 floats a ray) to d_probes; the direction is read from d_rays as given.  It writes all 128 bytes of a record: the
+ *   coefficients, rays, back = 0, miss = 0, state = CRT_PROBE_VALID, pad = 0.  Two runs give the same bytes.
+ * crt_probe_validity_device: back, miss and state of `count` records from the rays and the crt_hit records crt_trace_rays_device wrote for
+ *   them; the coefficients and `rays` are left as they are.  backface_limit must be finite in [0, 1].
+ * crt_probe_irradiance_device: the lookup at n points (d_points, d_normals: 3 floats each; n < 2^31) in the volume's records d_probes
+ *   (nx * ny * nz of them) to d_rgb (3 floats a point) and d_status (a byte a point, the corners used; may be NULL).
+ * crt_bake_probes is the frame-level call, synchronous; out_probes (host) and d_probes (device, aligned to 16), nx * ny * nz records each,
+ *   may each be NULL.  For chunks of probes whose rays fit one bounded scratch area (2^20 rays; at least one probe) it calls
+ *   crt_probe_rays_device, then crt_shoot_rays_device -- or, with options->use_gi, crt_shoot_rays_gi_device under the rule's keys; the
+ *   volume's gi_seed makes the keys, options->gi_seed is not read --, then crt_probe_project_device, and when backface_limit != 1.0f
+ *   crt_trace_rays_device and crt_probe_validity_device.  It calls those entry points as any caller does and waits once a chunk.  Like the
+ *   queries it leaves the persistent colour buffer, crt_stats, the ray queues' sizing, the progressive and adaptive frame, the history and
+ *   the lightmap bake's state exactly as they were, and it waits for a pending crt_render_async frame.  CRT_ERR_INVALID, with nothing
+ *   enqueued: an invalid volume, NULL options, and whatever the underlying radiance call refuses (max_depth + 1 > 64, gi_sample_size > 64,
+ *   levels that cannot be held).  Its arrays are the context's own: they grow and are kept.
+ * crt_probe_irradiance: the host variant of the lookup: probes, points, normals, out_rgb and out_status (may be NULL) are host memory; it
+ *   copies in, runs crt_probe_irradiance_device, copies out and returns when the result is there.
+ * crt_get_probe_stats: the last crt_bake_probes call: probes, the probes whose state is not VALID, rays = probes * rays, and HIP-event
+ *   times summed over the chunks: shoot_ms the radiance calls, project_ms the projection with the trace and the validity pass, total_ms
+ *   the chunks' whole device work. */
+typedef struct crt_probe_volume { float origin[3], spacing[3]; uint32_t nx, ny, nz, rays; uint32_t gi_seed; float backface_limit; } crt_probe_volume;   /* 48 bytes */
+void crt_probe_volume_defaults(crt_probe_volume *v);   /* origin 0, spacing 1, 1 x 1 x 1, 64 rays, gi_seed 0, backface_limit 1.0f */
+typedef struct crt_probe { float coef[9][3]; uint32_t rays, back, miss, state, pad; } crt_probe;   /* 128 bytes */
+enum { CRT_PROBE_INVALID = 0, CRT_PROBE_VALID = 1 };
+typedef struct crt_probe_stats { uint64_t probes, invalid, rays; double shoot_ms, project_ms, total_ms; } crt_probe_stats;
+int crt_probe_rays_device(crt_ctx *ctx, const crt_probe_volume *volume, uint32_t first, uint32_t count, crt_ray *d_rays, uint32_t *d_keys /* may be NULL */,
+                          void *stream);
+int crt_probe_project_device(crt_ctx *ctx, const crt_ray *d_rays, const float *d_rgb, uint32_t count, uint32_t rays, crt_probe *d_probes, void *stream);
+int crt_probe_validity_device(crt_ctx *ctx, const crt_ray *d_rays, const crt_hit *d_hits, uint32_t count, uint32_t rays, float backface_limit,
+                              crt_probe *d_probes, void *stream);
+int crt_probe_irradiance_device(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe *d_probes, const float *d_points, const float *d_normals,
+                                uint64_t n, float *d_rgb, uint8_t *d_status, void *stream);
+int crt_bake_probes(crt_ctx *ctx, const crt_probe_volume *volume, const crt_options *options, crt_probe *out_probes /* host, may be NULL */,
+                    crt_probe *d_probes /* device, may be NULL */);
+int crt_probe_irradiance(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe *probes, const float *points, const float *normals, uint64_t n,
+                         float *out_rgb, uint8_t *out_status);
+int crt_get_probe_stats(crt_ctx *ctx, crt_probe_stats *out);
+
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
  * stream per listed device (a device may be listed more than once); the covered 8x8 tiles are dealt round-robin, every
@@ -1198,7 +1305,7 @@ int crt_get_executed_plan_tests(crt_ctx *ctx, uint64_t out[2]);
 
 /* ---- Test hooks: exported by libcrt_hip_test.so only (the product's objects + csrc/crt_testhooks.hip; libcrt_hip.so has none of them):
  * crt_test_pow5, crt_test_gi, crt_bvh_selftest, crt_bvh_census, crt_debug_set_filter_stack, crt_debug_set_query_chunks,
- * crt_debug_multi_force_staged, crt_debug_multi_fail_next_alloc. ---- */
+ * crt_debug_multi_force_staged, crt_debug_multi_fail_next_alloc, crt_debug_set_probe_chunk. ---- */
 /* Test hook: out[i] = the device build of the restated glibc powf(x[i], 5) (the Fresnel term, RayTracer.cpp:407). */
 int crt_test_pow5(int device, const float *x, float *out, uint64_t n);
 /* Test hook for the GI mode's arithmetic (csrc/glibc_sincosf.h, csrc/gi_random.h), evaluated on `device`, or by the host
@@ -1224,6 +1331,9 @@ int crt_debug_set_filter_stack(crt_ctx *ctx, uint32_t entries);
  * round trip of the host variants (2^22), per launch (2^27), per pass of a radiance query (2^22).  0 restores the default; any other
  * value is clamped to [64, the default].  Waits for the context's work; changes no answer and no statistic but kernel_ms. */
 int crt_debug_set_query_chunks(crt_ctx *ctx, uint64_t host_rays, uint64_t launch_rays, uint64_t pass_rays);
+/* Test hook: crt_bake_probes of a live context takes `probes` probes per chunk from now on, so that a few probes run its chunk loop; 0
+ * restores the default (as many as fit its scratch).  Changes no record. */
+int crt_debug_set_probe_chunk(crt_ctx *ctx, uint32_t probes);
 
 /* Diagnostics for the development tools under tools/ (no counterpart in the reference; not needed to render):
  * the ray-stream pass's queue counters of the last frame (rays per recursion level, walks handed to the
