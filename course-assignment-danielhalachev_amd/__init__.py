@@ -241,6 +241,28 @@ PROBE_DTYPE = np.dtype([("coef", np.float32, (9, 3)), ("rays", np.uint32), ("bac
 PROBE_INVALID, PROBE_VALID = range(2)
 
 
+class ProbeVisibility(C.Structure):
+    """crt_probe_visibility, 20 bytes: the parameters of the Chebyshev-weighted lookup (make_probe_visibility fills it from a volume)"""
+    _fields_ = [("size", C.c_uint32), ("max_distance", C.c_float), ("normal_bias", C.c_float), ("variance_floor", C.c_float), ("min_weight", C.c_float)]
+
+
+def make_probe_visibility(volume, **fields):
+    """crt_probe_visibility_defaults of the volume (max_distance 1.5 x the cell diagonal, normal_bias 0.02 x the smallest spacing,
+    variance_floor 1e-6 x max_distance^2, min_weight 0.01) with the given fields replaced."""
+    p = ProbeVisibility()
+    if lib().crt_probe_visibility_defaults(C.byref(volume), C.byref(p)) != CRT_OK:
+        raise ValueError("make_probe_visibility: the volume is not valid")
+    for k, val in fields.items():
+        if k not in dict(ProbeVisibility._fields_):
+            raise KeyError("crt_probe_visibility has no field %r" % (k,))
+        setattr(p, k, val)
+    return p
+
+
+# crt_probe_depth as a numpy record (512 bytes: (mean, mean2) of the 64 texels of a probe's 8 x 8 octahedral map)
+PROBE_DEPTH_DTYPE = np.dtype([("moments", np.float32, (64, 2))])
+
+
 def make_pose(position, matrix):
     """a crt_camera_pose of 3 and 9 floats"""
     pose = CameraPose()
@@ -309,6 +331,8 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_st
                   "crt_bake_defaults", "crt_bake_work_bytes", "crt_bake_texels_device", "crt_bake_dilate_device", "crt_bake_lightmap", "crt_get_bake_stats",
                   "crt_probe_volume_defaults", "crt_probe_rays_device", "crt_probe_project_device", "crt_probe_validity_device", "crt_probe_irradiance_device",
                   "crt_bake_probes", "crt_probe_irradiance", "crt_get_probe_stats", "crt_debug_set_probe_chunk",
+                  "crt_probe_visibility_defaults", "crt_probe_depth_device", "crt_probe_irradiance_visible_device", "crt_probe_irradiance_visible",
+                  "crt_bake_probes_visible",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -440,6 +464,11 @@ def lib():
     L.crt_bake_probes.argtypes = [vp, C.POINTER(ProbeVolume), C.POINTER(Options), vp, vp]
     L.crt_probe_irradiance.argtypes = [vp, C.POINTER(ProbeVolume), vp, vp, vp, C.c_uint64, vp, vp]
     L.crt_get_probe_stats.argtypes = [vp, C.POINTER(ProbeStats)]
+    L.crt_probe_visibility_defaults.argtypes = [C.POINTER(ProbeVolume), C.POINTER(ProbeVisibility)]
+    L.crt_probe_depth_device.argtypes = [vp, vp, vp, u32, u32, C.c_float, vp, vp]
+    L.crt_probe_irradiance_visible_device.argtypes = [vp, C.POINTER(ProbeVolume), C.POINTER(ProbeVisibility), vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
+    L.crt_probe_irradiance_visible.argtypes = [vp, C.POINTER(ProbeVolume), C.POINTER(ProbeVisibility), vp, vp, vp, vp, C.c_uint64, vp, vp]
+    L.crt_bake_probes_visible.argtypes = [vp, C.POINTER(ProbeVolume), C.POINTER(ProbeVisibility), C.POINTER(Options), vp, vp, vp, vp]
     L.crt_host_shoot_stats_layout.argtypes = [C.POINTER(u32), u32]
     L.crt_host_shoot_stats_layout.restype = u32
     L.crt_get_kernel_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -1225,6 +1254,57 @@ class Tracer:
         rgb = np.zeros((len(points), 3), dtype=np.float32)
         status = np.zeros(len(points), dtype=np.uint8)
         self._check(lib().crt_probe_irradiance(self.ctx, C.byref(volume), _p(probes), _p(points), _p(normals), len(points), _p(rgb), _p(status)))
+        return rgb, status
+
+    # ---- probe visibility (include/crt_hip.h: "Probe visibility")
+    def probe_depth_device(self, d_rays_ptr, d_hits_ptr, count, rays, max_distance, d_depth_ptr, stream_ptr=None):
+        """The depth records of `count` probes of `rays` rays each from rays float32 [count * rays, 6] and the hits uint8 [count * rays, 48]
+        trace_rays_device wrote for them -> depth uint8 [count, 512] (PROBE_DEPTH_DTYPE, aligned to 16 bytes).  Enqueues and returns."""
+        self._single("probe_depth_device")
+        self._check(lib().crt_probe_depth_device(self.ctx, C.c_void_p(d_rays_ptr), C.c_void_p(d_hits_ptr), int(count), int(rays), float(max_distance),
+                                                 C.c_void_p(d_depth_ptr), C.c_void_p(stream_ptr or 0)))
+
+    def probe_irradiance_visible_device(self, volume, visibility, d_probes_ptr, d_depth_ptr, d_points_ptr, d_normals_ptr, n, d_rgb_ptr, d_status_ptr=None,
+                                        stream_ptr=None):
+        """probe_irradiance_device with every corner weighted by the Chebyshev bound of its depth record (visibility: make_probe_visibility).
+        Enqueues and returns."""
+        self._single("probe_irradiance_visible_device")
+        self._check(lib().crt_probe_irradiance_visible_device(self.ctx, C.byref(volume), C.byref(visibility), C.c_void_p(d_probes_ptr), C.c_void_p(d_depth_ptr),
+                                                              C.c_void_p(d_points_ptr), C.c_void_p(d_normals_ptr), int(n), C.c_void_p(d_rgb_ptr),
+                                                              C.c_void_p(d_status_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def bake_probes_visible(self, volume, visibility=None, options=None, d_probes_ptr=None, d_depth_ptr=None):
+        """bake_probes with the depth pass -> (PROBE_DTYPE [nz, ny, nx], PROBE_DEPTH_DTYPE [nz, ny, nx]); visibility: make_probe_visibility
+        (None: the volume's defaults); d_probes_ptr, d_depth_ptr: device memory that takes the records too.  probe_stats() describes the call."""
+        self._single("bake_probes_visible")
+        o = options if options is not None else make_options()
+        vis = visibility if visibility is not None else make_probe_visibility(volume)
+        shape = (max(int(volume.nz), 0), max(int(volume.ny), 0), max(int(volume.nx), 0))
+        out, depth = np.zeros(shape, dtype=PROBE_DTYPE), np.zeros(shape, dtype=PROBE_DEPTH_DTYPE)
+        self._check(lib().crt_bake_probes_visible(self.ctx, C.byref(volume), C.byref(vis), C.byref(o), _p(out) if out.size else None,
+                                                  C.c_void_p(d_probes_ptr or 0), _p(depth) if depth.size else None, C.c_void_p(d_depth_ptr or 0)))
+        return out, depth
+
+    def probe_irradiance_visible(self, volume, visibility, probes, depth, points, normals):
+        """probe_irradiance with the visibility term: `depth` are the volume's depth records as bake_probes_visible returns them
+        -> (rgb float32 [n, 3], status uint8 [n])."""
+        self._single("probe_irradiance_visible")
+        probes = np.ascontiguousarray(probes, dtype=PROBE_DTYPE).reshape(-1)
+        depth = np.asarray(depth)
+        if depth.dtype != PROBE_DEPTH_DTYPE:                               # the moments themselves, float32 [..., 64, 2]
+            depth = np.ascontiguousarray(depth, dtype=np.float32).reshape(-1, 128).view(PROBE_DEPTH_DTYPE)
+        depth = np.ascontiguousarray(depth).reshape(-1)
+        points = np.ascontiguousarray(points, dtype=np.float32)
+        normals = np.ascontiguousarray(normals, dtype=np.float32)
+        if points.ndim != 2 or points.shape[1] != 3 or normals.shape != points.shape:
+            raise ValueError("points, normals: expected two arrays of shape [n, 3], got %r and %r" % (points.shape, normals.shape))
+        total = int(volume.nx) * int(volume.ny) * int(volume.nz)
+        if len(probes) != total or len(depth) != total:
+            raise ValueError("probes, depth: expected %d x %d x %d records each, got %d and %d" % (volume.nz, volume.ny, volume.nx, len(probes), len(depth)))
+        rgb = np.zeros((len(points), 3), dtype=np.float32)
+        status = np.zeros(len(points), dtype=np.uint8)
+        self._check(lib().crt_probe_irradiance_visible(self.ctx, C.byref(volume), C.byref(visibility), _p(probes), _p(depth), _p(points), _p(normals),
+                                                       len(points), _p(rgb), _p(status)))
         return rgb, status
 
     def probe_stats(self) -> ProbeStats:

@@ -35,7 +35,10 @@ int main(int argc, char **argv) {
                  "       [--probes OX OY OZ SX SY SZ NX NY NZ [--probe-rays R] [--gi GI_SAMPLE_SIZE 1 [--seed S]] [--backface-limit X] [--probes-out FILE]]   (no\n"
                  "        render: bakes the NX x NY x NZ irradiance probe volume at origin O with spacing S, crt_hip.h's \"Irradiance probes\"; out.ppm is the\n"
                  "        volume seen by the camera: a hit pixel is the lookup at its point with its normal, every other pixel the background; FILE: the raw\n"
-                 "        128-byte records; one device)\n",
+                 "        128-byte records; one device;\n"
+                 "        --probe-visibility [MAX_DISTANCE] [--probe-depth-out FILE]: crt_hip.h's \"Probe visibility\": the bake also makes the depth records,\n"
+                 "        with the volume's default parameters but for MAX_DISTANCE, and out.ppm is the Chebyshev-weighted lookup; FILE: the raw 512-byte depth\n"
+                 "        records; it needs --probes)\n",
                  argv[0]);
     return 2;
   }
@@ -66,7 +69,9 @@ int main(int argc, char **argv) {
   crt_probe_volume volume;
   crt_probe_volume_defaults(&volume);
   long long probeRays = -1;   // (-1: crt_probe_volume_defaults')
-  std::string probesOut;
+  std::string probesOut, probeDepthOut;
+  bool probeVisibility = false, probeMaxDistanceGiven = false;
+  float probeMaxDistance = 0.0f;
   for (int i = 3; i < argc; i++) {
     if (!strcmp(argv[i], "--folder") && i + 1 < argc) folder = argv[++i];
     else if (!strcmp(argv[i], "--depth") && i + 1 < argc) depth = (unsigned)atoi(argv[++i]);
@@ -116,6 +121,11 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--probe-rays") && i + 1 < argc) probeRays = atoll(argv[++i]);
     else if (!strcmp(argv[i], "--backface-limit") && i + 1 < argc) { backfaceLimitGiven = true; volume.backface_limit = (float)atof(argv[++i]); }
     else if (!strcmp(argv[i], "--probes-out") && i + 1 < argc) probesOut = argv[++i];
+    else if (!strcmp(argv[i], "--probe-visibility")) {
+      probeVisibility = true;
+      if (i + 1 < argc && argv[i + 1][0] != '-') { probeMaxDistanceGiven = true; probeMaxDistance = (float)atof(argv[++i]); }
+    }
+    else if (!strcmp(argv[i], "--probe-depth-out") && i + 1 < argc) probeDepthOut = argv[++i];
     else if (!strcmp(argv[i], "--probe") && i + 2 < argc) { probe = true; probeRow = (unsigned)atoi(argv[++i]); probeCol = (unsigned)atoi(argv[++i]); }
   }
   if (bake && (devices.size() > 0 || progressive || adaptive || denoise || probe)) {
@@ -128,6 +138,14 @@ int main(int argc, char **argv) {
   }
   if ((probeRays != -1 || backfaceLimitGiven || !probesOut.empty()) && !probes) {
     std::fprintf(stderr, "error: --probe-rays, --backface-limit and --probes-out need --probes\n");
+    return 2;
+  }
+  if ((probeVisibility || !probeDepthOut.empty()) && !probes) {
+    std::fprintf(stderr, "error: --probe-visibility and --probe-depth-out need --probes\n");
+    return 2;
+  }
+  if (!probeDepthOut.empty() && !probeVisibility) {
+    std::fprintf(stderr, "error: --probe-depth-out needs --probe-visibility\n");
     return 2;
   }
   if (probeRays != -1 && (probeRays < 0 || probeRays > 0xFFFFFFFFll)) {
@@ -214,7 +232,27 @@ int main(int argc, char **argv) {
       if (probeRays != -1) volume.rays = (uint32_t)probeRays;   // (the library refuses a count outside 1 .. 4096)
       volume.gi_seed = seed;
       crt_probe_stats ps{};
-      const std::vector<crt_probe> records = tracer.bakeProbes(volume, options, &ps);
+      crt_probe_visibility visibility{};
+      std::vector<crt_probe_depth> depth;
+      if (probeVisibility) {
+        if (crt_probe_visibility_defaults(&volume, &visibility) != CRT_OK) {
+          std::fprintf(stderr, "error: --probe-visibility: the probe volume is not valid\n");
+          return 1;
+        }
+        if (probeMaxDistanceGiven) {   // (the library refuses a distance that is not finite and > 0)
+          visibility.max_distance = probeMaxDistance;
+          visibility.variance_floor = 1e-6f * (probeMaxDistance * probeMaxDistance);
+        }
+      }
+      const std::vector<crt_probe> records = probeVisibility ? tracer.bakeProbesVisible(volume, visibility, options, &depth, &ps) : tracer.bakeProbes(volume, options, &ps);
+      if (!probeDepthOut.empty()) {
+        FILE *f = std::fopen(probeDepthOut.c_str(), "wb");
+        if (!f || std::fwrite(depth.data(), sizeof(crt_probe_depth), depth.size(), f) != depth.size()) {
+          std::fprintf(stderr, "error: cannot write %s\n", probeDepthOut.c_str());
+          return 1;
+        }
+        std::fclose(f);
+      }
       if (!probesOut.empty()) {
         FILE *f = std::fopen(probesOut.c_str(), "wb");
         if (!f || std::fwrite(records.data(), sizeof(crt_probe), records.size(), f) != records.size()) {
@@ -223,7 +261,8 @@ int main(int argc, char **argv) {
         }
         std::fclose(f);
       }
-      tracer.probeIrradianceView(outPath, volume, records);
+      if (probeVisibility) tracer.probeIrradianceView(outPath, volume, records, &visibility, &depth);
+      else tracer.probeIrradianceView(outPath, volume, records);
       std::printf("{\"probes\": %llu, \"invalid\": %llu, \"rays\": %llu, \"shoot_ms\": %.4f, \"project_ms\": %.4f, \"total_ms\": %.4f}\n",
                   (unsigned long long)ps.probes, (unsigned long long)ps.invalid, (unsigned long long)ps.rays, ps.shoot_ms, ps.project_ms, ps.total_ms);
       return 0;

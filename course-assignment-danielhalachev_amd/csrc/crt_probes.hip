@@ -2,12 +2,16 @@
 // primitives crt_probe_rays_device, crt_probe_project_device, crt_probe_validity_device and crt_probe_irradiance_device, the synchronous
 // crt_bake_probes and crt_probe_irradiance, and crt_get_probe_stats.  Kernels: csrc/kernel_probes.h; the rule: csrc/probe_rule.h.  The
 // colours are the radiance queries' (crt_shoot_rays_device, crt_shoot_rays_gi_device) and the hits crt_trace_rays_device's, called as any
-// caller calls them; nothing of a frame, a walk, a query or a lightmap bake is touched.
+// caller calls them; nothing of a frame, a walk, a query or a lightmap bake is touched.  And the volume's visibility term (include/crt_hip.h:
+// "Probe visibility"): crt_probe_visibility_defaults, the enqueue-only crt_probe_depth_device and crt_probe_irradiance_visible_device, the
+// synchronous crt_bake_probes_visible -- crt_bake_probes' chunk loop with one trace a chunk for the validity and the depth pass -- and
+// crt_probe_irradiance_visible.  Kernels: csrc/kernel_probe_depth.h; the rule: csrc/probe_depth_rule.h.
 #include "crt_internal.h"
 #include "device_array.h"
 
 namespace {
 #include "kernel_probes.h"
+#include "kernel_probe_depth.h"
 }  // namespace
 
 static_assert(sizeof(crt_probe_volume) == 48 && sizeof(crt_probe_grid) == 48 && offsetof(crt_probe_volume, nx) == offsetof(crt_probe_grid, n) &&
@@ -20,6 +24,10 @@ static_assert(sizeof(crt_probe) == 128 && offsetof(crt_probe, rays) == 4 * CRT_P
               "a record is eight 16-byte stores, the state in the last");
 static_assert(CRT_PROBE_INVALID == CRT_PROBE_STATE_INVALID && CRT_PROBE_VALID == CRT_PROBE_STATE_VALID, "the rule's states are the header's");
 static_assert(sizeof(crt_ray) == 24 && sizeof(crt_hit) == 48, "a ray is a 16-byte and an 8-byte store");
+static_assert(sizeof(crt_probe_depth) == 512 && sizeof(crt_probe_depth) == CRT_PROBE_DEPTH_TEXELS * sizeof(float2), "a depth record is a wave's 64 8-byte stores");
+static_assert(sizeof(crt_probe_visibility) == 20 && sizeof(crt_probe_vis) == 20 && offsetof(crt_probe_visibility, max_distance) == offsetof(crt_probe_vis, max_distance) &&
+                  offsetof(crt_probe_visibility, min_weight) == offsetof(crt_probe_vis, min_weight),
+              "the rule reads crt_probe_visibility as it is");
 
 // rays of one chunk of crt_bake_probes: its scratch is 88 bytes a ray (ray, key, colour, hit)
 constexpr uint64_t PROBE_CHUNK_RAYS = 1ull << 20;
@@ -31,8 +39,10 @@ struct crt_probe_state {
     DeviceArray<float> rgb;
     DeviceArray<crt_hit> hits;
     DeviceArray<float4> probes;
-    // crt_probe_irradiance: the volume's records, the points, the normals, the colours, the statuses
+    DeviceArray<float2> depth;   // crt_bake_probes_visible: the depth records when the caller keeps none on the device
+    // crt_probe_irradiance and crt_probe_irradiance_visible: the volume's records, the points, the normals, the colours, the statuses
     DeviceArray<float4> look_probes;
+    DeviceArray<float2> look_depth;
     DeviceArray<float> points, normals, look_rgb;
     DeviceArray<uint8_t> status;
     uint32_t *pin = nullptr;
@@ -152,12 +162,73 @@ extern "C" int crt_probe_irradiance_device(crt_ctx *ctx, const crt_probe_volume 
     return CRT_OK;
 }
 
-extern "C" int crt_bake_probes(crt_ctx *ctx, const crt_probe_volume *volume, const crt_options *options, crt_probe *out_probes, crt_probe *d_probes) {
-    const char *what = "crt_bake_probes";
+static crt_probe_vis vis_of(const crt_probe_visibility *v) {
+    crt_probe_vis p;
+    memcpy(&p, v, sizeof(p));
+    return p;
+}
+
+static int visibility_check(crt_ctx *ctx, const char *what, const crt_probe_visibility *v) {
+    if (!v) return refuse(ctx, what, "visibility is NULL");
+    if (!crt_probe_vis_valid(vis_of(v)))
+        return refuse(ctx, what, "the visibility is not valid: size == sizeof(crt_probe_visibility), max_distance finite and > 0, normal_bias finite and >= 0, "
+                                 "variance_floor finite and > 0, min_weight finite in (0, 1]");
+    return CRT_OK;
+}
+
+extern "C" int crt_probe_visibility_defaults(const crt_probe_volume *volume, crt_probe_visibility *visibility) {
+    if (!volume || !visibility || !crt_probe_grid_valid(grid_of(volume))) return CRT_ERR_INVALID;
+    crt_probe_vis p;
+    crt_probe_vis_defaults(grid_of(volume), &p);
+    memcpy(visibility, &p, sizeof(p));
+    return CRT_OK;
+}
+
+extern "C" int crt_probe_depth_device(crt_ctx *ctx, const crt_ray *d_rays, const crt_hit *d_hits, uint32_t count, uint32_t rays, float max_distance,
+                                      crt_probe_depth *d_depth, void *stream) {
+    const char *what = "crt_probe_depth_device";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = range_check(ctx, what, count, rays)) return rc;
+    if (!crt_finite(max_distance) || !(max_distance > 0.0f)) return refuse(ctx, what, "max_distance is not finite and > 0");
+    if (count == 0) return CRT_OK;
+    if (!d_rays || !d_hits || !d_depth) return refuse(ctx, what, "d_rays, d_hits or d_depth is NULL");
+    if ((uintptr_t)d_depth % 16u) return refuse(ctx, what, "d_depth must be aligned to 16 bytes");
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(probe_depth, dim3(wave_blocks_of(count)), dim3(BLOCK), 0, (hipStream_t)stream,
+                       ProbeDepthArgs{d_rays, d_hits, count, rays, max_distance, (float2 *)d_depth});
+    CRT_HIP_CHECK(ctx, hipGetLastError());
+    return CRT_OK;
+}
+
+extern "C" int crt_probe_irradiance_visible_device(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe_visibility *visibility, const crt_probe *d_probes,
+                                                   const crt_probe_depth *d_depth, const float *d_points, const float *d_normals, uint64_t n, float *d_rgb,
+                                                   uint8_t *d_status, void *stream) {
+    const char *what = "crt_probe_irradiance_visible_device";
     if (!ctx) return CRT_ERR_INVALID;
     if (int rc = volume_check(ctx, what, volume)) return rc;
+    if (int rc = visibility_check(ctx, what, visibility)) return rc;
+    if (n == 0) return CRT_OK;
+    if (n >= CRT_MAX_PIXELS) return refuse(ctx, what, "n = " + std::to_string(n) + " >= 2^31");
+    if (!d_probes || !d_depth || !d_points || !d_normals || !d_rgb) return refuse(ctx, what, "d_probes, d_depth, d_points, d_normals or d_rgb is NULL");
+    if ((uintptr_t)d_probes % 16u || (uintptr_t)d_depth % 16u) return refuse(ctx, what, "d_probes and d_depth must be aligned to 16 bytes");
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(probe_lookup_visible, dim3(blocks_of(n)), dim3(BLOCK), 0, (hipStream_t)stream,
+                       ProbeLookupVisibleArgs{grid_of(volume), vis_of(visibility), (const float4 *)d_probes, (const float2 *)d_depth, d_points, d_normals, n, d_rgb,
+                                              d_status});
+    CRT_HIP_CHECK(ctx, hipGetLastError());
+    return CRT_OK;
+}
+
+// crt_bake_probes (visibility == NULL: no depth pass, the trace only for the validity pass) and crt_bake_probes_visible
+static int bake_probes(crt_ctx *ctx, const char *what, const crt_probe_volume *volume, const crt_probe_visibility *visibility, const crt_options *options,
+                       crt_probe *out_probes, crt_probe *d_probes, crt_probe_depth *out_depth, crt_probe_depth *d_depth) {
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = volume_check(ctx, what, volume)) return rc;
+    if (visibility)
+        if (int rc = visibility_check(ctx, what, visibility)) return rc;
     if (!options) return refuse(ctx, what, "options is NULL");
     if (d_probes && (uintptr_t)d_probes % 16u) return refuse(ctx, what, "d_probes must be aligned to 16 bytes");
+    if (d_depth && (uintptr_t)d_depth % 16u) return refuse(ctx, what, "d_depth must be aligned to 16 bytes");
     // what the radiance call behind it would refuse, asked before anything is enqueued
     if (int rc = query_shoot_check(ctx, what, options)) return rc;
     if (ctx->pending)
@@ -168,17 +239,20 @@ extern "C" int crt_bake_probes(crt_ctx *ctx, const crt_probe_volume *volume, con
     hipStream_t stream = ctx->stream;
     const crt_probe_grid g = grid_of(volume);
     const uint32_t total = crt_probe_count(g), R = g.rays;
-    const bool gi = options->use_gi != 0, validity = g.backface_limit != 1.0f;
+    const bool gi = options->use_gi != 0, validity = g.backface_limit != 1.0f, depth = visibility != nullptr;
     const uint32_t chunk = ctx->probe_chunk ? ctx->probe_chunk : (uint32_t)std::max<uint64_t>(PROBE_CHUNK_RAYS / R, 1u);
     const uint64_t chunk_rays = (uint64_t)std::min(chunk, total) * R;
     if (int rc = reserve_all(ctx, B->rays, chunk_rays, B->rgb, 3 * chunk_rays, B->counts, (uint64_t)1)) return rc;
     if (gi)
         if (int rc = B->keys.reserve(ctx, chunk_rays)) return rc;
-    if (validity)
+    if (validity || depth)
         if (int rc = B->hits.reserve(ctx, chunk_rays)) return rc;
     if (!d_probes)
         if (int rc = B->probes.reserve(ctx, 8 * (uint64_t)total)) return rc;
+    if (depth && !d_depth)
+        if (int rc = B->depth.reserve(ctx, CRT_PROBE_DEPTH_TEXELS * (uint64_t)total)) return rc;
     crt_probe *records = d_probes ? d_probes : (crt_probe *)B->probes.p;
+    crt_probe_depth *maps = d_depth ? d_depth : (crt_probe_depth *)B->depth.p;
     if (!B->pin) CRT_HIP_CHECK(ctx, hipHostMalloc((void **)&B->pin, sizeof(uint32_t)));
     for (hipEvent_t &e : B->ev)
         if (!e) CRT_HIP_CHECK(ctx, hipEventCreate(&e));
@@ -195,10 +269,12 @@ extern "C" int crt_bake_probes(crt_ctx *ctx, const crt_probe_volume *volume, con
             return rc;
         CRT_HIP_CHECK(ctx, hipEventRecord(B->ev[2], stream));
         if (int rc = crt_probe_project_device(ctx, B->rays.p, B->rgb.p, count, R, records + first, stream)) return rc;
-        if (validity) {
+        if (validity || depth)   // one trace serves both passes
             if (int rc = crt_trace_rays_device(ctx, B->rays.p, n, CRT_RAY_REFLECTION, B->hits.p, stream)) return rc;
+        if (validity)
             if (int rc = crt_probe_validity_device(ctx, B->rays.p, B->hits.p, count, R, g.backface_limit, records + first, stream)) return rc;
-        }
+        if (depth)
+            if (int rc = crt_probe_depth_device(ctx, B->rays.p, B->hits.p, count, R, visibility->max_distance, maps + first, stream)) return rc;
         CRT_HIP_CHECK(ctx, hipEventRecord(B->ev[3], stream));
         CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));   // the next chunk writes the same scratch, and the events are read
         float ms = 0;
@@ -214,6 +290,7 @@ extern "C" int crt_bake_probes(crt_ctx *ctx, const crt_probe_volume *volume, con
     CRT_HIP_CHECK(ctx, hipGetLastError());
     CRT_HIP_CHECK(ctx, hipMemcpyAsync(B->pin, B->counts.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     if (out_probes) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_probes, records, (size_t)total * sizeof(crt_probe), hipMemcpyDeviceToHost, stream));
+    if (depth && out_depth) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_depth, maps, (size_t)total * sizeof(crt_probe_depth), hipMemcpyDeviceToHost, stream));
     CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));
 
     crt_probe_stats &st = B->stats;
@@ -224,6 +301,51 @@ extern "C" int crt_bake_probes(crt_ctx *ctx, const crt_probe_volume *volume, con
     st.shoot_ms = shoot_ms;
     st.project_ms = project_ms;
     st.total_ms = total_ms;
+    return CRT_OK;
+}
+
+extern "C" int crt_bake_probes(crt_ctx *ctx, const crt_probe_volume *volume, const crt_options *options, crt_probe *out_probes, crt_probe *d_probes) {
+    return bake_probes(ctx, "crt_bake_probes", volume, nullptr, options, out_probes, d_probes, nullptr, nullptr);
+}
+
+extern "C" int crt_bake_probes_visible(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe_visibility *visibility, const crt_options *options,
+                                       crt_probe *out_probes, crt_probe *d_probes, crt_probe_depth *out_depth, crt_probe_depth *d_depth) {
+    const char *what = "crt_bake_probes_visible";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (!visibility) return refuse(ctx, what, "visibility is NULL");
+    return bake_probes(ctx, what, volume, visibility, options, out_probes, d_probes, out_depth, d_depth);
+}
+
+extern "C" int crt_probe_irradiance_visible(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe_visibility *visibility, const crt_probe *probes,
+                                            const crt_probe_depth *depth, const float *points, const float *normals, uint64_t n, float *out_rgb,
+                                            uint8_t *out_status) {
+    const char *what = "crt_probe_irradiance_visible";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = volume_check(ctx, what, volume)) return rc;
+    if (int rc = visibility_check(ctx, what, visibility)) return rc;
+    if (n == 0) return CRT_OK;
+    if (n >= CRT_MAX_PIXELS) return refuse(ctx, what, "n = " + std::to_string(n) + " >= 2^31");
+    if (!probes || !depth || !points || !normals || !out_rgb) return refuse(ctx, what, "probes, depth, points, normals or out_rgb is NULL");
+    if (ctx->pending)
+        if (int rc = crt_wait(ctx)) return rc;
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (int rc = probes_state(ctx)) return rc;
+    crt_probe_state *B = ctx->probes;
+    hipStream_t stream = ctx->stream;
+    const uint64_t total = crt_probe_count(grid_of(volume));
+    if (int rc = reserve_all(ctx, B->look_probes, 8 * total, B->look_depth, CRT_PROBE_DEPTH_TEXELS * total, B->points, 3 * n, B->normals, 3 * n, B->look_rgb, 3 * n,
+                             B->status, n))
+        return rc;
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(B->look_probes.p, probes, (size_t)total * sizeof(crt_probe), hipMemcpyHostToDevice, stream));
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(B->look_depth.p, depth, (size_t)total * sizeof(crt_probe_depth), hipMemcpyHostToDevice, stream));
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(B->points.p, points, (size_t)n * 12, hipMemcpyHostToDevice, stream));
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(B->normals.p, normals, (size_t)n * 12, hipMemcpyHostToDevice, stream));
+    if (int rc = crt_probe_irradiance_visible_device(ctx, volume, visibility, (const crt_probe *)B->look_probes.p, (const crt_probe_depth *)B->look_depth.p,
+                                                     B->points.p, B->normals.p, n, B->look_rgb.p, B->status.p, stream))
+        return rc;
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, B->look_rgb.p, (size_t)n * 12, hipMemcpyDeviceToHost, stream));
+    if (out_status) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_status, B->status.p, (size_t)n, hipMemcpyDeviceToHost, stream));
+    CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));
     return CRT_OK;
 }
 

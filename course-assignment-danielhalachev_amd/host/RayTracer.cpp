@@ -358,7 +358,45 @@ std::vector<float> RayTracer::probeIrradiance(const crt_probe_volume &volume, co
   return rgb;
 }
 
-std::vector<float> RayTracer::probeIrradianceView(const std::string &pathToImage, const crt_probe_volume &volume, const std::vector<crt_probe> &probes) {
+std::vector<crt_probe> RayTracer::bakeProbesVisible(const crt_probe_volume &volume, const crt_probe_visibility &visibility, const RenderOptions &ro,
+                                                    std::vector<crt_probe_depth> *depth, crt_probe_stats *stats) {
+  if (multi) throw std::runtime_error("bakeProbesVisible: not available on a multi-device tracer");
+  std::vector<crt_probe> probes((size_t)volume.nx * volume.ny * volume.nz);
+  if (depth) depth->assign(probes.size(), crt_probe_depth{});
+  crt_options options{};
+  options.max_depth = ro.MAX_DEPTH;
+  options.shadow_bias = ro.SHADOW_BIAS;
+  options.reflection_bias = ro.REFLECTION_BIAS;
+  options.refraction_bias = ro.REFRACTION_BIAS;
+  options.use_gi = ro.USE_GI ? 1u : 0u;
+  options.gi_sample_size = ro.GI_SAMPLE_SIZE;
+  options.monte_carlo_bias = ro.MONTE_CARLO_BIAS;
+  options.gi_seed = giSeed;
+  if (crt_bake_probes_visible(ctx, &volume, &visibility, &options, probes.empty() ? nullptr : probes.data(), nullptr,
+                              depth && !depth->empty() ? depth->data() : nullptr, nullptr) != CRT_OK)
+    throw std::runtime_error(std::string("bakeProbesVisible failed: ") + crt_last_error(ctx));
+  if (stats && crt_get_probe_stats(ctx, stats) != CRT_OK) throw std::runtime_error(std::string("bakeProbesVisible failed: ") + crt_last_error(ctx));
+  return probes;
+}
+
+std::vector<float> RayTracer::probeIrradianceVisible(const crt_probe_volume &volume, const crt_probe_visibility &visibility, const std::vector<crt_probe> &probes,
+                                                     const std::vector<crt_probe_depth> &depth, const std::vector<float> &points,
+                                                     const std::vector<float> &normals, std::vector<unsigned char> *status) {
+  if (multi) throw std::runtime_error("probeIrradianceVisible: not available on a multi-device tracer");
+  if (points.size() % 3 || normals.size() != points.size()) throw std::runtime_error("probeIrradianceVisible: three floats per point, one normal per point");
+  if (probes.size() != (size_t)volume.nx * volume.ny * volume.nz || depth.size() != probes.size())
+    throw std::runtime_error("probeIrradianceVisible: one record and one depth record per probe of the volume");
+  const size_t n = points.size() / 3;
+  std::vector<float> rgb(points.size());
+  if (status) status->assign(n, 0);
+  if (crt_probe_irradiance_visible(ctx, &volume, &visibility, probes.data(), depth.data(), points.data(), normals.data(), n, rgb.data(),
+                                   status && n ? status->data() : nullptr) != CRT_OK)
+    throw std::runtime_error(std::string("probeIrradianceVisible failed: ") + crt_last_error(ctx));
+  return rgb;
+}
+
+std::vector<float> RayTracer::probeIrradianceView(const std::string &pathToImage, const crt_probe_volume &volume, const std::vector<crt_probe> &probes,
+                                                  const crt_probe_visibility *visibility, const std::vector<crt_probe_depth> *depth) {
   const unsigned int W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
   const size_t n = (size_t)W * H;
   const std::vector<crt_hit> hits = traceRays(cameraRays(), CRT_RAY_PRIMARY);
@@ -366,7 +404,8 @@ std::vector<float> RayTracer::probeIrradianceView(const std::string &pathToImage
   for (size_t i = 0; i < n; i++)
     for (int k = 0; k < 3; k++) { points[3 * i + k] = hits[i].point[k]; normals[3 * i + k] = hits[i].normal[k]; }
   std::vector<unsigned char> status;
-  std::vector<float> rgb = probeIrradiance(volume, probes, points, normals, &status);
+  std::vector<float> rgb = visibility && depth ? probeIrradianceVisible(volume, *visibility, probes, *depth, points, normals, &status)
+                                               : probeIrradiance(volume, probes, points, normals, &status);
   const Color &bg = scene.sceneSettings.sceneBackgroundColor;
   for (size_t i = 0; i < n; i++)
     if (!hits[i].hit || !status[i]) { rgb[3 * i] = bg.x; rgb[3 * i + 1] = bg.y; rgb[3 * i + 2] = bg.z; }

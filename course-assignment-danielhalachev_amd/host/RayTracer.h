@@ -135,7 +135,18 @@ class RayTracer {
   std::vector<crt_probe> bakeProbes(const crt_probe_volume &volume, const RenderOptions &renderOptions, crt_probe_stats *stats = nullptr);
   std::vector<float> probeIrradiance(const crt_probe_volume &volume, const std::vector<crt_probe> &probes, const std::vector<float> &points,
                                      const std::vector<float> &normals, std::vector<unsigned char> *status = nullptr);
-  std::vector<float> probeIrradianceView(const std::string &pathToImage, const crt_probe_volume &volume, const std::vector<crt_probe> &probes);
+  std::vector<float> probeIrradianceView(const std::string &pathToImage, const crt_probe_volume &volume, const std::vector<crt_probe> &probes,
+                                         const crt_probe_visibility *visibility = nullptr, const std::vector<crt_probe_depth> *depth = nullptr);
+
+  // ---- probe visibility (crt_hip.h: "Probe visibility", crt_bake_probes_visible, crt_probe_irradiance_visible): bakeProbesVisible is
+  // bakeProbes with the depth pass -- *depth takes the volume's nx * ny * nz depth records --, and probeIrradianceVisible is probeIrradiance
+  // with every corner weighted by the Chebyshev bound of its depth record.  probeIrradianceView with a visibility and depth records looks the
+  // camera rays' first hits up that way.  Single-device tracers only.
+  std::vector<crt_probe> bakeProbesVisible(const crt_probe_volume &volume, const crt_probe_visibility &visibility, const RenderOptions &renderOptions,
+                                           std::vector<crt_probe_depth> *depth, crt_probe_stats *stats = nullptr);
+  std::vector<float> probeIrradianceVisible(const crt_probe_volume &volume, const crt_probe_visibility &visibility, const std::vector<crt_probe> &probes,
+                                            const std::vector<crt_probe_depth> &depth, const std::vector<float> &points, const std::vector<float> &normals,
+                                            std::vector<unsigned char> *status = nullptr);
 
   // ---- chain guides (crt_hip.h: "Chain guides", crt_guide_rays): for every ray the guide record of the surface it shows -- the chain of
   // closest hits through reflective and refractive meshes to the first diffuse or constant surface, a miss or maxBounces (<= 63) --, with

@@ -1253,6 +1253,104 @@ int crt_probe_irradiance(crt_ctx *ctx, const crt_probe_volume *volume, const crt
                          float *out_rgb, uint8_t *out_status);
 int crt_get_probe_stats(crt_ctx *ctx, crt_probe_stats *out);
 
+/* ---- Probe visibility: a depth record per probe and a Chebyshev-weighted lookup, so that an irradiance probe volume does not leak light
+ * through walls.  crt_probe_irradiance* above blends a cell's eight corners by trilinear weight alone; the calls of this section lift that
+ * limit: crt_probe_depth_device and crt_bake_probes_visible store, per probe and per direction, the first two moments of the distance the
+ * probe's rays saw, and crt_probe_irradiance_visible* weights every corner by a one-sided Chebyshev bound on "this probe sees the point".
+ * Kernels: csrc/kernel_probe_depth.h; the rule, one header for host and device: csrc/probe_depth_rule.h.  It is additive: crt_bake_probes
+ * and crt_probe_irradiance* give the bytes they gave, and no frame, walk, query, radiance, GI-frame or lightmap kernel is involved or
+ * changed.  Single-device contexts only.
+ *
+ * The rule (csrc/probe_depth_rule.h, verbatim; tests/probe_depth_sets.py restates it in numpy and the GPU gives its bits):
+ * Depth record.  crt_probe_depth is 512 bytes: 64 pairs (mean, mean2) of float32, pair k = row * 8 + col the texel (col, row) of an 8 x 8
+ *   octahedral map of the sphere.  The side is CRT_PROBE_DEPTH_SIDE = 8: a wave's 64 lanes are a probe's 64 texels, and a tap is one
+ *   8-byte load.
+ * Texel direction.  e_k is the octahedral decode of the texel's centre:
+ *     qx = (((float)col + 0.5f) / 8.0f) * 2.0f - 1.0f, qy likewise from row
+ *     z = (1.0f - |qx|) - |qy|
+ *     (x, y) = (qx, qy) where z >= 0, otherwise the fold ((1.0f - |qy|) * sgn(qx), (1.0f - |qx|) * sgn(qy)), sgn(v) = v >= 0 ? 1.0f : -1.0f
+ *     len = sqrtf((x * x + y * y) + z * z); e_k = (x / len, y / len, z / len)
+ * Ray distance.  For ray j of the probe with the hit record h crt_trace_rays_device wrote:
+ *     r = (h.hit != 0 && h.t < max_distance) ? h.t : max_distance       (a NaN t gives max_distance)
+ *     r = r > 0.0f ? r : 0.0f
+ *   A back-face hit counts with its own distance.  d_j is the direction READ FROM THE RAY ARRAY as given.
+ * Projection.  For texel k, the left folds over j = 0 .. R - 1 in increasing order, each starting from 0.0f:
+ *     c = (d_j.x * e_k.x + d_j.y * e_k.y) + d_j.z * e_k.z; c = c > 0.0f ? c : 0.0f
+ *     w = c^16 by four squarings (w = c * c; w = w * w; w = w * w; w = w * w)
+ *     W = W + w; S1 = S1 + w * r; S2 = S2 + w * (r * r)
+ *   The folds run inside one lane: no cross-lane sum, no dependence on arrival.  Where W > 0.0f: mean = S1 / W, mean2 = S2 / W.  Otherwise
+ *   (nothing seen, or a NaN) the pair is (max_distance, max_distance * max_distance): the texel saw nothing and hides nothing.
+ * Depth tap.  For a direction u (a unit vector, but any floats are answered):
+ *     s = (|u.x| + |u.y|) + |u.z|; px = u.x / s; py = u.y / s
+ *     where u.z < 0.0f: (px, py) = ((1.0f - |py|) * sgn(px), (1.0f - |px|) * sgn(py)), both from the unfolded values
+ *     per axis: g = (p * 0.5f + 0.5f) * 8.0f - 0.5f, clamped as a float: g = g > -0.5f ? g : -0.5f (a NaN gives -0.5f), then
+ *         g = g < 7.5f ? g : 7.5f
+ *     i = (int32_t)g, lowered by one when (float)i > g: the floor, in [-1, 7]; f = g - (float)i
+ *     the four taps (tx, ty) = (ix + a, iy + b), b = 0, 1 outer, a = 0, 1 inner, have the weights (a ? fx : 1.0f - fx) * (b ? fy : 1.0f - fy)
+ *     an index outside [0, 7] wraps the octahedral way: tx < 0: tx = 0, ty = 7 - ty; tx > 7: tx = 7, ty = 7 - ty; then, with the new
+ *         values, ty < 0: ty = 0, tx = 7 - tx; ty > 7: ty = 7, tx = 7 - tx
+ *     k = ty * 8 + tx; it is compared with 64 as an integer before an address is formed
+ *     m1 = the left fold over the four taps, starting from 0.0f, of weight * mean_k; m2 likewise of weight * mean2_k
+ * Lookup.  csrc/probe_rule.h's lookup in the finite test, the per-axis clamp, the corner order, the trilinear weight wc = (wx * wy) * wz from
+ *   the point x, the skipped corners (wc == 0.0f, or not VALID), crt_probe_resolve and status = the corners used.  A used corner is added
+ *   with the weight w = wc * vis instead of wc.  With P the corner's crt_probe_position:
+ *     b.k = x.k + n.k * normal_bias; v.k = b.k - P.k
+ *     dist = sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z)
+ *     if dist > 0.0f fails (the point AT the probe, or a NaN): vis = 1.0f
+ *     otherwise u.k = v.k / dist; (m1, m2) = the depth tap of the corner's record at u
+ *         var = m2 - m1 * m1; var = |var|; var = var > variance_floor ? var : variance_floor        (a NaN gives variance_floor)
+ *         if dist <= m1: ch = 1.0f
+ *         else e = dist - m1; ch = var / (var + e * e); ch = (ch * ch) * ch
+ *         vis = ch > min_weight ? ch : min_weight                                                    (a NaN gives min_weight)
+ *   There is no direction ("wrap") factor, so with every pair (max_distance, max_distance^2) and every corner within max_distance of b the
+ *   lookup is csrc/probe_rule.h's bit for bit.
+ * Parameters.  crt_probe_visibility { uint32_t size; float max_distance, normal_bias, variance_floor, min_weight; }, 20 bytes.  Valid:
+ *   size == 20, max_distance finite and > 0, normal_bias finite and >= 0, variance_floor finite and > 0, min_weight finite in (0, 1].
+ *   crt_probe_visibility_defaults fills it from a volume:
+ *     diag = sqrtf((sx * sx + sy * sy) + sz * sz) of the spacing; max_distance = 1.5f * diag
+ *     normal_bias = 0.02f * the smallest spacing
+ *     variance_floor = 1e-6f * (max_distance * max_distance)
+ *     min_weight = 0.01f
+ *
+ * Known limits.
+ *   * The map's side is fixed at 8: a wall thinner than a texel's footprint at its distance is blurred with what lies behind it.
+ *   * There is no direction factor: a probe behind the surface's tangent plane is not down-weighted for that.
+ *   * Back-face hits count with their own distance.
+ *   * One max_distance per volume.
+ *   * Static scenes: nothing blends a re-baked depth record over time.
+ *   * Single-device contexts only.
+ * crt_probe_visibility_defaults: the parameters above from the volume's spacing; CRT_ERR_INVALID for a NULL or an invalid volume.  A
+ *   visibility that is not valid is CRT_ERR_INVALID in every call below, with nothing enqueued and nothing changed.
+ * crt_probe_depth_device and crt_probe_irradiance_visible_device only ENQUEUE one kernel on `stream`, as the four primitives above: no wait,
+ *   no allocation, no memset or copy node, so they can be captured.  count == 0 or n == 0 is CRT_OK and touches nothing; a NULL array with
+ *   work to do is CRT_ERR_INVALID.  Every d_depth must be aligned to 16 bytes.
+ * crt_probe_depth_device: the depth records of `count` probes of `rays` rays each (the ranges of crt_probe_project_device) from the rays
+ *   d_rays and the crt_hit records d_hits crt_trace_rays_device wrote for them to d_depth; max_distance must be finite and > 0.  It writes
+ *   all 512 bytes of a record.  Two runs give the same bytes.
+ * crt_probe_irradiance_visible_device: the lookup at n points (n < 2^31) in the volume's records d_probes and depth records d_depth
+ *   (nx * ny * nz each) to d_rgb and d_status (may be NULL), as crt_probe_irradiance_device.  crt_probe_irradiance_visible is its host
+ *   variant: every array is host memory; it copies in, runs, copies out and returns when the result is there.
+ * crt_bake_probes_visible is crt_bake_probes with the depth pass: the same chunk loop, and in every chunk ONE crt_trace_rays_device call
+ *   whose hits serve crt_probe_validity_device (when backface_limit != 1.0f) and crt_probe_depth_device (visibility->max_distance).  The SH
+ *   records are crt_bake_probes' bytes.  out_depth (host) and d_depth (device, aligned to 16), nx * ny * nz records each, may each be NULL,
+ *   as out_probes and d_probes.  It waits as crt_bake_probes waits, leaves what crt_bake_probes leaves as it was, and refuses what it
+ *   refuses, and a NULL or invalid visibility.  crt_get_probe_stats then describes this call: project_ms includes the trace and the depth
+ *   pass.  crt_debug_set_probe_chunk applies to it. */
+typedef struct crt_probe_depth { float moments[64][2]; } crt_probe_depth;   /* 512 bytes: (mean, mean2) of texel row * 8 + col */
+typedef struct crt_probe_visibility { uint32_t size; float max_distance, normal_bias, variance_floor, min_weight; } crt_probe_visibility;   /* 20 bytes */
+int crt_probe_visibility_defaults(const crt_probe_volume *volume, crt_probe_visibility *visibility);
+int crt_probe_depth_device(crt_ctx *ctx, const crt_ray *d_rays, const crt_hit *d_hits, uint32_t count, uint32_t rays, float max_distance,
+                           crt_probe_depth *d_depth, void *stream);
+int crt_probe_irradiance_visible_device(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe_visibility *visibility, const crt_probe *d_probes,
+                                        const crt_probe_depth *d_depth, const float *d_points, const float *d_normals, uint64_t n, float *d_rgb,
+                                        uint8_t *d_status /* may be NULL */, void *stream);
+int crt_probe_irradiance_visible(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe_visibility *visibility, const crt_probe *probes,
+                                 const crt_probe_depth *depth, const float *points, const float *normals, uint64_t n, float *out_rgb,
+                                 uint8_t *out_status /* may be NULL */);
+int crt_bake_probes_visible(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe_visibility *visibility, const crt_options *options,
+                            crt_probe *out_probes /* host, may be NULL */, crt_probe *d_probes /* device, may be NULL */,
+                            crt_probe_depth *out_depth /* host, may be NULL */, crt_probe_depth *d_depth /* device, may be NULL */);
+
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
  * stream per listed device (a device may be listed more than once); the covered 8x8 tiles are dealt round-robin, every
