@@ -223,6 +223,11 @@ class ProbeStats(C.Structure):
                 ("total_ms", C.c_double)]
 
 
+class ProbeLitStats(C.Structure):
+    """crt_probe_lit_stats: the DIFFUSE records of the last probe-lit query that took light from the volume, and those that found no probe"""
+    _fields_ = [("lit", C.c_uint64), ("unlit", C.c_uint64)]
+
+
 def make_probe_volume(**fields):
     """crt_probe_volume_defaults (origin 0, spacing 1, 1 x 1 x 1, 64 rays, gi_seed 0, backface_limit 1.0) with the given fields replaced;
     origin and spacing take three numbers each."""
@@ -333,6 +338,7 @@ DEVICE_SYMBOLS = ["crt_bvh_selftest", "crt_bvh_census", "crt_debug_set_filter_st
                   "crt_bake_probes", "crt_probe_irradiance", "crt_get_probe_stats", "crt_debug_set_probe_chunk",
                   "crt_probe_visibility_defaults", "crt_probe_depth_device", "crt_probe_irradiance_visible_device", "crt_probe_irradiance_visible",
                   "crt_bake_probes_visible",
+                  "crt_probe_light_hits_device", "crt_shoot_rays_lit", "crt_shoot_rays_lit_device", "crt_render_probe_lit", "crt_render_probe_lit_host", "crt_get_probe_lit_stats",
                   "crt_build_tree_device", "crt_built_tree_node_count", "crt_built_tree_index_total", "crt_built_tree_boxes",
                   "crt_built_tree_links", "crt_built_tree_indexes", "crt_built_tree_free", "crt_build_last_error",
                   "crt_multi_create", "crt_multi_set_camera", "crt_multi_render", "crt_multi_read_quantized", "crt_multi_get_stats",
@@ -469,6 +475,12 @@ def lib():
     L.crt_probe_irradiance_visible_device.argtypes = [vp, C.POINTER(ProbeVolume), C.POINTER(ProbeVisibility), vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
     L.crt_probe_irradiance_visible.argtypes = [vp, C.POINTER(ProbeVolume), C.POINTER(ProbeVisibility), vp, vp, vp, vp, C.c_uint64, vp, vp]
     L.crt_bake_probes_visible.argtypes = [vp, C.POINTER(ProbeVolume), C.POINTER(ProbeVisibility), C.POINTER(Options), vp, vp, vp, vp]
+    L.crt_probe_light_hits_device.argtypes = [vp, C.POINTER(ProbeVolume), C.POINTER(ProbeVisibility), vp, vp, vp, vp, C.c_uint64, u32, vp, vp, vp]
+    L.crt_shoot_rays_lit_device.argtypes = [vp, vp, C.c_uint64, u32, C.POINTER(Options), C.POINTER(ProbeVolume), C.POINTER(ProbeVisibility), vp, vp, vp, vp]
+    L.crt_shoot_rays_lit.argtypes = [vp, vp, C.c_uint64, u32, C.POINTER(Options), C.POINTER(ProbeVolume), C.POINTER(ProbeVisibility), vp, vp, vp]
+    L.crt_render_probe_lit.argtypes = [vp, C.POINTER(ProbeVolume), C.POINTER(ProbeVisibility), vp, vp, C.POINTER(Options), vp, vp]
+    L.crt_render_probe_lit_host.argtypes = [vp, C.POINTER(ProbeVolume), C.POINTER(ProbeVisibility), vp, vp, C.POINTER(Options), vp, vp]
+    L.crt_get_probe_lit_stats.argtypes = [vp, C.POINTER(ProbeLitStats)]
     L.crt_host_shoot_stats_layout.argtypes = [C.POINTER(u32), u32]
     L.crt_host_shoot_stats_layout.restype = u32
     L.crt_get_kernel_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -1306,6 +1318,81 @@ class Tracer:
         self._check(lib().crt_probe_irradiance_visible(self.ctx, C.byref(volume), C.byref(visibility), _p(probes), _p(depth), _p(points), _p(normals),
                                                        len(points), _p(rgb), _p(status)))
         return rgb, status
+
+    # ---- probe-lit radiance (include/crt_hip.h: "Probe-lit radiance"): diffuse hits take their bounce light from a probe volume
+    @staticmethod
+    def _vis_ref(visibility):
+        return C.byref(visibility) if visibility is not None else None
+
+    def probe_light_hits_device(self, volume, visibility, d_probes_ptr, d_depth_ptr, d_hits_ptr, d_status_ptr, n, gi_sample_size, d_rgb_ptr,
+                                d_counts_ptr=None, stream_ptr=None):
+        """For each of n records whose status byte is SHADE_DIFFUSE: rgb = (rgb + S * Lbar) * (1 / (S + 1)), Lbar the zonal lookup of the
+        record's point and normal in the volume (visibility None: the plain lookup; otherwise the Chebyshev-weighted one, with depth records).
+        hits uint8 [n, 48], status uint8 [n], rgb float32 [n, 3] in place, counts uint64 [2] or None ([0] += lit, [1] += unlit).  Enqueues
+        and returns."""
+        self._single("probe_light_hits_device")
+        self._check(lib().crt_probe_light_hits_device(self.ctx, C.byref(volume), self._vis_ref(visibility), C.c_void_p(d_probes_ptr),
+                                                      C.c_void_p(d_depth_ptr or 0), C.c_void_p(d_hits_ptr), C.c_void_p(d_status_ptr), int(n),
+                                                      int(gi_sample_size), C.c_void_p(d_rgb_ptr), C.c_void_p(d_counts_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    @staticmethod
+    def _probe_records(volume, probes, depth, need_depth):
+        probes = np.ascontiguousarray(probes, dtype=PROBE_DTYPE).reshape(-1)
+        total = int(volume.nx) * int(volume.ny) * int(volume.nz)
+        if len(probes) != total:
+            raise ValueError("probes: expected %d x %d x %d records, got %d" % (volume.nz, volume.ny, volume.nx, len(probes)))
+        if not need_depth:
+            return probes, None
+        depth = np.asarray(depth)
+        if depth.dtype != PROBE_DEPTH_DTYPE:                               # the moments themselves, float32 [..., 64, 2]
+            depth = np.ascontiguousarray(depth, dtype=np.float32).reshape(-1, 128).view(PROBE_DEPTH_DTYPE)
+        depth = np.ascontiguousarray(depth).reshape(-1)
+        if len(depth) != total:
+            raise ValueError("depth: expected %d x %d x %d records, got %d" % (volume.nz, volume.ny, volume.nx, len(depth)))
+        return probes, depth
+
+    def shoot_rays_lit(self, rays, volume, probes, visibility=None, depth=None, ray_type=RAY_REFLECTION, options=None, **option_fields):
+        """The GI build's colours with the probe volume in place of the sample rays: rays float32 [n, 6], probes (and, with a visibility,
+        depth) the volume's records as bake_probes / bake_probes_visible return them -> float32 [n, 3].  options: an Options with use_gi set
+        (its gi_sample_size is the rule's S), or make_options' fields by name."""
+        self._single("shoot_rays_lit")
+        rays = self._rays_array(rays)
+        if visibility is not None and depth is None:
+            raise ValueError("shoot_rays_lit: a visibility needs the volume's depth records")
+        probes, depth = self._probe_records(volume, probes, depth, visibility is not None)
+        rgb = np.zeros((len(rays), 3), dtype=np.float32)
+        o = self._gi_options(options, option_fields)
+        self._check(lib().crt_shoot_rays_lit(self.ctx, _p(rays), len(rays), ray_type, C.byref(o), C.byref(volume), self._vis_ref(visibility), _p(probes),
+                                             _p(depth) if depth is not None else None, _p(rgb)))
+        return rgb
+
+    def shoot_rays_lit_device(self, d_rays_ptr, n, d_rgb_ptr, volume, d_probes_ptr, visibility=None, d_depth_ptr=None, ray_type=RAY_REFLECTION,
+                              options=None, stream_ptr=None, **option_fields):
+        """The same on device memory (data_ptr() of: rays float32 [n, 6], rgb float32 [n, 3], probes uint8 [count, 128], depth uint8
+        [count, 512]) on the stream; the call waits for the stream once per recursion level, so it cannot be captured into a graph."""
+        self._single("shoot_rays_lit_device")
+        o = self._gi_options(options, option_fields)
+        self._check(lib().crt_shoot_rays_lit_device(self.ctx, C.c_void_p(d_rays_ptr), int(n), ray_type, C.byref(o), C.byref(volume),
+                                                    self._vis_ref(visibility), C.c_void_p(d_probes_ptr), C.c_void_p(d_depth_ptr or 0),
+                                                    C.c_void_p(d_rgb_ptr), C.c_void_p(stream_ptr or 0)))
+
+    def render_probe_lit(self, volume, d_probes_ptr, visibility=None, d_depth_ptr=None, options=None, quantized=False, **option_fields):
+        """The probe-lit frame: the camera's rays of every pixel through shoot_rays_lit_device -> float32 [H, W, 3], or, quantized=True,
+        (that, uint8 [H, W, 3] from the quantiser).  d_probes_ptr and d_depth_ptr are device memory."""
+        self._single("render_probe_lit")
+        o = self._gi_options(options, option_fields)
+        rgb = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        rgb8 = np.zeros((self.height, self.width, 3), dtype=np.uint8) if quantized else None
+        self._check(lib().crt_render_probe_lit(self.ctx, C.byref(volume), self._vis_ref(visibility), C.c_void_p(d_probes_ptr), C.c_void_p(d_depth_ptr or 0),
+                                               C.byref(o), _p(rgb), _p(rgb8) if quantized else None))
+        return (rgb, rgb8) if quantized else rgb
+
+    def probe_lit_stats(self) -> ProbeLitStats:
+        """lit / unlit: the DIFFUSE records of the last probe-lit query or frame, over all its levels (waits for it)."""
+        self._single("probe_lit_stats")
+        st = ProbeLitStats()
+        self._check(lib().crt_get_probe_lit_stats(self.ctx, C.byref(st)))
+        return st
 
     def probe_stats(self) -> ProbeStats:
         self._single("probe_stats")

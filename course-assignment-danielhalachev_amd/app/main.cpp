@@ -38,7 +38,10 @@ int main(int argc, char **argv) {
                  "        128-byte records; one device;\n"
                  "        --probe-visibility [MAX_DISTANCE] [--probe-depth-out FILE]: crt_hip.h's \"Probe visibility\": the bake also makes the depth records,\n"
                  "        with the volume's default parameters but for MAX_DISTANCE, and out.ppm is the Chebyshev-weighted lookup; FILE: the raw 512-byte depth\n"
-                 "        records; it needs --probes)\n",
+                 "        records; it needs --probes;\n"
+                 "        --probe-lit [S]: crt_hip.h's \"Probe-lit radiance\": the volume is baked with --depth minus one, and out.ppm is the frame of the\n"
+                 "        radiance queries -- direct light, mirrors and glass -- whose diffuse hits take S (default: GI_SAMPLE_SIZE) times the volume's zonal\n"
+                 "        lookup as their indirect sum; it needs --probes and --gi GI_SAMPLE_SIZE 1)\n",
                  argv[0]);
     return 2;
   }
@@ -72,6 +75,8 @@ int main(int argc, char **argv) {
   std::string probesOut, probeDepthOut;
   bool probeVisibility = false, probeMaxDistanceGiven = false;
   float probeMaxDistance = 0.0f;
+  bool probeLit = false;
+  long long probeLitSamples = -1;   // (-1: GI_SAMPLE_SIZE)
   for (int i = 3; i < argc; i++) {
     if (!strcmp(argv[i], "--folder") && i + 1 < argc) folder = argv[++i];
     else if (!strcmp(argv[i], "--depth") && i + 1 < argc) depth = (unsigned)atoi(argv[++i]);
@@ -126,6 +131,10 @@ int main(int argc, char **argv) {
       if (i + 1 < argc && argv[i + 1][0] != '-') { probeMaxDistanceGiven = true; probeMaxDistance = (float)atof(argv[++i]); }
     }
     else if (!strcmp(argv[i], "--probe-depth-out") && i + 1 < argc) probeDepthOut = argv[++i];
+    else if (!strcmp(argv[i], "--probe-lit")) {
+      probeLit = true;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') probeLitSamples = atoll(argv[++i]);
+    }
     else if (!strcmp(argv[i], "--probe") && i + 2 < argc) { probe = true; probeRow = (unsigned)atoi(argv[++i]); probeCol = (unsigned)atoi(argv[++i]); }
   }
   if (bake && (devices.size() > 0 || progressive || adaptive || denoise || probe)) {
@@ -142,6 +151,10 @@ int main(int argc, char **argv) {
   }
   if ((probeVisibility || !probeDepthOut.empty()) && !probes) {
     std::fprintf(stderr, "error: --probe-visibility and --probe-depth-out need --probes\n");
+    return 2;
+  }
+  if (probeLit && (!probes || !useGI || probeLitSamples > 64)) {
+    std::fprintf(stderr, "error: --probe-lit needs --probes and --gi GI_SAMPLE_SIZE 1, and an S of 0 .. 64\n");
     return 2;
   }
   if (!probeDepthOut.empty() && !probeVisibility) {
@@ -244,7 +257,10 @@ int main(int argc, char **argv) {
           visibility.variance_floor = 1e-6f * (probeMaxDistance * probeMaxDistance);
         }
       }
-      const std::vector<crt_probe> records = probeVisibility ? tracer.bakeProbesVisible(volume, visibility, options, &depth, &ps) : tracer.bakeProbes(volume, options, &ps);
+      // --probe-lit: the volume holds what a hit's sample rays would return, the radiance one bounce short of the frame's depth
+      crt::RenderOptions bakeOptions(options);
+      if (probeLit && bakeOptions.MAX_DEPTH > 0) bakeOptions.MAX_DEPTH--;
+      const std::vector<crt_probe> records = probeVisibility ? tracer.bakeProbesVisible(volume, visibility, bakeOptions, &depth, &ps) : tracer.bakeProbes(volume, bakeOptions, &ps);
       if (!probeDepthOut.empty()) {
         FILE *f = std::fopen(probeDepthOut.c_str(), "wb");
         if (!f || std::fwrite(depth.data(), sizeof(crt_probe_depth), depth.size(), f) != depth.size()) {
@@ -261,8 +277,19 @@ int main(int argc, char **argv) {
         }
         std::fclose(f);
       }
-      if (probeVisibility) tracer.probeIrradianceView(outPath, volume, records, &visibility, &depth);
+      crt_probe_lit_stats ls{};
+      if (probeLit) {
+        crt::RenderOptions litOptions(options);
+        if (probeLitSamples >= 0) litOptions.GI_SAMPLE_SIZE = (unsigned)probeLitSamples;
+        tracer.renderProbeLit(outPath, litOptions, volume, records, probeVisibility ? &visibility : nullptr, probeVisibility ? &depth : nullptr, &ls);
+      }
+      else if (probeVisibility) tracer.probeIrradianceView(outPath, volume, records, &visibility, &depth);
       else tracer.probeIrradianceView(outPath, volume, records);
+      if (probeLit)
+        std::printf("{\"probes\": %llu, \"invalid\": %llu, \"rays\": %llu, \"shoot_ms\": %.4f, \"project_ms\": %.4f, \"total_ms\": %.4f, \"lit\": %llu, \"unlit\": %llu}\n",
+                    (unsigned long long)ps.probes, (unsigned long long)ps.invalid, (unsigned long long)ps.rays, ps.shoot_ms, ps.project_ms, ps.total_ms,
+                    (unsigned long long)ls.lit, (unsigned long long)ls.unlit);
+      else
       std::printf("{\"probes\": %llu, \"invalid\": %llu, \"rays\": %llu, \"shoot_ms\": %.4f, \"project_ms\": %.4f, \"total_ms\": %.4f}\n",
                   (unsigned long long)ps.probes, (unsigned long long)ps.invalid, (unsigned long long)ps.rays, ps.shoot_ms, ps.project_ms, ps.total_ms);
       return 0;

@@ -214,6 +214,11 @@ CRT_INTERNAL int query_closest_run(crt_ctx *ctx, const crt_ray *d_rays, uint64_t
 // the widest levels of the radiance passes since this call (query_level_headroom reads them)
 CRT_INTERNAL void query_level_peaks_reset(crt_ctx *ctx);
 CRT_INTERNAL int query_level_headroom(crt_ctx *ctx, const crt_options *o, uint64_t pass_rays);   // behind a frame's sample 0: room in the level arrays for later samples
+// the probe-lit radiance queries (crt_probes.hip: crt_shoot_rays_lit*, crt_render_probe_lit): the GI radiance call's own check of the caller's
+// options, and its passes with gi_sample_size = 0 and probe_light_launch behind every level's lighting launches
+CRT_INTERNAL int query_lit_check(crt_ctx *ctx, const char *what, const crt_ray *d_rays, const crt_options *options, const float *d_rgb, uint32_t ray_type);
+CRT_INTERNAL int query_lit_run(crt_ctx *ctx, const char *what, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options,
+                               const struct ProbeLight *lit, float *d_rgb, hipStream_t stream);
 CRT_INTERNAL int guide_check(crt_ctx *ctx, const char *what, uint64_t n, uint32_t max_bounces);   // what every guide call asks beyond its arrays
 CRT_INTERNAL int guide_enqueue(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, float reflection_bias, float refraction_bias,
                                uint32_t max_bounces, crt_hit *d_out_hits, uint8_t *d_out_status, crt_ray *d_out_last_rays, void *d_work, hipStream_t stream,
@@ -226,6 +231,18 @@ CRT_INTERNAL int progressive_check(crt_ctx *ctx, const char *what, const uint32_
 CRT_INTERNAL void bake_destroy(crt_ctx *ctx);
 // ---- crt_probes.hip
 CRT_INTERNAL void probes_destroy(crt_ctx *ctx);
+// what a probe-lit radiance pass hands to every level (csrc/probe_lit_rule.h): the volume, checked by the entry point, and the caller's S
+struct ProbeLight {
+    const crt_probe_volume *volume;
+    const crt_probe_visibility *visibility;   // or null: the plain lookup
+    const crt_probe *d_probes;
+    const crt_probe_depth *d_depth;           // with a visibility
+    uint32_t samples;
+    unsigned long long *d_counts;             // or null: [0] += LIT records, [1] += UNLIT records
+};
+// probe_light_records for a level's records, unchecked: behind the level's lighting launches, for the radiance passes (crt_query.hip)
+CRT_INTERNAL int probe_light_launch(crt_ctx *ctx, const ProbeLight &L, const crt_hit *d_hits, const uint8_t *d_status, uint64_t n, float *d_rgb,
+                                    hipStream_t stream);
 // ---- crt_denoise.hip: the denoiser's settings check and launches, for crt_render_denoised (crt_giframe.hip)
 CRT_INTERNAL int denoise_check(crt_ctx *ctx, const char *what, const crt_denoise *d);
 CRT_INTERNAL int denoise_launch_variance(crt_ctx *ctx, const float *d_sum, const float *d_sq, const uint32_t *d_counts, uint64_t n, float *d_mean,

@@ -5,13 +5,17 @@
 // caller calls them; nothing of a frame, a walk, a query or a lightmap bake is touched.  And the volume's visibility term (include/crt_hip.h:
 // "Probe visibility"): crt_probe_visibility_defaults, the enqueue-only crt_probe_depth_device and crt_probe_irradiance_visible_device, the
 // synchronous crt_bake_probes_visible -- crt_bake_probes' chunk loop with one trace a chunk for the validity and the depth pass -- and
-// crt_probe_irradiance_visible.  Kernels: csrc/kernel_probe_depth.h; the rule: csrc/probe_depth_rule.h.
+// crt_probe_irradiance_visible.  Kernels: csrc/kernel_probe_depth.h; the rule: csrc/probe_depth_rule.h.  And the picture that reads the volume
+// (include/crt_hip.h: "Probe-lit radiance"): the enqueue-only crt_probe_light_hits_device, crt_shoot_rays_lit* -- crt_query.hip's GI level loop
+// with that launch behind every level's lighting --, crt_render_probe_lit and crt_get_probe_lit_stats.  Kernel: csrc/kernel_probe_light.h; the
+// rule: csrc/probe_lit_rule.h.
 #include "crt_internal.h"
 #include "device_array.h"
 
 namespace {
 #include "kernel_probes.h"
 #include "kernel_probe_depth.h"
+#include "kernel_probe_light.h"
 }  // namespace
 
 static_assert(sizeof(crt_probe_volume) == 48 && sizeof(crt_probe_grid) == 48 && offsetof(crt_probe_volume, nx) == offsetof(crt_probe_grid, n) &&
@@ -45,10 +49,20 @@ struct crt_probe_state {
     DeviceArray<float2> look_depth;
     DeviceArray<float> points, normals, look_rgb;
     DeviceArray<uint8_t> status;
+    // crt_shoot_rays_lit* and crt_render_probe_lit: the host variant's and the frame's rays, the call's LIT and UNLIT counters, their pinned
+    // copy, and the event behind that copy (lit_open: it has not been read yet)
+    DeviceArray<crt_ray> lit_rays;
+    DeviceArray<unsigned long long> lit_counts;
+    unsigned long long *lit_pin = nullptr;
+    hipEvent_t lit_ev = nullptr;
+    bool lit_open = false;
+    crt_probe_lit_stats lit_stats{};
     uint32_t *pin = nullptr;
     hipEvent_t ev[4] = {};
     crt_probe_stats stats{};
     ~crt_probe_state() {
+        if (lit_pin) (void)hipHostFree(lit_pin);
+        if (lit_ev) (void)hipEventDestroy(lit_ev);
         if (pin) (void)hipHostFree(pin);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
@@ -373,6 +387,211 @@ extern "C" int crt_probe_irradiance(crt_ctx *ctx, const crt_probe_volume *volume
     CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, B->look_rgb.p, (size_t)n * 12, hipMemcpyDeviceToHost, stream));
     if (out_status) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_status, B->status.p, (size_t)n, hipMemcpyDeviceToHost, stream));
     CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));
+    return CRT_OK;
+}
+
+// ---- probe-lit radiance (include/crt_hip.h: "Probe-lit radiance"; csrc/probe_lit_rule.h, csrc/kernel_probe_light.h): the DIFFUSE records of
+// a radiance query take their bounce light from the volume.  The primitive enqueues probe_light_records and nothing else; the query is
+// crt_query.hip's GI level loop with gi_sample_size = 0 and that launch behind every level's lighting launches (query_lit_run).
+
+// What every probe-lit call asks, in ONE place each.  light_check: of the volume, the visibility (only when there is one) and S --
+// crt_probe_irradiance_visible_device's refusals.  light_records_check: of the volume's records when there is work to do; `device`: they are
+// device memory, read with 16-byte loads.
+static int light_check(crt_ctx *ctx, const char *what, const crt_probe_volume *volume, const crt_probe_visibility *visibility, const uint32_t samples) {
+    if (int rc = volume_check(ctx, what, volume)) return rc;
+    if (visibility)
+        if (int rc = visibility_check(ctx, what, visibility)) return rc;
+    if (samples > 64u) return refuse(ctx, what, "gi_sample_size too large: " + std::to_string(samples) + ", at most 64");
+    return CRT_OK;
+}
+static int light_records_check(crt_ctx *ctx, const char *what, const crt_probe_visibility *visibility, const void *probes, const void *depth, const bool device) {
+    if (!probes) return refuse(ctx, what, "probes is NULL");
+    if (visibility && !depth) return refuse(ctx, what, "a visibility without depth records: depth is NULL");
+    if (device && ((uintptr_t)probes % 16u || (visibility && (uintptr_t)depth % 16u))) return refuse(ctx, what, "probes and depth must be aligned to 16 bytes");
+    return CRT_OK;
+}
+
+int probe_light_launch(crt_ctx *ctx, const ProbeLight &L, const crt_hit *d_hits, const uint8_t *d_status, const uint64_t n, float *d_rgb, hipStream_t stream) {
+    if (n == 0) return CRT_OK;
+    ProbeLightArgs P{};
+    P.grid = grid_of(L.volume);
+    if (L.visibility) P.vis = vis_of(L.visibility);
+    P.probes = (const float4 *)L.d_probes;
+    P.depth = (const float2 *)L.d_depth;
+    P.hits = d_hits; P.status = d_status; P.n = n; P.samples = L.samples; P.rgb = d_rgb; P.counts = L.d_counts;
+    hipLaunchKernelGGL(L.visibility ? probe_light_records<true> : probe_light_records<false>, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, P);
+    CRT_HIP_CHECK(ctx, hipGetLastError());
+    return CRT_OK;
+}
+
+extern "C" int crt_probe_light_hits_device(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe_visibility *visibility, const crt_probe *d_probes,
+                                           const crt_probe_depth *d_depth, const crt_hit *d_hits, const uint8_t *d_status, uint64_t n,
+                                           uint32_t gi_sample_size, float *d_rgb, uint64_t *d_counts, void *stream) {
+    const char *what = "crt_probe_light_hits_device";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (int rc = light_check(ctx, what, volume, visibility, gi_sample_size)) return rc;
+    if (n == 0) return CRT_OK;
+    if (n >= CRT_MAX_PIXELS) return refuse(ctx, what, "n = " + std::to_string(n) + " >= 2^31");
+    if (int rc = light_records_check(ctx, what, visibility, d_probes, d_depth, true)) return rc;
+    if (!d_hits || !d_status || !d_rgb) return refuse(ctx, what, "d_hits, d_status or d_rgb is NULL");
+    if ((uintptr_t)d_hits % 4u || (uintptr_t)d_rgb % 4u || (uintptr_t)d_counts % 8u)
+        return refuse(ctx, what, "d_hits and d_rgb must be aligned to 4 bytes, d_counts to 8");
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const ProbeLight L{volume, visibility, d_probes, visibility ? d_depth : nullptr, gi_sample_size, reinterpret_cast<unsigned long long *>(d_counts)};
+    return probe_light_launch(ctx, L, d_hits, d_status, n, d_rgb, (hipStream_t)stream);
+}
+
+// the counters of the last probe-lit query, once: waits for it
+static int light_harvest(crt_ctx *ctx) {
+    crt_probe_state *B = ctx->probes;
+    if (!B || !B->lit_open) return CRT_OK;
+    CRT_HIP_CHECK(ctx, hipEventSynchronize(B->lit_ev));
+    B->lit_open = false;
+    B->lit_stats.lit = B->lit_pin[0];
+    B->lit_stats.unlit = B->lit_pin[1];
+    return CRT_OK;
+}
+
+// the start of a probe-lit query on `stream`: the refusals, before anything is enqueued; then the call's two counters, cleared
+static int light_begin(crt_ctx *ctx, const char *what, const crt_ray *d_rays, const uint32_t ray_type, const crt_options *options, const float *d_rgb,
+                       const crt_probe_volume *volume, const crt_probe_visibility *visibility, const crt_probe *d_probes, const crt_probe_depth *d_depth,
+                       hipStream_t stream, ProbeLight *L) {
+    if (int rc = query_lit_check(ctx, what, d_rays, options, d_rgb, ray_type)) return rc;
+    if (int rc = light_check(ctx, what, volume, visibility, options->gi_sample_size)) return rc;
+    if (int rc = light_records_check(ctx, what, visibility, d_probes, d_depth, true)) return rc;
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    CRT_HIP_CHECK(ctx, hipStreamIsCapturing(stream, &status));
+    if (status != hipStreamCaptureStatusNone)
+        return refuse(ctx, what, "the stream is being captured and the call waits once a recursion level (there is no enqueue-only form)");
+    if (ctx->pending)
+        if (int rc = crt_wait(ctx)) return rc;
+    if (int rc = probes_state(ctx)) return rc;
+    crt_probe_state *B = ctx->probes;
+    if (int rc = B->lit_counts.reserve(ctx, 2)) return rc;
+    if (!B->lit_pin) CRT_HIP_CHECK(ctx, hipHostMalloc((void **)&B->lit_pin, 2 * sizeof(unsigned long long)));
+    if (!B->lit_ev) CRT_HIP_CHECK(ctx, hipEventCreate(&B->lit_ev));
+    if (int rc = light_harvest(ctx)) return rc;   // the last call's counters leave the pinned words before this call's copy lands there
+    B->lit_stats = crt_probe_lit_stats{};         // (a call that fails from here on leaves no other call's counts behind)
+    CRT_HIP_CHECK(ctx, hipMemsetAsync(B->lit_counts.p, 0, 2 * sizeof(unsigned long long), stream));
+    *L = ProbeLight{volume, visibility, d_probes, visibility ? d_depth : nullptr, options->gi_sample_size, B->lit_counts.p};
+    return CRT_OK;
+}
+
+// ... and its end: the counters on their way to pinned memory, behind the call's last launch
+static int light_end(crt_ctx *ctx, hipStream_t stream) {
+    crt_probe_state *B = ctx->probes;
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(B->lit_pin, B->lit_counts.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    CRT_HIP_CHECK(ctx, hipEventRecord(B->lit_ev, stream));
+    B->lit_open = true;
+    return CRT_OK;
+}
+
+extern "C" int crt_shoot_rays_lit_device(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options,
+                                         const crt_probe_volume *volume, const crt_probe_visibility *visibility, const crt_probe *d_probes,
+                                         const crt_probe_depth *d_depth, float *d_rgb, void *stream) {
+    const char *what = "crt_shoot_rays_lit_device";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    ProbeLight L{};
+    int rc;
+    if ((rc = light_begin(ctx, what, d_rays, ray_type, options, d_rgb, volume, visibility, d_probes, d_depth, (hipStream_t)stream, &L)) ||
+        (rc = query_lit_run(ctx, what, d_rays, n, ray_type, options, &L, d_rgb, (hipStream_t)stream)))
+        return rc;
+    return light_end(ctx, (hipStream_t)stream);
+}
+
+// the volume's records on the device for the host variants: the lookup calls' copies
+static int light_upload(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe *probes, const crt_probe_depth *depth, hipStream_t stream) {
+    crt_probe_state *B = ctx->probes;
+    const uint64_t total = crt_probe_count(grid_of(volume));
+    if (int rc = reserve_all(ctx, B->look_probes, 8 * total, B->look_depth, depth ? CRT_PROBE_DEPTH_TEXELS * total : 0)) return rc;
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(B->look_probes.p, probes, (size_t)total * sizeof(crt_probe), hipMemcpyHostToDevice, stream));
+    if (depth) CRT_HIP_CHECK(ctx, hipMemcpyAsync(B->look_depth.p, depth, (size_t)total * sizeof(crt_probe_depth), hipMemcpyHostToDevice, stream));
+    return CRT_OK;
+}
+
+extern "C" int crt_shoot_rays_lit(crt_ctx *ctx, const crt_ray *rays, uint64_t n, uint32_t ray_type, const crt_options *options, const crt_probe_volume *volume,
+                                  const crt_probe_visibility *visibility, const crt_probe *probes, const crt_probe_depth *depth, float *out_rgb) {
+    const char *what = "crt_shoot_rays_lit";
+    if (!ctx) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    if (int rc = query_lit_check(ctx, what, rays, options, out_rgb, ray_type)) return rc;
+    if (int rc = light_check(ctx, what, volume, visibility, options->gi_sample_size)) return rc;
+    if (int rc = light_records_check(ctx, what, visibility, probes, depth, false)) return rc;
+    if (n >= CRT_MAX_PIXELS) return refuse(ctx, what, "n = " + std::to_string(n) + " >= 2^31");
+    if (ctx->pending)
+        if (int rc = crt_wait(ctx)) return rc;
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (int rc = probes_state(ctx)) return rc;
+    crt_probe_state *B = ctx->probes;
+    hipStream_t stream = ctx->stream;
+    if (int rc = reserve_all(ctx, B->lit_rays, n, B->look_rgb, 3 * n)) return rc;
+    if (int rc = light_upload(ctx, volume, probes, visibility ? depth : nullptr, stream)) return rc;
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(B->lit_rays.p, rays, (size_t)n * sizeof(crt_ray), hipMemcpyHostToDevice, stream));
+    if (int rc = crt_shoot_rays_lit_device(ctx, B->lit_rays.p, n, ray_type, options, volume, visibility, (const crt_probe *)B->look_probes.p,
+                                           visibility ? (const crt_probe_depth *)B->look_depth.p : nullptr, B->look_rgb.p, stream))
+        return rc;
+    CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, B->look_rgb.p, (size_t)n * 12, hipMemcpyDeviceToHost, stream));
+    CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));
+    return CRT_OK;
+}
+
+// crt_render_probe_lit (`host` false: the records are device memory) and crt_render_probe_lit_host (true: host memory, uploaded first)
+static int render_lit(crt_ctx *ctx, const char *what, const crt_probe_volume *volume, const crt_probe_visibility *visibility, const crt_probe *d_probes,
+                      const crt_probe_depth *d_depth, const crt_options *options, float *out_rgb, uint8_t *out_rgb8, const bool host) {
+    if (!ctx) return CRT_ERR_INVALID;
+    const uint64_t pixels = (uint64_t)ctx->width * ctx->height;
+    if (int rc = pixels_check(ctx, what, pixels)) return rc;
+    if (pixels == 0) return CRT_OK;
+    if (!options) return refuse(ctx, what, "options is NULL");
+    if (ctx->pending)
+        if (int rc = crt_wait(ctx)) return rc;
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (int rc = probes_state(ctx)) return rc;
+    crt_probe_state *B = ctx->probes;
+    hipStream_t stream = ctx->stream;
+    if (int rc = B->lit_rays.reserve(ctx, pixels)) return rc;
+    // what the query would refuse, asked before the frame under way is ended and anything is enqueued
+    if (int rc = query_lit_check(ctx, what, B->lit_rays.p, options, ctx->d_frame, CRT_RAY_PRIMARY)) return rc;
+    if (int rc = light_check(ctx, what, volume, visibility, options->gi_sample_size)) return rc;
+    if (int rc = light_records_check(ctx, what, visibility, d_probes, d_depth, !host)) return rc;
+    giframe_reset(ctx);   // the persistent colour buffer is this frame's now, as after crt_render*
+    int rc;
+    if (host) {
+        if ((rc = light_upload(ctx, volume, d_probes, visibility ? d_depth : nullptr, stream))) return rc;
+        d_probes = (const crt_probe *)B->look_probes.p;
+        d_depth = visibility ? (const crt_probe_depth *)B->look_depth.p : nullptr;
+    }
+    if ((rc = crt_camera_rays_device(ctx, B->lit_rays.p, stream)) ||
+        (rc = crt_shoot_rays_lit_device(ctx, B->lit_rays.p, pixels, CRT_RAY_PRIMARY, options, volume, visibility, d_probes, d_depth, ctx->d_frame, stream)))
+        return rc;
+    if (out_rgb) CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb, ctx->d_frame, 3 * pixels * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (out_rgb8) {
+        if ((rc = crt_quantize_device(ctx, ctx->d_frame, 3 * pixels, ctx->d_quant, stream))) return rc;
+        CRT_HIP_CHECK(ctx, hipMemcpyAsync(out_rgb8, ctx->d_quant, 3 * pixels, hipMemcpyDeviceToHost, stream));
+    }
+    CRT_HIP_CHECK(ctx, hipStreamSynchronize(stream));
+    return CRT_OK;
+}
+
+extern "C" int crt_render_probe_lit(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe_visibility *visibility, const crt_probe *d_probes,
+                                    const crt_probe_depth *d_depth, const crt_options *options, float *out_rgb, uint8_t *out_rgb8) {
+    return render_lit(ctx, "crt_render_probe_lit", volume, visibility, d_probes, d_depth, options, out_rgb, out_rgb8, false);
+}
+
+extern "C" int crt_render_probe_lit_host(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe_visibility *visibility, const crt_probe *probes,
+                                         const crt_probe_depth *depth, const crt_options *options, float *out_rgb, uint8_t *out_rgb8) {
+    return render_lit(ctx, "crt_render_probe_lit_host", volume, visibility, probes, depth, options, out_rgb, out_rgb8, true);
+}
+
+extern "C" int crt_get_probe_lit_stats(crt_ctx *ctx, crt_probe_lit_stats *out) {
+    if (!ctx || !out) return CRT_ERR_INVALID;
+    *out = crt_probe_lit_stats{};
+    if (!ctx->probes) return CRT_OK;
+    CRT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (int rc = light_harvest(ctx)) return rc;
+    *out = ctx->probes->lit_stats;
     return CRT_OK;
 }
 

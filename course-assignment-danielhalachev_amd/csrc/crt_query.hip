@@ -565,6 +565,7 @@ struct ShootGi {
     const uint32_t *d_keys;   // the pass's keys on the device, or null: those of a frame's pixels key_first ..., sample 0
     uint32_t key_first;       // the index in the call of the pass's first ray
     float *d_direct;          // crt_shoot_rays_gi_split*: the pass's slice of the direct parts, or null: nothing more is launched
+    const ProbeLight *lit;    // crt_shoot_rays_lit*: the volume every level's DIFFUSE records are lit from, or null: nothing more is launched
 };
 
 // room for `cap` rays at level g (`own_rgb`: with colours of its own; level 0 writes the caller's array; `keys`: a GI call)
@@ -704,6 +705,9 @@ static int shoot_down(crt_ctx *ctx, ShootPass &P) {
         // a split call: level 0's colours are its records' direct light now, and the up-sweep overwrites them (csrc/split_rule.h)
         if (g == 0 && gi && P.gi->d_direct && (rc = split_launch_keep_direct(ctx, L.status.p, rgb, S.n, o->gi_sample_size, P.gi->d_direct, P.stream)))
             return rc;
+        // a probe-lit call: the level's DIFFUSE records take their bounce light from the volume now (csrc/probe_lit_rule.h); the pass runs
+        // with gi_sample_size = 0, so the up-sweep leaves them as they are
+        if (gi && P.gi->lit && (rc = probe_light_launch(ctx, *P.gi->lit, L.hits.p, L.status.p, S.n, rgb, P.stream))) return rc;
         G.child_count = d_count + g + 1;
         G.spawn = g + 1 <= o->max_depth ? 1u : 0u;   // a child enters shootRay with depth g + 1 (RayTracer.cpp:427)
         if ((rc = shoot_children(ctx, P, g, G))) return rc;
@@ -764,6 +768,7 @@ static int shoot_run(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t r
             part.d_keys = gi->d_keys ? gi->d_keys + done : nullptr;
             part.key_first = gi->key_first + (uint32_t)done;
             part.d_direct = gi->d_direct ? gi->d_direct + 3 * done : nullptr;
+            part.lit = gi->lit;
         }
         ShootPass P{d_rays + done, m, ray_type, options, d_rgb + 3 * done, stream, gi ? &part : nullptr, nullptr};
         if ((rc = query_list_reserve(ctx, m)) || (rc = shoot_level_reserve(ctx, 0, m, false, gi != nullptr)) || (rc = shoot_pass(ctx, P))) return rc;
@@ -982,6 +987,22 @@ int query_gi_run(crt_ctx *ctx, const crt_ray *d_rays, const uint32_t *d_keys, ui
                  const uint64_t pass, hipStream_t stream) {
     const ShootGi gi{d_keys, 0u, d_direct};
     return shoot_run(ctx, d_rays, n, CRT_RAY_PRIMARY, options, d_rgb, stream, pass, &gi);
+}
+
+// ---- what the probe-lit radiance queries (crt_probes.hip) run of the above
+int query_lit_check(crt_ctx *ctx, const char *what, const crt_ray *d_rays, const crt_options *options, const float *d_rgb, const uint32_t ray_type) {
+    uint64_t pass = 0;
+    return query_check(ctx, shoot_needs(what, d_rays, options, d_rgb, ray_type, true, &pass));
+}
+
+int query_lit_run(crt_ctx *ctx, const char *what, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options, const ProbeLight *lit,
+                  float *d_rgb, hipStream_t stream) {
+    crt_options o = *options;
+    o.gi_sample_size = 0;   // no sample rays: the volume stands for them
+    uint64_t pass = 0;
+    if (int rc = query_check(ctx, shoot_needs(what, d_rays, &o, d_rgb, ray_type, true, &pass))) return rc;
+    const ShootGi gi{nullptr, 0u, nullptr, lit};
+    return shoot_run(ctx, d_rays, n, ray_type, &o, d_rgb, stream, pass, &gi);
 }
 
 int query_closest_run(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, crt_hit *d_hits, hipStream_t stream) {

@@ -427,6 +427,52 @@ std::vector<float> RayTracer::probeIrradianceView(const std::string &pathToImage
   return rgb;
 }
 
+// renderOptions as the probe-lit calls take them: USE_GI set, GI_SAMPLE_SIZE the rule's S
+static crt_options litOptions(const RenderOptions &ro, uint32_t giSeed) {
+  crt_options options{};
+  options.max_depth = ro.MAX_DEPTH;
+  options.shadow_bias = ro.SHADOW_BIAS;
+  options.reflection_bias = ro.REFLECTION_BIAS;
+  options.refraction_bias = ro.REFRACTION_BIAS;
+  options.use_gi = 1u;
+  options.gi_sample_size = ro.GI_SAMPLE_SIZE;
+  options.monte_carlo_bias = ro.MONTE_CARLO_BIAS;
+  options.gi_seed = giSeed;
+  return options;
+}
+
+std::vector<float> RayTracer::shootRaysLit(const std::vector<crt_ray> &rays, unsigned rayType, const RenderOptions &ro, const crt_probe_volume &volume,
+                                           const std::vector<crt_probe> &probes, const crt_probe_visibility *visibility,
+                                           const std::vector<crt_probe_depth> *depth) {
+  if (multi) throw std::runtime_error("shootRaysLit: not available on a multi-device tracer");
+  if (probes.size() != (size_t)volume.nx * volume.ny * volume.nz || (visibility && (!depth || depth->size() != probes.size())))
+    throw std::runtime_error("shootRaysLit: one record per probe of the volume, and with a visibility one depth record");
+  std::vector<float> rgb(3 * rays.size());
+  const crt_options options = litOptions(ro, giSeed);
+  if (crt_shoot_rays_lit(ctx, rays.data(), rays.size(), rayType, &options, &volume, visibility, probes.data(), visibility ? depth->data() : nullptr,
+                         rgb.data()) != CRT_OK)
+    throw std::runtime_error(std::string("shootRaysLit failed: ") + crt_last_error(ctx));
+  return rgb;
+}
+
+std::vector<float> RayTracer::renderProbeLit(const std::string &pathToImage, const RenderOptions &ro, const crt_probe_volume &volume,
+                                             const std::vector<crt_probe> &probes, const crt_probe_visibility *visibility,
+                                             const std::vector<crt_probe_depth> *depth, crt_probe_lit_stats *stats) {
+  if (multi) throw std::runtime_error("renderProbeLit: not available on a multi-device tracer");
+  if (probes.empty() || probes.size() != (size_t)volume.nx * volume.ny * volume.nz || (visibility && (!depth || depth->size() != probes.size())))
+    throw std::runtime_error("renderProbeLit: one record per probe of the volume, and with a visibility one depth record");
+  const unsigned int W = scene.sceneSettings.image.width, H = scene.sceneSettings.image.height;
+  const size_t n = (size_t)W * H;
+  std::vector<float> rgb(3 * n);
+  std::vector<uint8_t> q(3 * n);
+  const crt_options options = litOptions(ro, giSeed);
+  if (crt_render_probe_lit_host(ctx, &volume, visibility, probes.data(), visibility ? depth->data() : nullptr, &options, rgb.data(), q.data()) != CRT_OK ||
+      (stats && crt_get_probe_lit_stats(ctx, stats) != CRT_OK))
+    throw std::runtime_error(std::string("renderProbeLit failed: ") + crt_last_error(ctx));
+  if (!pathToImage.empty()) writePPMQuantized(pathToImage, q.data(), W, H);
+  return rgb;
+}
+
 crt_query_stats RayTracer::queryStats() const {
   crt_query_stats s{};
   if (!multi) crt_get_query_stats(ctx, &s);

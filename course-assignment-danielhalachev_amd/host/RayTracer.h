@@ -148,6 +148,18 @@ class RayTracer {
                                             const std::vector<crt_probe_depth> &depth, const std::vector<float> &points, const std::vector<float> &normals,
                                             std::vector<unsigned char> *status = nullptr);
 
+  // ---- probe-lit radiance (crt_hip.h: "Probe-lit radiance", crt_shoot_rays_lit, crt_render_probe_lit): shootRaysLit is shootRaysGI with
+  // the probe volume in place of the sample rays -- a diffuse hit takes GI_SAMPLE_SIZE times the volume's zonal lookup at its point and
+  // normal as its indirect sum, through mirrors and glass too; renderProbeLit is that for the camera's rays of every pixel, written as a
+  // PPM when pathToImage is not empty, *stats the frame's lit and unlit records.  renderOptions.USE_GI is taken as set.  A visibility
+  // needs the depth records.  Single-device tracers only.
+  std::vector<float> shootRaysLit(const std::vector<crt_ray> &rays, unsigned rayType, const RenderOptions &renderOptions, const crt_probe_volume &volume,
+                                  const std::vector<crt_probe> &probes, const crt_probe_visibility *visibility = nullptr,
+                                  const std::vector<crt_probe_depth> *depth = nullptr);
+  std::vector<float> renderProbeLit(const std::string &pathToImage, const RenderOptions &renderOptions, const crt_probe_volume &volume,
+                                    const std::vector<crt_probe> &probes, const crt_probe_visibility *visibility = nullptr,
+                                    const std::vector<crt_probe_depth> *depth = nullptr, crt_probe_lit_stats *stats = nullptr);
+
   // ---- chain guides (crt_hip.h: "Chain guides", crt_guide_rays): for every ray the guide record of the surface it shows -- the chain of
   // closest hits through reflective and refractive meshes to the first diffuse or constant surface, a miss or maxBounces (<= 63) --, with
   // the path length as t and a tagged mesh; the biases come from renderOptions.  *status: a byte a ray (bits 0-5 the bounces, bit 7 cut),

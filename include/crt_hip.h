@@ -1351,6 +1351,90 @@ int crt_bake_probes_visible(crt_ctx *ctx, const crt_probe_volume *volume, const 
                             crt_probe *out_probes /* host, may be NULL */, crt_probe *d_probes /* device, may be NULL */,
                             crt_probe_depth *out_depth /* host, may be NULL */, crt_probe_depth *d_depth /* device, may be NULL */);
 
+/* ---- Probe-lit radiance: the radiance queries' picture with bounce light from an irradiance probe volume.  The three sections above make a
+ * light cache; the calls of this section are what reads it: a DIFFUSE record of a radiance query takes, in place of the GI build's
+ * gi_sample_size random sample rays, the EXPECTATION of their colours from the volume's SH9 records -- no sample ray is shot, so the result
+ * is free of noise and costs about what crt_shoot_rays_device costs.  Mirrors and glass recurse as they do in crt_shoot_rays_gi*, and the
+ * diffuse surfaces seen in them are lit from the volume too.  Kernel: csrc/kernel_probe_light.h; the rule, one header for host and device:
+ * csrc/probe_lit_rule.h.  It is additive: no existing call changes a byte, no existing kernel gets a new argument, and the frame kernels of
+ * crt_render* are not involved.  Single-device contexts only.
+ *
+ * The rule (csrc/probe_lit_rule.h, verbatim; tests/probe_lit_sets.py restates it in numpy and the GPU gives its bits):
+ * Derivation.  In the GI build a DIFFUSE record's colour is (direct + c_0 + ... + c_{S-1}) * (1 / (float)(S + 1)), S = gi_sample_size,
+ *   c_i the colour shootRay returns for sample ray i (radiance_combine<true>, csrc/kernel_radiance.h).  gi_sample_direction
+ *   (csrc/kernel_lane.h) draws angle1 = pi * u1 and angle2 = 2 pi * u2, forms (cos angle1, sin angle1, 0) in the (right, normal, forward)
+ *   frame and rotates it about the normal by angle2: the angle alpha between the sample and the normal is |pi/2 - angle1|, uniform on
+ *   [0, pi/2], and the azimuth is uniform.  The density per solid angle is p(omega) = 1 / (pi^2 sin alpha) on the normal's hemisphere; it
+ *   depends on the normal alone.  The expectation of one sample's colour, Lbar(x, n) = the integral of L(x, omega) p(omega) d omega, is a
+ *   zonal convolution of the incoming radiance, and by Funk-Hecke its SH band factors are
+ *       lambda_l = (2 / pi) * the integral over [0, pi/2] of P_l(cos alpha) d alpha:   lambda_0 = 1, lambda_1 = 2 / pi, lambda_2 = 1 / 4
+ *   where csrc/probe_rule.h's clamped-cosine lookup has A = 1, 2/3, 1/4.
+ * Zonal resolve.  csrc/probe_rule.h's lookup -- or, with a visibility, csrc/probe_depth_rule.h's -- in the finite test, the per-axis clamp,
+ *   the corner order, the skipped corners, the weights and the folds W and S[c][ch] (crt_probe_axis, crt_probe_sum_add, the depth tap and
+ *   the Chebyshev weight, all unchanged), resolved with the zonal table in place of A:
+ *     no corner used: status 0, Lbar = 0
+ *     e[ch] = the left fold over c = 0..8, starting from 0.0f, of (Z_c * Y_c(n)) * S[c][ch], Z = 1.0f, 0.63661975f (x3), 0.25f (x5)
+ *     q = e[ch] / W; Lbar[ch] = q > 0.0f ? q : 0.0f          (a NaN gives 0)
+ *     status = the number of corners used (1 to 8)
+ *   x is the record's point and n its normal as the crt_hit holds them (the normal radiance_scatter<true> hands to gi_sample_direction),
+ *   used as given and not normalised.  A point or normal that is not finite: status 0, Lbar = 0.
+ * Combine.  For a record whose status byte is CRT_SHADE_DIFFUSE, with direct[ch] the colour crt_shade_hits_device left:
+ *     ind = (float)S * Lbar[ch]
+ *     inv = 1.0f / (float)(S + 1u)
+ *     colour[ch] = (direct[ch] + ind) * inv
+ *   Every other record keeps its colour's bytes.  A DIFFUSE record of status 0 counts as UNLIT, every other DIFFUSE record as LIT.  With
+ *   S = 0 and a finite Lbar the colour is (direct + 0.0f) * 1.0f: direct as a float value.  The indirect term is multiplied by no albedo and
+ *   no texture: the reference's is not either (README, "Split GI frames").
+ *
+ * Known limits.
+ *   * The light is the volume's: as smooth as SH9 and the probe spacing make it, with the leaks the lookup in use has, and as old as the
+ *     last bake.  Re-baked volumes are not blended over time.
+ *   * Lbar is the mean of the GI build's estimator when the volume holds the radiance the sample rays would return; a volume baked with
+ *     max_depth - 1 and gi_sample_size S approximates that.  Nothing checks which options a volume was baked with.
+ *   * The indirect term carries no albedo (the reference has none).
+ *   * The frame kernels of crt_launch.hip do not read the volume: crt_render* give the bytes they gave.
+ *   * The query waits once a level: there is no enqueue-only or graph-capturable form.
+ *   * Single-device contexts only.
+ * crt_probe_light_hits_device only ENQUEUES one kernel on `stream`, as the probe primitives above: no wait, no allocation, no memset or copy
+ *   node, so it can be captured.  For each of the n records (n < 2^31) whose d_status byte is CRT_SHADE_DIFFUSE it reads the point and the
+ *   normal of d_hits[i] and the direct light d_rgb[3i ..] as crt_shade_hits_device left it, and writes the combined colour over it; every
+ *   other record's colour keeps its bytes.  visibility NULL: the plain lookup, and d_depth is not read; otherwise the Chebyshev-weighted
+ *   one, and d_depth must not be NULL.  d_counts (may be NULL; two 64-bit words aligned to 8 bytes, which the CALLER clears): [0] += the LIT
+ *   records, [1] += the UNLIT ones.  It refuses what crt_probe_irradiance_visible_device refuses -- a NULL or invalid volume, an invalid
+ *   visibility, n >= 2^31, a NULL array with work to do, d_probes or d_depth not aligned to 16 bytes --, and gi_sample_size > 64.  n == 0 is
+ *   CRT_OK and touches nothing.  Two runs give the same bytes.
+ * crt_shoot_rays_lit_device: the colours of n rays on `stream`, as crt_shoot_rays_gi_device takes rays and gives colours (level by level,
+ *   GI occlusion rule, one wait a level), run with gi_sample_size = 0 and with the launch above behind every level's lighting launches,
+ *   which gets options->gi_sample_size as S.  options->use_gi must be 1.  There are no keys: nothing random is drawn.  With
+ *   gi_sample_size = 0 the colours are crt_shoot_rays_gi_device's with gi_sample_size = 0 as float values.  It is CRT_ERR_INVALID, with
+ *   nothing enqueued, for what crt_shoot_rays_gi_device refuses, for what the primitive refuses of the volume, and on a stream that is being
+ *   captured.  crt_get_shoot_stats describes the call as it describes a crt_shoot_rays_gi_device call.  crt_shoot_rays_lit is its host
+ *   variant: rays, probes, depth and out_rgb are host memory (n < 2^31); it copies in, runs on the context's stream, copies out and waits.
+ * crt_render_probe_lit: the frame.  The camera's rays (crt_camera_rays_device) of EVERY pixel, shot as CRT_RAY_PRIMARY rays through
+ *   crt_shoot_rays_lit_device into the persistent colour buffer, then the quantiser (crt_quantize_device); out_rgb (host, H x W x 3 floats)
+ *   and out_rgb8 (host, H x W x 3 bytes) may each be NULL.  d_probes and d_depth are device memory.  It waits for a pending frame, ends a
+ *   progressive frame under way as crt_render* do, and returns when the copies have landed.  crt_render_probe_lit_host is the same call for records in HOST memory (probes, depth): it copies them to the
+ *   device first.
+ * crt_get_probe_lit_stats: the LIT and UNLIT records of the last crt_shoot_rays_lit* or crt_render_probe_lit call, over all its levels and
+ *   passes (waits for it); lit + unlit = that call's crt_shoot_stats::shadow_records.  crt_shoot_stats gains nothing. */
+typedef struct crt_probe_lit_stats { uint64_t lit, unlit; } crt_probe_lit_stats;
+int crt_probe_light_hits_device(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe_visibility *visibility /* may be NULL */,
+                                const crt_probe *d_probes, const crt_probe_depth *d_depth /* may be NULL without a visibility */, const crt_hit *d_hits,
+                                const uint8_t *d_status, uint64_t n, uint32_t gi_sample_size, float *d_rgb /* in: direct light, out: the lit colour */,
+                                uint64_t *d_counts /* may be NULL */, void *stream);
+int crt_shoot_rays_lit_device(crt_ctx *ctx, const crt_ray *d_rays, uint64_t n, uint32_t ray_type, const crt_options *options,
+                              const crt_probe_volume *volume, const crt_probe_visibility *visibility /* may be NULL */, const crt_probe *d_probes,
+                              const crt_probe_depth *d_depth /* may be NULL without a visibility */, float *d_rgb, void *stream);
+int crt_shoot_rays_lit(crt_ctx *ctx, const crt_ray *rays, uint64_t n, uint32_t ray_type, const crt_options *options, const crt_probe_volume *volume,
+                       const crt_probe_visibility *visibility /* may be NULL */, const crt_probe *probes, const crt_probe_depth *depth, float *out_rgb);
+int crt_render_probe_lit(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe_visibility *visibility /* may be NULL */, const crt_probe *d_probes,
+                         const crt_probe_depth *d_depth /* may be NULL without a visibility */, const crt_options *options, float *out_rgb /* may be NULL */,
+                         uint8_t *out_rgb8 /* may be NULL */);
+int crt_render_probe_lit_host(crt_ctx *ctx, const crt_probe_volume *volume, const crt_probe_visibility *visibility /* may be NULL */, const crt_probe *probes,
+                              const crt_probe_depth *depth /* may be NULL without a visibility */, const crt_options *options, float *out_rgb /* may be NULL */,
+                              uint8_t *out_rgb8 /* may be NULL */);
+int crt_get_probe_lit_stats(crt_ctx *ctx, crt_probe_lit_stats *out);
+
 /* ---- one scene on several devices of one node, behind the same call (SURVEY.md section 8b "multi-GPU handled inside the
  * context"; the reference's counterpart is the bucket thread pool, RayTracer.cpp:141-158).  One context, host thread and
  * stream per listed device (a device may be listed more than once); the covered 8x8 tiles are dealt round-robin, every
